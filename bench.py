@@ -16,12 +16,22 @@ all-reduce(SUM) of the counts picks the winner, as a sharded search round
 does.  The collectives are the library's own (pow_group_allreduce_u64: RCCL
 called from C++, mpi_blockchain_amd/csrc/pow_group.cpp), not torch's.
 
-Config 4's cooperative search is measured beside it (outside the timed
-region): `group_search` = time-to-block of pow_group_mine_any over all N GPUs
-(every GPU mines a static shard of one template; the first hit stops the
-others through the stop board; one all-reduce agrees on the winner).
+A plain run does only what that headline needs: set-up, W warm-up steps, the
+K timed steps, and the result line (`ms_per_step` = wall ms of one timed
+step).  `--dump-outputs DIR` also writes what the last timed step computed
+(dump_outputs below), so that two builds can be compared output for output.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+`--full` adds everything else the benchmark measures or checks, each outside
+the timed region: the per-rank parity check of the timed step's solution list
+against the committed fingerprints, the measured VALU ceilings and the live
+rocprofv3 counter passes of the roofline block, each GPU's clock under load,
+the CPU baseline, the difficulty ladder, the protocol runs, and config 4's
+cooperative search: `group_search` = time-to-block of pow_group_mine_any over
+all N GPUs (every GPU mines a static shard of one template; the first hit
+stops the others through the stop board; one all-reduce agrees on the winner).
+The `--no-*` options leave single blocks out of a `--full` run.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 
 Without a launcher, `--gpus N` (N > 1) starts the second form itself as a
@@ -55,8 +65,9 @@ class RankPhases:
     be killed at the driver's limit with nothing written.  Instead every rank:
 
     * walks through named phases (import -> process_group -> device_init ->
-      group_init -> topology -> warmup -> steps -> parity -> group_search ->
-      protocol / report), each with a time budget, under one job deadline
+      group_init -> topology -> warmup -> steps -> dump_outputs -> parity ->
+      group_search -> protocol / report; a plain run has no parity,
+      group_search or protocol phase), each with a time budget, under one job deadline
       (BENCH_DEADLINE_S, default 570 s: inside the driver's 600 s limit);
     * on an exception, a phase or job deadline, or SIGTERM (torch.distributed.run
       stops the surviving ranks that way once one rank has failed), writes ONE
@@ -895,6 +906,34 @@ def list_fingerprint(buf, n: int) -> str:
     return hashlib.sha256(a.astype("<u4").tobytes()).hexdigest()
 
 
+DUMP_MAX_ENTRIES = 4_000_000  # 32 MB as float64
+
+
+def dump_outputs(dirpath: str, buf, n: int, total: int, lowest) -> dict:
+    """--dump-outputs: what the last timed step gave its caller, as float64
+    .npy files (every value is an integer below 2^53: exact):
+      * count.npy     [1]  solving counters found, whole job (the step's sum);
+      * lowest.npy    [1]  lowest solving counter, whole job (-1: none);
+      * solutions.npy [m]  rank 0's device list of solving counters (relative to
+        the window's start), sorted ascending, since the kernel appends in no
+        fixed order.  A list longer than DUMP_MAX_ENTRIES is sampled: the
+        entries at DUMP_MAX_ENTRIES indices of the sorted list drawn without
+        replacement by numpy's default_rng(0), ascending.
+    The block, window and difficulty are fixed by the arguments, so the files
+    of two runs with the same arguments are equal."""
+    import numpy as np
+
+    os.makedirs(dirpath, exist_ok=True)
+    a = np.sort(buf.read_u32(n))
+    if a.size > DUMP_MAX_ENTRIES:
+        a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ENTRIES, replace=False))]
+    np.save(os.path.join(dirpath, "count.npy"), np.array([total], dtype=np.float64))
+    np.save(os.path.join(dirpath, "lowest.npy"), np.array([-1 if lowest is None else lowest], dtype=np.float64))
+    np.save(os.path.join(dirpath, "solutions.npy"), a.astype(np.float64))
+    return {"dir": dirpath, "files": ["count.npy", "lowest.npy", "solutions.npy"], "solutions_listed": n,
+            "solutions_written": int(a.size)}
+
+
 def launch_plan(gpus: int, env) -> str:
     """How this process runs `bench.py --gpus N`:
       * "run"      — it is one rank already (WORLD_SIZE set by the launcher and
@@ -997,6 +1036,11 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--difficulty", type=int, default=9)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beside the headline (parity, ceilings, counters, "
+                         "CPU baseline, ladder, group search, protocol); the --no-* options leave blocks out of it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ladder", action="store_true")
     ap.add_argument("--no-peak", action="store_true")
@@ -1004,6 +1048,11 @@ def main():
     ap.add_argument("--no-group-search", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 traffic passes")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: the headline only
+        args.no_cpu_baseline = args.no_ladder = args.no_peak = args.no_protocol = True
+        args.no_group_search = args.no_pmc = True
 
     plan = launch_plan(args.gpus, os.environ)
     if plan == "self":
@@ -1071,12 +1120,15 @@ def run_rank(args, ph: RankPhases, world: int, rank: int, local: int) -> None:
         os.environ["POW_TEST_RCCL_LIB"] = STUB_LIB
     miner = GpuMiner(local, test_hooks=transport == "rccl_stub")
     # The library's own RCCL communicator (the id travels over torch.distributed);
-    # at N = 1 a one-rank group, used only by the group_search measurement.
+    # at N = 1 a one-rank group, used only by the group_search measurement
+    # (not formed without it).
     # pow_group_init gives up after 60 s if a peer never joins (RCCL's init on
     # a helper thread under a deadline).
     ph.enter("group_init", 120)
     group, group_err = None, None
-    if transport == "gloo":
+    if dist is None and args.no_group_search:
+        pass
+    elif transport == "gloo":
         group = ShardedMiner(miner, rank, world)
     else:
         try:
@@ -1173,18 +1225,29 @@ def run_rank(args, ph: RankPhases, world: int, rank: int, local: int) -> None:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
 
-    # Per-rank parity (outside the timed region): every rank's window whose
+    # What the last timed step computed, for a build-to-build comparison: the
+    # job's count and lowest counter, and rank 0's solution list.
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        ph.enter("dump_outputs", 120)
+        dumped = dump_outputs(args.dump_outputs, buf, min(local_last[0][0], cap), last[0], last[1])
+
+    # --full: per-rank parity (outside the timed region): every rank's window whose
     # fingerprints are committed (rank 0: [0, 2^32); rank 7: [7*2^32, 8*2^32),
     # the farthest window of an 8-GPU run) is checked against them.  With it,
     # each rank's own timing: its mean kernel ms and all-reduce ms per step and
     # its own steps' wall (a sub-linear N > 1 result is attributable from the
     # record: one slow GPU, the collective, or host time between them).
-    ph.enter("parity", 120)
     n_loc = local_last[0][0]
-    local_last[0] = (*local_last[0], list_fingerprint(buf, n_loc) if d == 9 and n_loc <= cap else None)
-    if dist is not None:
-        dist.barrier()  # every GPU loaded at once for the clock probe
-    my_timing = rank_timing(rank, kernel_ms, allreduce_ms, el_own, args.steps, loaded_clock_ghz(miner))
+    fp, clock = None, None
+    if args.full:
+        ph.enter("parity", 120)
+        fp = list_fingerprint(buf, n_loc) if d == 9 and n_loc <= cap else None
+        if dist is not None:
+            dist.barrier()  # every GPU loaded at once for the clock probe
+        clock = loaded_clock_ghz(miner)
+    local_last[0] = (*local_last[0], fp)
+    my_timing = rank_timing(rank, kernel_ms, allreduce_ms, el_own, args.steps, clock)
     per_rank = [(local_last[0], my_timing)]
     if dist is not None:
         per_rank = [None] * world
@@ -1281,7 +1344,7 @@ def run_rank(args, ph: RankPhases, world: int, rank: int, local: int) -> None:
     # sanity/parity at full size: rank 0's window is the golden 2^32 window
     parity = {"solutions_rank0": per_rank[0][0], "solutions_all_ranks": last[0], "lowest": last[1]}
     checked = {}
-    for r, (n_r, mn_r, fp_r) in enumerate(per_rank):
+    for r, (n_r, mn_r, fp_r) in enumerate(per_rank if args.full else []):
         fpp = os.path.join(ROOT, "tests", "golden",
                            "fingerprints_2p32.json" if r == 0 else f"fingerprints_2p32_S0_at{r * WINDOW}.json")
         if d == 9 and os.path.exists(fpp):
@@ -1289,7 +1352,8 @@ def run_rank(args, ph: RankPhases, world: int, rank: int, local: int) -> None:
             checked[str(r)] = {"solutions": n_r, "expected": want["count"],
                                "ok": n_r == want["count"] and mn_r == r * WINDOW + want["first"][0],
                                "fingerprint_ok": fp_r == want["sha256_le_u32"]}
-    parity["unchecked_ranks"] = [r for r in range(world) if str(r) not in checked]
+    if args.full:
+        parity["unchecked_ranks"] = [r for r in range(world) if str(r) not in checked]
     if checked:
         parity["checked_ranks"] = checked
         parity["count_ok"] = all(c["ok"] for c in checked.values())
@@ -1303,6 +1367,7 @@ def run_rank(args, ph: RankPhases, world: int, rank: int, local: int) -> None:
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": round(1e3 * el / args.steps, 3),
         "higher_is_better": True,
         "scaling": "weak",
@@ -1321,8 +1386,11 @@ def run_rank(args, ph: RankPhases, world: int, rank: int, local: int) -> None:
                                    info["cu_count"]),
         "device": info,
         "parity": parity,
-        "topology": topology,
     }
+    if had_group or world > 1:  # a plain one-GPU run forms no group: nothing to self-check
+        res["topology"] = topology
+    if dumped is not None:
+        res["outputs"] = dumped
     if world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline()
     if world == 1 and not args.no_ladder:

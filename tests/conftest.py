@@ -33,3 +33,11 @@ def fingerprints():
 @pytest.fixture(scope="session")
 def templates(golden):
     return {t["name"]: t for t in golden["templates"]}
+
+
+@pytest.fixture(scope="session")
+def reference_vectors():
+    """Outputs of the reference's own build for the tests' fixed inputs
+    (tests/golden/gen_reference_vectors.py)."""
+    with open(os.path.join(GOLDEN, "reference_vectors.json")) as f:
+        return json.load(f)

@@ -49,6 +49,21 @@ REF_LOG_CHAIN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__f
                              "ref_log_chain")
 
 
+DUMP_RULE = "-" * 20 + "\n"
+
+
+def restated_dump(entries) -> bytes:
+    """reference_dump's bytes, restated: the termination message, then every
+    block between two rules.  Pinned to the reference's recorded dumps
+    (tests/golden/reference_vectors.json) by tests/test_node_host.py; the GPU
+    tests compare against it where oracle/_ref/ref_log_chain is not built."""
+    s = "Terminé con la siguiente cadena\n" + DUMP_RULE + "Mi blockchain es la siguiente en \n"
+    for e in entries:
+        s += (f"{DUMP_RULE}Block number: {e.index}\nOwner: {e.owner}\nPrevious block hash: {e.prev}\n"
+              f"Block hash: {e.hash}\n{DUMP_RULE}")
+    return s.encode()
+
+
 def reference_dump(entries, rank: int) -> bytes:
     """The bytes the REFERENCE's log_msg + log_chain (node.cpp:40-68, run as
     proof_of_work's termination does, node.cpp:286-289) write for this chain

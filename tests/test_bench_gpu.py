@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_json_contract():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full",
                         "--no-ladder", "--no-cpu-baseline", "--no-peak", "--no-protocol"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -44,6 +44,46 @@ def test_bench_json_contract():
     # no figure labelled "busy" above 100 % (counter_defs' VALUBusy prices SIMD-16 issue)
     assert 0 < r["valu_busy_pct_simd32"] <= 100, r
     assert not [k for k, v in r.items() if "busy" in k and isinstance(v, (int, float)) and v > 100], r
+
+
+def test_bench_plain_run_and_dump(tmp_path):
+    """Without --full: the headline only (no extra block in the line), and
+    --dump-outputs writes the last timed step's outputs: the count and lowest
+    counter of S0's [0, 2^32) window at d = 9 equal the committed fingerprint
+    file's, the solution list is the fixed sample, ascending, in float64."""
+    import numpy as np
+
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 0
+    assert d["unit"] == "trials/s" and d["dtype"] == "u32" and d["higher_is_better"] is True
+    # value = 2^32 trials per step over ms_per_step; the kernel is most of the step
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 / 2 ** 32 - 1) < 1e-3, d
+    assert 0 < d["kernel_ms_per_step"] <= d["ms_per_step"] < 2 * d["kernel_ms_per_step"], d
+    for k in ("cpu_baseline", "ladder", "group_search", "protocol", "topology"):
+        assert k not in d, k
+    r = d["roofline"]
+    assert "counters_live" not in r and "microbench_full_rate" not in r["peak_detail"], r
+    assert "checked_ranks" not in d["parity"] and d["timing"]["per_rank_clock_ghz"] == [None], d
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "fingerprints_2p32.json")))["ladder"]["9"]
+    files = sorted(os.listdir(out))
+    assert files == ["count.npy", "lowest.npy", "solutions.npy"] == sorted(d["outputs"]["files"])
+    assert sum(os.path.getsize(out / f) for f in files) <= 64_000_000
+    a = {f[:-4]: np.load(out / f) for f in files}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert a["count"].tolist() == [want["count"]] == [d["parity"]["solutions_all_ranks"]]
+    assert a["lowest"].tolist() == [want["first"][0]]
+    s = a["solutions"]
+    sys.path.insert(0, ROOT)
+    import bench
+
+    assert s.size == bench.DUMP_MAX_ENTRIES == d["outputs"]["solutions_written"] < want["count"]
+    assert s[0] >= want["first"][0] and s[-1] < 2 ** 32 and np.all(np.diff(s) > 0) and np.all(s == np.floor(s))
 
 
 def test_valu_microbench_ceilings():
@@ -95,7 +135,7 @@ def run_rehearsal(n: int, transport: str = "gloo") -> dict:
     env = dict(os.environ, BENCH_REHEARSAL="1", BENCH_REHEARSAL_TRANSPORT=transport)
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n),
                         "--master-addr", "127.0.0.1", "--master-port", str(port),
-                        os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "1", "--warmup", "1"],
+                        os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "1", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -328,3 +328,69 @@ def test_board_summary():
     b = bench.board_summary([dict(ok_rank, rank=r) for r in range(2)], [460_000.0, 470_000.0], 2)
     assert b["all_ranks_board"] and b["peers_stopped_by_board"] is False  # bound, but not stopping peers
     assert bench.board_summary([dict(ok_rank, rank=0)], [], 1)["peers_stopped_by_board"] is None
+
+
+class FakeList:
+    """A device buffer's read_u32: the list in the order the kernel left it."""
+
+    def __init__(self, values):
+        self.values = values
+
+    def read_u32(self, n):
+        import numpy as np
+
+        return np.array(self.values[:n], dtype=np.uint32)
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: count, lowest and the ascending list as float64; a list
+    above DUMP_MAX_ENTRIES is cut to the same seeded sample whatever order the
+    kernel appended in; counters near 2^32 and 2^35 stay exact."""
+    import numpy as np
+
+    rng = np.random.default_rng(5)
+    vals = np.unique(rng.integers(0, 1 << 32, 5000, dtype=np.uint64)).astype(np.uint32)
+    vals[-1] = (1 << 32) - 1
+    shuffled = rng.permutation(vals)
+    info = bench.dump_outputs(str(tmp_path / "a"), FakeList(shuffled), len(vals), 3 * len(vals), (7 << 32) + 5)
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(info["files"]) == ["count.npy", "lowest.npy", "solutions.npy"]
+    a = {f: np.load(tmp_path / "a" / f) for f in info["files"]}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert a["count.npy"].tolist() == [3 * len(vals)] and a["lowest.npy"].tolist() == [(7 << 32) + 5]
+    assert a["solutions.npy"].tolist() == sorted(vals.tolist()) and a["solutions.npy"][-1] == 2.0 ** 32 - 1
+    assert info["solutions_listed"] == info["solutions_written"] == len(vals)
+    # no solution at all
+    bench.dump_outputs(str(tmp_path / "none"), FakeList([]), 0, 0, None)
+    assert np.load(tmp_path / "none" / "lowest.npy").tolist() == [-1] and np.load(
+        tmp_path / "none" / "solutions.npy").size == 0
+    # sampled: the same entries from two appending orders, ascending, all from the list
+    monkeypatch.setattr(bench, "DUMP_MAX_ENTRIES", 1000)
+    i1 = bench.dump_outputs(str(tmp_path / "b"), FakeList(shuffled), len(vals), len(vals), int(vals.min()))
+    bench.dump_outputs(str(tmp_path / "c"), FakeList(shuffled[::-1]), len(vals), len(vals), int(vals.min()))
+    b, c = np.load(tmp_path / "b" / "solutions.npy"), np.load(tmp_path / "c" / "solutions.npy")
+    assert i1["solutions_written"] == b.size == 1000 and np.array_equal(b, c)
+    assert np.all(np.diff(b) > 0) and set(b.tolist()) <= set(vals.tolist())
+
+
+def test_plain_run_switches_the_extras_off(monkeypatch):
+    """Without --full every block beside the headline is off; with it the
+    --no-* options still leave single blocks out."""
+    seen = []
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(bench, "RankPhases", lambda *a: type("P", (), {"start": lambda self: self})())
+    monkeypatch.setattr(bench, "run_rank", lambda args, *a: seen.append(args))
+    for argv in (["--gpus", "1", "--steps", "3", "--warmup", "1"], ["--full", "--no-ladder", "--dump-outputs", "d"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        bench.main()
+    plain, full = seen
+    off = ("no_cpu_baseline", "no_ladder", "no_peak", "no_protocol", "no_group_search", "no_pmc")
+    assert not plain.full and all(getattr(plain, k) for k in off) and plain.dump_outputs is None
+    assert plain.steps == 3 and plain.warmup == 1
+    assert full.full and full.no_ladder and not any(getattr(full, k) for k in off if k != "no_ladder")
+    assert full.dump_outputs == "d"
+    import pytest
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2

@@ -40,25 +40,30 @@ def _chain(n: int, rng):
 
 
 @pytest.mark.parametrize("n", [1, 10, 37])
-def test_chain_dump_matches_reference(tmp_path, n):
+def test_chain_dump_matches_reference(tmp_path, n, reference_vectors):
     """pow_node's termination dump (log_msg + log_chain,
     run through pow_node_test --log-chain-stdin: the same member functions,
     no MPI, no GPU) is byte-identical to what the reference's own node.cpp
-    writes for the same chain (oracle/_ref/ref_log_chain), and parses back
-    into the chain (mpi_blockchain_amd.node.parse_chain_dump)."""
+    writes for the same chain (oracle/_ref/ref_log_chain; its dumps of these
+    chains are recorded in tests/golden/reference_vectors.json, and where the
+    binary is built it is run too), and parses back into the chain
+    (mpi_blockchain_amd.node.parse_chain_dump)."""
     import os
     import random
 
-    from helpers import REF_LOG_CHAIN, reference_dump
+    from helpers import REF_LOG_CHAIN, reference_dump, restated_dump
     from mpi_blockchain_amd.node import parse_chain_dump
 
-    if not os.path.exists(REF_LOG_CHAIN):
-        pytest.skip("oracle/_ref/ref_log_chain not built (needs /root/reference)")
+    rec = reference_vectors["log_chain"]
+    want = rec["dumps_latin1"][str(n)].encode("latin-1")
     chain = _chain(n, random.Random(n))
+    assert restated_dump(chain) == want  # the GPU tests' stand-in where the reference binary is not built
+    if os.path.exists(REF_LOG_CHAIN):
+        assert reference_dump(chain, rec["rank"]) == want
     tsv = "".join(f"{e.index}\t{e.owner}\t{e.prev}\t{e.hash}\n" for e in chain)
-    p = subprocess.run([build_node(test=True), "--log-chain-stdin", "5"], input=tsv.encode(), cwd=str(tmp_path),
-                       env=mpi_env(), capture_output=True, timeout=60)
+    p = subprocess.run([build_node(test=True), "--log-chain-stdin", str(rec["rank"])], input=tsv.encode(),
+                       cwd=str(tmp_path), env=mpi_env(), capture_output=True, timeout=60)
     assert p.returncode == 0, p.stderr
-    ours = (tmp_path / "5.out").read_bytes()
-    assert ours == reference_dump(chain, 5)
+    ours = (tmp_path / f"{rec['rank']}.out").read_bytes()
+    assert ours == want
     assert parse_chain_dump(ours.decode()) == chain

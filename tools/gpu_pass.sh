@@ -6,7 +6,7 @@
 # steps:
 #   tests            the whole GPU suite (pytest -m gpu)
 #   smoke            __graft_entry__.smoke()
-#   bench            python bench.py (default: N = 1, every block of the JSON line)
+#   bench            python bench.py --full (N = 1, every block of the JSON line)
 #   profile          tools/profile_round.sh r06 (kernel trace + 4 PMC passes of the bench workload)
 #   rehearse N T     bench.py's N > 1 path with N ranks sharing the GPU (BENCH_REHEARSAL=1), transport T
 #                    (gloo | rccl_stub): the JSON line with timing, board and placement blocks
@@ -41,12 +41,12 @@ while [ $# -gt 0 ]; do
     tests) POW_NODE_LOG_DIR="$R/gpurun_out/netlogs" \
              $S gputests 900 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread || exit $? ;;
     smoke) $S smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
-    bench) $S bench 900 python -u bench.py || exit $? ;;
+    bench) $S bench 900 python -u bench.py --full || exit $? ;;
     profile) bash "$R/tools/profile_round.sh" r06 || exit $? ;;
     rehearse) n=$1; tr=$2; shift 2
       BENCH_REHEARSAL=1 BENCH_REHEARSAL_TRANSPORT=$tr $S rehearse_${n}_$tr 900 python -u -m torch.distributed.run \
         --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus "$n" \
-        --steps 2 --warmup 1 || exit $? ;;
+        --steps 2 --warmup 1 --full || exit $? ;;
     fuzz) $S fuzz 900 python -u tests/parity_fuzz.py --cases 1000 --seed 404 || exit $? ;;
     fuzz_big) $S fuzz_big 900 python -u tests/parity_fuzz.py --cases 10000 --seed 4004 &&
       POW_LAT_WPS=4 $S fuzz_lat_asm 900 python -u tests/parity_fuzz.py --test-hooks --cases 2000 --seed 4005 &&
