@@ -11,7 +11,7 @@ import os
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libpow_gpu.so")
-# The same library built with -DPOW_TEST_HOOKS (build.py): test and tuning
+# The same objects plus csrc/pow_hooks.cpp (build.py TEST_ONLY): test and tuning
 # switches read from the environment at pow_init.  Only tests load it.
 TEST_LIB_PATH = os.path.join(PKG, "libpow_gpu_test.so")
 

@@ -5,6 +5,7 @@ git-ignored but travels to the GPU box with the gpurun snapshot, so the GPU
 tests load exactly this file.
 
     python -m mpi_blockchain_amd.build [--force]
+    python -m mpi_blockchain_amd.build --sources [--test]   # the source paths of a library, one per line
 """
 from __future__ import annotations
 
@@ -17,9 +18,10 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libpow_gpu.so")
-SOURCES = ["pow_api.cpp", "pow_aql.cpp", "pow_board.cpp", "pow_group.cpp", "pow_kernels.hip", "pow_sort.hip", "valu_peak.hip",
-           "pow_test_kernels.hip"]
-HEADERS = ["pow_template.h", "sha256_dev.h", "pow_aql.h"]
+# In link order; every library links its sources in this order (the shipped one without TEST_ONLY).
+SOURCES = ["pow_board.cpp", "pow_kernels.hip", "pow_sort.hip", "valu_peak.hip", "pow_api.cpp", "pow_group.cpp", "pow_host.cpp",
+           "pow_hooks.cpp", "pow_aql.cpp", "pow_test_kernels.hip"]
+HEADERS = ["pow_template.h", "sha256_dev.h", "pow_aql.h", "pow_host.h", "pow_ctx.h"]
 INCLUDES = [os.path.join(ROOT, "include", h) for h in ("pow_gpu.h", "pow_tools.h")]
 ARCH = "gfx950"
 
@@ -35,18 +37,23 @@ def _inputs() -> list[str]:
     return [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + INCLUDES
 
 
-# Test build: the same kernels and API with -DPOW_TEST_HOOKS, i.e. the test and
-# tuning switches read from the environment at pow_init (POW_FORCE_FULL,
-# POW_FAULT_INJECT, POW_LAT_MAX, POW_LAT_WPS, POW_GRID_PER_CU) and the RCCL
-# library override (POW_TEST_RCCL_LIB, tests/stub_rccl).  The shipped
-# libpow_gpu.so has none of them; only tests load this one.
+# Test library: the shipped library's objects plus TEST_ONLY.  pow_hooks.cpp
+# fills the seam of csrc/pow_ctx.h as the library loads: the test and tuning
+# switches read from the environment at pow_init (POW_FORCE_FULL,
+# POW_FAULT_INJECT, POW_LAT_MAX, POW_LAT_WPS, POW_GRID_PER_CU, ...), the RCCL
+# library override (POW_TEST_RCCL_LIB, tests/stub_rccl) and direct AQL
+# dispatch (pow_aql.cpp: round 4's K1'/K2' launch path, opt-in with POW_AQL=1),
+# with the watchdog tests' stall kernel.  The shipped libpow_gpu.so has none of
+# them: it launches every kernel through hipLaunchKernel and does not link the
+# HSA runtime.  Only tests load this one.
 TEST_LIB = os.path.join(PKG, "libpow_gpu_test.so")
 OBJ = os.path.join(ROOT, "build", "obj")  # git- and gpurun-ignored: the .so files travel, not the objects
-HOOKED = ("pow_api.cpp", "pow_group.cpp")  # the sources that differ between the two builds
-# Direct AQL dispatch (round 4's K1'/K2' launch path): linked into the test
-# library only, opt-in there with POW_AQL=1.  The shipped library launches
-# every kernel through hipLaunchKernel and does not link the HSA runtime.
-TEST_ONLY = ("pow_aql.cpp", "pow_test_kernels.hip")  # + the watchdog tests' stall kernel
+TEST_ONLY = ("pow_hooks.cpp", "pow_aql.cpp", "pow_test_kernels.hip")
+
+
+def sources(test: bool = False) -> list[str]:
+    """The source files of libpow_gpu.so, or of libpow_gpu_test.so (test=True)."""
+    return [os.path.join(CSRC, s) for s in SOURCES if test or s not in TEST_ONLY]
 
 
 def _flags() -> list[str]:
@@ -61,10 +68,10 @@ def up_to_date(lib: str = LIB) -> bool:
     return all(os.path.getmtime(p) <= t for p in _inputs())
 
 
-def _compile(src: str, obj: str, defs: tuple[str, ...], verbose: bool) -> None:
+def _compile(src: str, obj: str, verbose: bool) -> None:
     if os.path.exists(obj) and all(os.path.getmtime(p) <= os.path.getmtime(obj) for p in _inputs()):
         return
-    cmd = [hipcc(), *_flags(), *defs, "-c", os.path.join(CSRC, src), "-o", obj + ".tmp"]
+    cmd = [hipcc(), *_flags(), "-c", src, "-o", obj + ".tmp"]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.run(cmd, check=True, cwd=ROOT)
@@ -73,30 +80,20 @@ def _compile(src: str, obj: str, defs: tuple[str, ...], verbose: bool) -> None:
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """libpow_gpu.so (shipped) and libpow_gpu_test.so (tests).  Every source
-    is compiled once; pow_api.cpp and pow_group.cpp once more with
-    -DPOW_TEST_HOOKS for the test library."""
+    is compiled exactly once; the test library is the shipped one's objects
+    plus those of TEST_ONLY."""
     if not force and up_to_date(LIB) and up_to_date(TEST_LIB):
         return LIB
     os.makedirs(OBJ, exist_ok=True)
     if force:
         for f in os.listdir(OBJ):
             os.remove(os.path.join(OBJ, f))
-    common, plain, hooked = [], [], []
-    for s in SOURCES:
-        base = os.path.splitext(s)[0]
-        if s in TEST_ONLY:
-            hooked.append(os.path.join(OBJ, base + ".test.o"))
-            _compile(s, hooked[-1], ("-DPOW_TEST_HOOKS",), verbose)
-        elif s in HOOKED:
-            plain.append(os.path.join(OBJ, base + ".o"))
-            hooked.append(os.path.join(OBJ, base + ".test.o"))
-            _compile(s, plain[-1], (), verbose)
-            _compile(s, hooked[-1], ("-DPOW_TEST_HOOKS",), verbose)
-        else:
-            common.append(os.path.join(OBJ, base + ".o"))
-            _compile(s, common[-1], (), verbose)
-    for lib, objs in ((LIB, plain), (TEST_LIB, hooked)):
-        cmd = [hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", *common, *objs, "-o", lib + ".tmp"]
+    obj = {s: os.path.join(OBJ, os.path.splitext(os.path.basename(s))[0] + ".o") for s in sources(test=True)}
+    for s, o in obj.items():
+        _compile(s, o, verbose)
+    for lib in (LIB, TEST_LIB):
+        cmd = [hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", *(obj[s] for s in sources(lib == TEST_LIB)),
+               "-o", lib + ".tmp"]
         if lib == TEST_LIB:  # pow_aql.cpp: direct dispatch
             cmd += ["-L", "/opt/rocm/lib", "-lhsa-runtime64", "-Wl,-rpath,/opt/rocm/lib"]
         if verbose:
@@ -169,6 +166,9 @@ def build_node(force: bool = False, verbose: bool = False, test: bool = False) -
 
 
 if __name__ == "__main__":
+    if "--sources" in sys.argv:
+        print("\n".join(sources(test="--test" in sys.argv)))
+        sys.exit(0)
     print(build(force="--force" in sys.argv, verbose=True))
     print(build_node(force="--force" in sys.argv, verbose=True))
     print(build_node(force="--force" in sys.argv, verbose=True, test=True))

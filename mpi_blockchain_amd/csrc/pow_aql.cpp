@@ -51,7 +51,6 @@
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
 #include <sys/stat.h>
-#include <time.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -64,7 +63,7 @@
 #include <vector>
 
 #include "pow_aql.h"
-#include "pow_template.h"
+#include "pow_host.h"
 
 namespace {
 
@@ -319,12 +318,6 @@ constexpr int kQueueDead = 0x7D0D;
 void on_queue_error(hsa_status_t st, hsa_queue_t*, void* data) {
   static_cast<std::atomic<int>*>(data)->store((int)st, std::memory_order_release);
 }
-
-uint64_t now_ns() {
-  timespec t;
-  clock_gettime(CLOCK_MONOTONIC, &t);
-  return (uint64_t)t.tv_sec * 1000000000ull + (uint64_t)t.tv_nsec;
-}
 }  // namespace
 
 int pow_aql_open(int device, unsigned flags, pow_aql** out, std::string* why) {
@@ -522,7 +515,7 @@ int pow_aql_dispatch(pow_aql* a, int kernel, uint32_t workgroups, uint32_t wg_si
       a->queue_error->compare_exchange_strong(zero, kQueueDead, std::memory_order_acq_rel);
       return refuse("the queue reported an error");
     }
-    if ((n & 1023u) == 1023u && now_ns() > deadline_ns) {
+    if ((n & 1023u) == 1023u && mono_ns() > deadline_ns) {
       int zero = 0;
       a->queue_error->compare_exchange_strong(zero, kQueueDead, std::memory_order_acq_rel);
       return refuse("no free packet slot before the deadline; the queue is marked dead");

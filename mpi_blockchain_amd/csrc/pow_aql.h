@@ -1,6 +1,6 @@
-// Direct AQL dispatch of the latency-bound kernels (pow_aql.cpp).  Compiled
-// into the TEST library only (libpow_gpu_test.so, -DPOW_TEST_HOOKS, opt-in
-// with POW_AQL=1): the shipped libpow_gpu.so launches every kernel through
+// Direct AQL dispatch of the latency-bound kernels (pow_aql.cpp).  Linked
+// into the TEST library only (libpow_gpu_test.so, called from pow_hooks.cpp,
+// opt-in with POW_AQL=1): the shipped libpow_gpu.so launches every kernel through
 // hipLaunchKernel ("Direct dispatch, round 5").  Not part of the
 // C ABI.
 #pragma once

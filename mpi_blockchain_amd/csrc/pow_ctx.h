@@ -1,0 +1,129 @@
+// The context of the C ABI and what pow_api.cpp shares with the test
+// library's hooks (pow_hooks.cpp).  Private to csrc/; not part of the C ABI.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <string>
+
+#include "pow_host.h"
+
+#define HIP_OK(expr)                                                                       \
+  do {                                                                                     \
+    hipError_t e_ = (expr);                                                                \
+    if (e_ != hipSuccess)                                                                  \
+      return fail(POW_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
+                  __LINE__);                                                               \
+  } while (0)
+
+struct pow_aql;  // the direct dispatcher (pow_aql.h): test library only
+
+struct pow_ctx {
+  int device = 0;
+  int cu_count = 0;
+  int clock_khz = 0;
+  int realtime_khz = 100000;  // s_memrealtime rate (hipDeviceAttributeWallClockRate)
+  uint32_t lat_seq = 0;       // K1' launches so far (PowLaunchLat::seq)
+  PowConstsLat lat_consts{};  // K1''s kernel argument (the subset of h_blob->consts it reads)
+  char name[256] = {0};
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t ev_block = nullptr;  // polled with sleeps during long launches
+  PowBlob* d_blob = nullptr;   // per-template constants + result words, one allocation
+  PowBlob* h_blob = nullptr;   // pinned staging copy: uploaded with one H2D per launch
+  bool consts_dirty = false;   // h_blob->consts not yet on the device
+  PowResult* d_lat = nullptr;           // latency kernel: self-resetting device result words ...
+  PowResult* h_lat = nullptr;           // ... published by its last wave here (mapped host memory)
+  PowHashOut* h_one = nullptr;          // K2' (pow_hash_block): digest + done word (mapped host memory)
+  PowHashOut* d_one = nullptr;          // device address of h_one
+  uint32_t one_seq = 0;                 // K2' launches so far (the done word's value)
+  PowResult* d_lat_host = nullptr;      // device address of h_lat
+  unsigned int* h_epoch = nullptr;      // pow_cancel's word: mapped, coherent host memory ...
+  unsigned int* d_epoch = nullptr;      // ... and its device address
+  std::atomic<bool> armed{false};       // pow_cancel has published an epoch
+  uint32_t launch_epoch = 0;            // mine calls: the caller's epoch ...
+  bool watch_epoch = false;             // ... watched on the GPU when armed
+  pow_board* board = nullptr;           // bound stop board (pow_board_bind) ...
+  const unsigned long long* board_dev = nullptr;  // ... its slots, device address
+  int board_slot = -1;
+  uint32_t board_tag = 0;
+  bool board_off = false;               // winner re-hash: not part of the search
+  PowConsts* d_consts = nullptr;  // = &d_blob->consts
+  PowResult* d_res = nullptr;     // = &d_blob->res
+  PowResult* h_res = nullptr;  // pinned read-back of d_res
+  uint32_t* d_tail = nullptr;  // sweep: per-wave remainders (< 32 each), appended after the launch
+  uint32_t tail_cap = 0;
+  uint32_t* d_out = nullptr;   // pow_sweep's device list and its radix-sort twin
+  uint32_t* d_alt = nullptr;
+  void* d_sort_tmp = nullptr;
+  size_t sort_tmp_bytes = 0;
+  size_t out_cap = 0;
+  uint32_t* d_msgs = nullptr;
+  uint32_t* d_dig = nullptr;
+  size_t hash_cap = 0;
+  unsigned grid_full = 0;  // workgroups that fill the chip (8 per CU)
+  // Set only by the test library's hooks (pow_hooks.cpp, at pow_init):
+  bool force_full = false;        // use the d > 32 kernel for every d
+  const char* fault_mine = nullptr;  // non-null: every pow_mine[_any] call fails with this text (failure-propagation tests)
+  uint64_t lat_max = 1ull << 24;  // first-sub-round cap for K1' (0 = K1 only)
+  unsigned lat_wps = 0;           // K1' waves per SIMD at every d (0 = the plan)
+  bool sentinel_idle = false;     // K1 mine launches: the sentinel wave takes no chunk (POW_LAUNCH_SENTINEL_IDLE)
+  unsigned test_stall_us = 0;     // a bounded stall kernel in front of every HIP launch (watchdog tests)
+  // K1' and K2' launches as AQL packets (pow_aql.cpp) instead of
+  // hipLaunchKernel: test library only, opt-in there; null = the HIP launch
+  // path, the only one the shipped library has.
+  pow_aql* aql = nullptr;
+  std::string aql_why;            // why aql is null, if it is
+  // Watchdog (every host wait on a launch is bounded): base deadline of a
+  // latency launch, and of a throughput launch on top of its per-counter share.
+  uint64_t watchdog_ns = 10ull * 1000000000ull;
+  // A watchdog fired (or a direct dispatch was refused after its packet slot
+  // was reserved): a launch of this context may still be queued.  pow_group_*
+  // then do not queue a collective behind it; pow_destroy frees only what a
+  // bounded wait shows drained.
+  bool wedged = false;
+  bool aql_lost = false;  // the direct dispatcher was closed with a packet still in flight
+  pow_stats stats{};
+};
+
+// The launch wrappers of the .hip files.
+hipError_t pow_launch_search(int mode, bool full, unsigned grid, hipStream_t stream, const PowConsts* C,
+                             const PowLaunch& L, uint32_t* out, PowResult* res);
+hipError_t pow_launch_hash(uint32_t n, hipStream_t stream, const uint32_t* msgs, uint32_t* digests);
+hipError_t pow_launch_hash_one(hipStream_t stream, const PowMsg& M, PowHashOut* hout, uint32_t seq);
+hipError_t pow_sort_u32(void* temp, size_t* temp_bytes, uint32_t* keys, uint32_t* alt, uint32_t n,
+                        uint32_t** sorted, hipStream_t stream);
+hipError_t pow_launch_search_lat(bool full, bool any, bool asm_groups, unsigned grid, hipStream_t stream,
+                                 const PowConstsLat& C, const PowLaunchLat& L, PowResult* res, PowResult* hout);
+
+#pragma GCC visibility push(hidden)
+
+// ... and pow_api.cpp's launches of K1' and K2' on the context's launch path.
+int launch_search_lat(pow_ctx* ctx, bool full, bool any, bool asm_groups, unsigned grid, const PowLaunchLat& L,
+                      uint64_t deadline_ns);
+int launch_hash_one(pow_ctx* ctx, const PowMsg& M, uint32_t seq, uint64_t deadline_ns);
+
+// The seam of the test library: null in libpow_gpu.so; libpow_gpu_test.so is
+// the same objects plus pow_hooks.cpp, which points it at its table as the
+// library loads.  Everything that reads a test or tuning switch from the
+// environment, and the direct-dispatch launch path, is behind it.
+struct pow_test_hooks {
+  void (*configure)(pow_ctx* ctx);  // pow_init, before the allocations: the switches
+  void (*open_path)(pow_ctx* ctx);  // pow_init, after them: the direct dispatcher, if asked for
+  int (*before_launch)(pow_ctx* ctx);  // in front of a HIP launch (the stall kernel); POW_OK or an error
+  // K1' / K2' by direct dispatch: 1 = sent, 0 = take the HIP path, < 0 = error (recorded)
+  int (*dispatch_lat)(pow_ctx* ctx, bool full, bool any, bool asm_groups, unsigned grid, const PowLaunchLat& L,
+                      uint64_t deadline_ns);
+  int (*dispatch_hash_one)(pow_ctx* ctx, const PowMsg& M, uint32_t seq, uint64_t deadline_ns);
+  // With ctx->aql set: the last packet (0 = completed, 1 = running, < 0 = minus
+  // the queue's HSA status), and the watchdog's account of it.
+  int (*path_status)(pow_ctx* ctx);
+  std::string (*path_diag)(pow_ctx* ctx);
+  int (*warm_path)(pow_ctx* ctx, const PowLaunchLat& L, const PowMsg& M);  // pow_warmup: the path's first packets
+  bool (*close_path)(pow_ctx* ctx);  // pow_destroy; false = a packet may still write: free nothing
+  // pow_group: a stand-in RCCL to load, if one is named (null + *why: it did not load)
+  void* (*rccl_lib)(char* why, size_t cap);
+};
+extern const pow_test_hooks* pow_hooks;  // pow_api.cpp
+
+#pragma GCC visibility pop

@@ -42,8 +42,7 @@
 #include <memory>
 #include <thread>
 
-#include "../../include/pow_gpu.h"
-#include "pow_template.h"
+#include "pow_ctx.h"
 
 namespace {
 
@@ -78,17 +77,8 @@ const Rccl& rccl() {
   static const Rccl r = [] {
     Rccl x;
     void* h = nullptr;
-#ifdef POW_TEST_HOOKS
-    // Test library only: a stand-in RCCL (tests/stub_rccl) that reduces over
-    // POSIX shared memory, so pow_group_init's RCCL leg runs with several
-    // ranks on the one GPU of a test box (RCCL refuses two ranks per GPU).
-    if (const char* p = getenv("POW_TEST_RCCL_LIB")) {
-      if (!(h = dlopen(p, RTLD_NOW | RTLD_LOCAL))) {
-        snprintf(x.why, sizeof x.why, "cannot load POW_TEST_RCCL_LIB %s: %s", p, dlerror());
-        return x;
-      }
-    }
-#endif
+    // Test library only: the stand-in RCCL of the shard tests (pow_hooks.cpp).
+    if (pow_hooks && !(h = pow_hooks->rccl_lib(x.why, sizeof x.why)) && x.why[0]) return x;
     // One RCCL runtime per process: if one is loaded already (torch's, in
     // bench.py's ranks), bind to that very copy (RTLD_NOLOAD: no second
     // load) instead of resolving librccl.so.1 on our own, which could map
@@ -140,12 +130,6 @@ int hip_fail(const char* what, hipError_t e) {
 
 constexpr size_t kMaxWords = 8;
 
-uint64_t now_ns() {
-  timespec t;
-  clock_gettime(CLOCK_MONOTONIC, &t);
-  return (uint64_t)t.tv_sec * 1000000000ull + (uint64_t)t.tv_nsec;
-}
-
 // pow_group_init's deadline for every rank to join the communicator.
 constexpr unsigned kInitTimeoutMs = 60000;
 
@@ -163,7 +147,7 @@ ncclResult_t comm_settle(ncclComm_t c, uint64_t deadline_ns, bool* late) {
     const ncclResult_t r = rccl().get_async_error(c, &st);
     if (r != ncclSuccess) return r;
     if (st != ncclInProgress) return st;
-    if (now_ns() > deadline_ns) {
+    if (mono_ns() > deadline_ns) {
       *late = true;
       return ncclInProgress;
     }
@@ -284,7 +268,7 @@ int group_allreduce(pow_group* g, uint64_t* v, size_t n, int op) {
   // stuck in its own launch) fails the call instead of hanging every rank.  A
   // peer still mining its shard of the round is waited for: the budget grows
   // with the round's shard (2 ns per counter, as the launch watchdog).
-  const uint64_t t0 = now_ns(), budget = 10ull * 1000000000ull + 2ull * g->shard_budget;
+  const uint64_t t0 = mono_ns(), budget = 10ull * 1000000000ull + 2ull * g->shard_budget;
   ncclResult_t r = rccl().all_reduce(g->d_buf, g->d_buf, n, ncclUint64, o, g->comm, st);
   bool late = false;
   if (r == ncclInProgress) r = comm_settle(g->comm, t0 + budget, &late);  // enqueued in the background
@@ -293,7 +277,7 @@ int group_allreduce(pow_group* g, uint64_t* v, size_t n, int op) {
     if (!late) return comm_fail("ncclAllReduce", r);
     char buf[256];
     snprintf(buf, sizeof buf, "ncclAllReduce: not enqueued within %.3f s (the communicator stayed in progress)",
-             (now_ns() - t0) * 1e-9);
+             (mono_ns() - t0) * 1e-9);
     return pow_set_error(POW_ECOMM, buf);
   }
   if ((e = hipMemcpyAsync(g->h_buf, g->d_buf, n * 8, hipMemcpyDeviceToHost, st)) != hipSuccess) {
@@ -395,10 +379,10 @@ int group_search(pow_group* g, const pow_block* tmpl, uint64_t ctr_start, uint64
     ++info.rounds;
     info.local_found = 0;
     if (k) {
-      const uint64_t m0 = now_ns();
+      const uint64_t m0 = mono_ns();
       local_rc = any ? pow_mine_any(g->ctx, tmpl, s, k, diff_bits, cancel_word, epoch, &mine_blk, &c, nullptr)
                      : pow_mine(g->ctx, tmpl, s, k, diff_bits, cancel_word, epoch, &mine_blk, &c, nullptr);
-      info.mine_end_ns = now_ns();
+      info.mine_end_ns = mono_ns();
       info.mine_ms += (info.mine_end_ns - m0) * 1e-6;
       st.add(g->ctx);
       if (local_rc == 1) {
@@ -423,9 +407,9 @@ int group_search(pow_group* g, const pow_block* tmpl, uint64_t ctr_start, uint64
       return pow_set_error(local_rc, buf);
     }
     if (cancel_moved(cancel_word, epoch)) v[1] = 0;
-    const uint64_t a0 = now_ns();
+    const uint64_t a0 = mono_ns();
     const int arc = group_allreduce(g, v, 3, POW_REDUCE_MIN);
-    info.allreduce_ms += (now_ns() - a0) * 1e-6;
+    info.allreduce_ms += (mono_ns() - a0) * 1e-6;
     g->shard_budget = 0;
     if (arc) {
       if (local_rc >= 0) return arc;
@@ -448,9 +432,9 @@ int group_search(pow_group* g, const pow_block* tmpl, uint64_t ctr_start, uint64
       // that rank with an error and the others with the block).
       uint64_t w[5] = {0, 0, 0, 0, 0};
       if (local_rc == 1 && c == v[0] && digest_words(mine_blk.block_hash, w)) w[4] = 1;
-      const uint64_t a1 = now_ns();
+      const uint64_t a1 = mono_ns();
       const int drc = group_allreduce(g, w, 5, POW_REDUCE_MAX);
-      info.allreduce_ms += (now_ns() - a1) * 1e-6;
+      info.allreduce_ms += (mono_ns() - a1) * 1e-6;
       if (drc) return drc;
       if (w[4] != 1) return pow_set_error(POW_ECOMM, "the winner's digest did not arrive");
       winner_block(tmpl, v[0], w, out);
@@ -544,12 +528,12 @@ int pow_group_init_within(pow_ctx* ctx, int nranks, int rank, const uint8_t id[P
   job->nranks = nranks;
   job->rank = rank;
   job->device = pow_ctx_device(ctx);
-  const uint64_t t0 = now_ns(), budget = (uint64_t)timeout_ms * 1000000ull;
+  const uint64_t t0 = mono_ns(), budget = (uint64_t)timeout_ms * 1000000ull;
   std::thread(run_init, job).detach();
   bool late = false;
   while (job->state.load(std::memory_order_acquire) == 0 && !late) {
     std::this_thread::sleep_for(std::chrono::microseconds(200));
-    late = now_ns() > t0 + budget;
+    late = mono_ns() > t0 + budget;
   }
   int running = 0;
   if (late && job->state.compare_exchange_strong(running, 2, std::memory_order_acq_rel)) {
@@ -559,7 +543,7 @@ int pow_group_init_within(pow_ctx* ctx, int nranks, int rank, const uint8_t id[P
              "ncclCommInitRankConfig: rank %d of %d on HIP device %d: not every rank joined within %.3f s "
              "(elapsed %.3f s); the call is left to a helper thread, which aborts the communicator if it ever "
              "returns",
-             rank, nranks, pow_ctx_device(ctx), budget * 1e-9, (now_ns() - t0) * 1e-9);
+             rank, nranks, pow_ctx_device(ctx), budget * 1e-9, (mono_ns() - t0) * 1e-9);
     pow_group_destroy(g);
     return pow_set_error(POW_ECOMM, buf);
   }
@@ -570,7 +554,7 @@ int pow_group_init_within(pow_ctx* ctx, int nranks, int rank, const uint8_t id[P
     char buf[480];
     snprintf(buf, sizeof buf,
              "ncclCommInitRankConfig: rank %d of %d on HIP device %d: %s (after %.3f s); communicator aborted", rank,
-             nranks, pow_ctx_device(ctx), R.error_string(r), (now_ns() - t0) * 1e-9);
+             nranks, pow_ctx_device(ctx), R.error_string(r), (mono_ns() - t0) * 1e-9);
     g->comm = nullptr;
     pow_group_destroy(g);
     return pow_set_error(POW_ECOMM, buf);

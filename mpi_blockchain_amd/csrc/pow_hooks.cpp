@@ -1,0 +1,147 @@
+// The test library's side of the seam (pow_ctx.h): linked into
+// libpow_gpu_test.so only (build.py TEST_ONLY), never into the shipped
+// libpow_gpu.so.  The test and tuning switches read from the environment at
+// pow_init, the direct-dispatch launch path (pow_aql.cpp, POW_AQL=1), the stall
+// kernel of the watchdog tests and the stand-in RCCL of the shard tests.
+#include <dlfcn.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <thread>
+
+#include "pow_aql.h"
+#include "pow_ctx.h"
+
+hipError_t pow_launch_test_stall(hipStream_t stream, unsigned us, int realtime_khz);  // pow_test_kernels.hip
+
+namespace {
+
+void configure(pow_ctx* ctx) {
+  if (const char* ff = getenv("POW_FORCE_FULL")) ctx->force_full = ff[0] == '1';
+  if (const char* fi = getenv("POW_FAULT_INJECT"))
+    ctx->fault_mine = std::strcmp(fi, "mine") == 0 ? "injected fault (POW_FAULT_INJECT=mine)" : nullptr;
+  if (const char* lm = getenv("POW_LAT_MAX")) ctx->lat_max = std::min<uint64_t>(strtoull(lm, nullptr, 0), 1ull << 31);
+  if (const char* lw = getenv("POW_LAT_WPS")) ctx->lat_wps = (unsigned)std::min(8ul, strtoul(lw, nullptr, 0));
+  if (const char* si = getenv("POW_TEST_SENTINEL_IDLE")) ctx->sentinel_idle = si[0] == '1';
+  if (const char* ts = getenv("POW_TEST_STALL_US")) ctx->test_stall_us = (unsigned)strtoul(ts, nullptr, 0);
+  if (const char* g = getenv("POW_GRID_PER_CU")) {  // launch-geometry experiments
+    const int per = atoi(g);
+    if (per > 0 && per <= 64) ctx->grid_full = (unsigned)ctx->cu_count * (unsigned)per;
+  }
+  // POW_WATCHDOG_MS: the watchdog's base deadline (tests of the watchdog itself)
+  if (const char* wd = getenv("POW_WATCHDOG_MS")) ctx->watchdog_ns = std::max(1ull, strtoull(wd, nullptr, 0)) * 1000000ull;
+}
+
+// POW_AQL=1: K1'/K2' as AQL packets (pow_aql.cpp; dispatch A/B and the
+// multi-producer ordering test), POW_AQL_EXP its experiment flags.
+void open_path(pow_ctx* ctx) {
+  const char* use_aql = getenv("POW_AQL");
+  const unsigned aql_flags = getenv("POW_AQL_EXP") ? (unsigned)strtoul(getenv("POW_AQL_EXP"), nullptr, 0) : 0u;
+  if (use_aql && use_aql[0] == '1' && pow_aql_open(ctx->device, aql_flags, &ctx->aql, &ctx->aql_why) != 0)
+    ctx->aql = nullptr;  // the HIP launch path
+}
+
+int before_launch(pow_ctx* ctx) {
+  if (ctx->test_stall_us) HIP_OK(pow_launch_test_stall(ctx->stream, ctx->test_stall_us, ctx->realtime_khz));
+  return POW_OK;
+}
+
+// The explicit kernel arguments of a direct dispatch (pow_aql.cpp): the
+// parameters in declaration order, each at its natural alignment.
+struct ArgPack {
+  alignas(8) uint8_t b[2048];
+  uint32_t n = 0;
+  template <class T>
+  void put(const T& v) {
+    n = (n + (uint32_t)alignof(T) - 1) & ~((uint32_t)alignof(T) - 1);
+    memcpy(b + n, &v, sizeof v);
+    n += (uint32_t)sizeof v;
+  }
+};
+
+// A context whose direct-dispatch queue has reported an error goes back to
+// the HIP launch path for good (pow_launch_path then says so).
+bool aql_usable(pow_ctx* ctx) {
+  if (!ctx->aql) return false;
+  if (pow_aql_status(ctx->aql) >= 0) return true;
+  ctx->aql_why = "the dispatch queue reported an error; back on the HIP launch path";
+  if (!pow_aql_close(ctx->aql)) ctx->wedged = ctx->aql_lost = true;  // a packet may still be in flight
+  ctx->aql = nullptr;
+  return false;
+}
+
+// One packet through the context's dispatcher: 1 = sent.  A refused packet may
+// have left its reserved slot behind (pow_aql_dispatch): the context is wedged.
+int send_packet(pow_ctx* ctx, int kernel, const char* name, uint32_t grid, uint32_t wg, const ArgPack& a,
+                uint64_t deadline_ns) {
+  std::string why;
+  if (!pow_aql_dispatch(ctx->aql, kernel, grid, wg, a.b, a.n, deadline_ns, &why)) return 1;
+  ctx->wedged = true;
+  return fail(POW_EHIP, "dispatch of %s failed: %s (%s)", name, why.c_str(), pow_aql_diag(ctx->aql).c_str());
+}
+
+int dispatch_lat(pow_ctx* ctx, bool full, bool any, bool asm_groups, unsigned grid, const PowLaunchLat& L,
+                 uint64_t deadline_ns) {
+  if (!aql_usable(ctx)) return 0;
+  ArgPack a;
+  a.put(ctx->lat_consts);
+  a.put(L);
+  a.put(ctx->d_lat);
+  a.put(ctx->d_lat_host);
+  const int k = POW_AQL_LAT0 + (full ? 1 : 0) + (any ? 2 : 0) + (asm_groups ? 4 : 0);
+  return send_packet(ctx, k, "pow_search_lat", grid, 256, a, deadline_ns);
+}
+
+int dispatch_hash_one(pow_ctx* ctx, const PowMsg& M, uint32_t seq, uint64_t deadline_ns) {
+  if (!aql_usable(ctx)) return 0;
+  ArgPack a;
+  a.put(M);
+  a.put(ctx->d_one);
+  a.put(seq);
+  return send_packet(ctx, POW_AQL_HASH_ONE, "pow_hash_one", 1, 64, a, deadline_ns);
+}
+
+int path_status(pow_ctx* ctx) { return pow_aql_status(ctx->aql); }
+
+std::string path_diag(pow_ctx* ctx) { return "launch path direct, " + pow_aql_diag(ctx->aql); }
+
+// The warm-up launches once more through the direct-dispatch queue (its first packets).
+int warm_path(pow_ctx* ctx, const PowLaunchLat& L, const PowMsg& M) {
+  if (!ctx->aql) return POW_OK;
+  for (int k = 0; k < 9; ++k) {
+    const uint64_t deadline = mono_ns() + ctx->watchdog_ns;
+    if (int rc = k < 8 ? launch_search_lat(ctx, k & 1, k & 2, k & 4, 1, L, deadline)
+                       : launch_hash_one(ctx, M, 0, deadline))
+      return rc;
+    for (int st, n = 0; (st = pow_aql_status(ctx->aql)) != 0; ++n) {
+      if (st < 0) return fail(POW_EHIP, "warm-up dispatch: queue error 0x%x", -st);
+      if (n > 20000) break;  // POW_AQL_EXP_NO_SIGNAL: no completion to wait for; ~20 ms
+      std::this_thread::sleep_for(std::chrono::microseconds(1));
+    }
+  }
+  return POW_OK;
+}
+
+// Direct-dispatch packets, which the stream does not see, are waited for on
+// the dispatcher's completion signal (pow_aql_close).
+bool close_path(pow_ctx* ctx) { return !ctx->aql_lost && pow_aql_close(ctx->aql); }
+
+// A stand-in RCCL (tests/stub_rccl) that reduces over POSIX shared memory, so
+// pow_group_init's RCCL leg runs with several ranks on the one GPU of a test
+// box (RCCL refuses two ranks per GPU).
+void* rccl_lib(char* why, size_t cap) {
+  const char* p = getenv("POW_TEST_RCCL_LIB");
+  if (!p) return nullptr;
+  void* h = dlopen(p, RTLD_NOW | RTLD_LOCAL);
+  if (!h) snprintf(why, cap, "cannot load POW_TEST_RCCL_LIB %s: %s", p, dlerror());
+  return h;
+}
+
+const pow_test_hooks kHooks = {configure,   open_path, before_launch, dispatch_lat, dispatch_hash_one,
+                               path_status, path_diag, warm_path,     close_path,   rccl_lib};
+const bool kRegistered = (pow_hooks = &kHooks, true);  // as the library loads
+
+}  // namespace

@@ -1,0 +1,261 @@
+// Host code of the C ABI that needs no GPU (pow_host.h): the error string, the
+// clock, the per-template precompute, the launch splitting and the host-side
+// helpers of include/pow_gpu.h.  No HIP header: tests/host_unit.cpp links this
+// file alone and runs it on the CPU.
+#include "pow_host.h"
+
+#include <time.h>
+
+#include <cstdarg>
+#include <cstddef>
+#include <cstdio>
+#include <cstring>
+#include <string>
+
+static_assert(sizeof(pow_block) == 552, "pow_block must match block.h:17-25 (LP64)");
+static_assert(offsetof(pow_block, created_at) == 16, "layout");
+static_assert(offsetof(pow_block, nonce) == 24, "layout");
+static_assert(offsetof(pow_block, previous_block_hash) == 34, "layout");
+static_assert(offsetof(pow_block, block_hash) == 290, "layout");
+static_assert(sizeof(PowConsts) % 4 == 0 && sizeof(PowConsts) < 4096, "consts");
+static_assert(offsetof(PowConsts, kw0) == 4 * PC_KW0, "PC_KW0");
+static_assert(offsetof(PowConsts, u20) == 4 * PC_U20, "PC_U20");
+static_assert(offsetof(PowConsts, u21) == 4 * (PC_U20 + 1), "PC_U21");
+static_assert(offsetof(PowConsts, u22) == 4 * (PC_U20 + 2), "PC_U22");
+static_assert(offsetof(PowConsts, u25) == 4 * PC_U25, "PC_U25");
+static_assert(offsetof(PowConsts, kw3) == 4 * PC_KW3, "PC_KW3");
+static_assert(offsetof(PowConsts, u18) == 4 * PC_U18, "PC_U18");
+static_assert(offsetof(PowConsts, w3) == 4 * PC_W3, "PC_W3");
+static_assert(offsetof(PowConsts, k) == 4 * PC_K, "PC_K");
+static_assert(offsetof(PowConsts, st0) == 4 * PC_ST0, "PC_ST0");
+static_assert(offsetof(PowConsts, w0raw) == 4 * PC_WRAW, "PC_WRAW");
+static_assert(offsetof(PowConstsLat, st0) == 4 * LC_ST0 && offsetof(PowConstsLat, kw0) == 4 * LC_KW0 &&
+                  offsetof(PowConstsLat, k) == 4 * LC_K && offsetof(PowConstsLat, w0raw) == 4 * LC_WRAW,
+              "LC_*");
+
+namespace {
+
+thread_local std::string g_err;
+
+// ---------------- host SHA-256 pieces for the template precompute ----------------
+// (FIPS 180-4 / picosha2.h:46-136; only the parts needed to fold constants)
+const uint32_t kK[64] = {
+    0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5,
+    0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174,
+    0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da,
+    0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967,
+    0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85,
+    0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070,
+    0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3,
+    0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
+const uint32_t kIV[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a,
+                         0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
+
+inline uint32_t rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
+inline uint32_t ssig0(uint32_t x) { return rotr(x, 7) ^ rotr(x, 18) ^ (x >> 3); }
+inline uint32_t ssig1(uint32_t x) { return rotr(x, 17) ^ rotr(x, 19) ^ (x >> 10); }
+
+// block.cpp:61-72 alphabet.
+inline char digit_char(unsigned d) {
+  return d < 26 ? (char)('a' + d) : d < 52 ? (char)('A' + d - 26) : (char)('0' + d - 52);
+}
+
+// One 64-byte chunk's message schedule with K folded in: kw[i] = K[i] + W[i]
+// (the rounds that consume it run on the GPU).
+void chunk_kw(uint32_t kw[64], const uint8_t* chunk) {
+  uint32_t w[64];
+  for (int i = 0; i < 16; ++i) w[i] = be32(chunk + 4 * i);
+  for (int i = 16; i < 64; ++i) w[i] = ssig1(w[i - 2]) + w[i - 7] + ssig0(w[i - 15]) + w[i - 16];
+  for (int i = 0; i < 64; ++i) kw[i] = kK[i] + w[i];
+}
+
+// The n base-62 digits of v, most significant first.
+void split62(uint64_t v, uint32_t* digit, int n) {
+  for (int i = n - 1; i >= 0; --i) {
+    digit[i] = (uint32_t)(v % 62);
+    v /= 62;
+  }
+}
+
+// d <= 32: a digest solves iff H0 <= thr; d > 32: thr = 0 (the full test).
+uint32_t diff_thr(unsigned diff) { return diff >= 32 ? 0u : (0xFFFFFFFFu >> diff); }
+
+}  // namespace
+
+int fail(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  g_err = buf;
+  return code;
+}
+
+int pow_set_error(int code, const char* msg) { return fail(code, "%s", msg); }
+
+uint64_t mono_ns() {
+  timespec t;
+  clock_gettime(CLOCK_MONOTONIC, &t);
+  return (uint64_t)t.tv_sec * 1000000000ull + (uint64_t)t.tv_nsec;
+}
+
+uint32_t be32(const uint8_t* p) {
+  return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+}
+
+void padded_message(const pow_block* b, uint8_t m[320]) {
+  memset(m, 0, 320);
+  pow_block_to_bytes(b, m);
+  m[POW_MSG_BYTES] = 0x80;
+  const uint64_t bits = (uint64_t)POW_MSG_BYTES * 8;  // 2160
+  for (int i = 0; i < 8; ++i) m[319 - i] = (uint8_t)(bits >> (8 * i));
+}
+
+void pow_build_consts(const pow_block* tmpl, PowConsts* C) {
+  memset(C, 0, sizeof *C);
+  pow_block b = *tmpl;
+  memset(b.nonce, 0, sizeof b.nonce);  // nonce bytes are per trial; nonce[9] stays NUL
+  uint8_t m[320];
+  padded_message(&b, m);
+  for (int c = 1; c < 5; ++c) chunk_kw(C->kw[c - 1], m + 64 * c);
+  uint32_t W[16];
+  for (int i = 0; i < 16; ++i) W[i] = be32(m + 4 * i);
+  C->w0 = W[0];
+  C->w3lo = W[3] & 0x00FFFFFFu;  // [nonce[9]=0, prev[0], prev[1]]
+  for (int i = 4; i < 16; ++i) C->kw0[i] = kK[i] + W[i];
+  // round 0 of chunk 0 (uniform)
+  uint32_t a = kIV[0], bb = kIV[1], c = kIV[2], d = kIV[3], e = kIV[4], f = kIV[5], g = kIV[6], h = kIV[7];
+  {
+    uint32_t S1 = rotr(e, 6) ^ rotr(e, 11) ^ rotr(e, 25);
+    uint32_t chv = (e & f) ^ (~e & g);
+    uint32_t t1 = h + S1 + chv + kK[0] + W[0];
+    uint32_t S0 = rotr(a, 2) ^ rotr(a, 13) ^ rotr(a, 22);
+    uint32_t mj = (a & bb) ^ (a & c) ^ (bb & c);
+    h = g; g = f; f = e; e = d + t1; d = c; c = bb; bb = a; a = t1 + S0 + mj;
+  }
+  const uint32_t st[8] = {a, bb, c, d, e, f, g, h};
+  memcpy(C->st0, st, sizeof st);
+  C->u16 = ssig1(W[14]) + W[9] + W[0];
+  C->u17 = ssig1(W[15]) + W[10];
+  C->u19 = W[12] + ssig0(W[4]);
+  C->u20 = W[13] + ssig0(W[5]) + W[4];
+  C->u21 = W[14] + ssig0(W[6]) + W[5];
+  C->u22 = W[15] + ssig0(W[7]) + W[6];
+  C->u23 = ssig0(W[8]) + W[7];
+  C->u24 = ssig0(W[9]) + W[8];
+  for (int k = 0; k < 6; ++k) C->u25[k] = ssig0(W[10 + k]) + W[9 + k];
+  C->w15 = W[15];
+  memcpy(C->k, kK, sizeof kK);
+  memcpy(C->w0raw, W, sizeof W);  // nonce words zero: W1 = W2 = 0, W3 = w3lo
+  for (unsigned j = 0; j < POW_J; ++j) {
+    const uint32_t w3 = ((uint32_t)(uint8_t)digit_char(j) << 24) | C->w3lo;
+    C->w3[j] = w3;
+    C->kw3[j] = kK[3] + w3;
+    C->u18[j] = ssig0(w3) + W[11];
+  }
+}
+
+void pow_build_msg(const pow_block* b, PowMsg* M) {
+  uint8_t m[320];
+  padded_message(b, m);
+  for (int c = 0; c < 5; ++c) chunk_kw(M->kw[c], m + 64 * c);
+}
+
+void digest_out(const uint32_t* h, uint8_t* digest, char* hex) {
+  static const char hexd[] = "0123456789abcdef";
+  uint8_t d[32];
+  for (int k = 0; k < 8; ++k) {
+    d[4 * k] = (uint8_t)(h[k] >> 24);
+    d[4 * k + 1] = (uint8_t)(h[k] >> 16);
+    d[4 * k + 2] = (uint8_t)(h[k] >> 8);
+    d[4 * k + 3] = (uint8_t)h[k];
+  }
+  if (digest) memcpy(digest, d, 32);
+  if (hex) {
+    for (int k = 0; k < 32; ++k) {
+      hex[2 * k] = hexd[d[k] >> 4];
+      hex[2 * k + 1] = hexd[d[k] & 15];
+    }
+    hex[64] = 0;
+  }
+}
+
+int check_range(const pow_block* tmpl, uint64_t start, uint64_t count, unsigned diff) {
+  if (!tmpl) return fail(POW_EINVAL, "null template");
+  if (diff > 256) return fail(POW_EINVAL, "difficulty %u > 256 bits", diff);
+  if (start >= POW_COUNTER_LIMIT || count > POW_COUNTER_LIMIT - start)
+    return fail(POW_EINVAL, "counter range past 62^9");
+  return POW_OK;
+}
+
+int make_launch(uint64_t start, uint64_t count, unsigned diff, uint32_t cap, uint32_t mode,
+                PowLaunch* L) {
+  memset(L, 0, sizeof *L);
+  const uint64_t P0 = start / POW_J;
+  L->off0 = (uint32_t)(start - P0 * POW_J);
+  const uint64_t np = (L->off0 + count + POW_J - 1) / POW_J;
+  if (np > 0xFFFFFFFFull - (1u << 26)) return fail(POW_EINVAL, "launch too large");
+  L->n_prefix = (uint32_t)np;
+  split62(P0, L->base_digit, 8);
+  L->count = count;
+  L->diff = diff;
+  L->thr = diff_thr(diff);
+  L->cap = cap;
+  L->mode = mode;
+  return POW_OK;
+}
+
+void make_launch_lat(uint64_t start, uint64_t count, unsigned diff, PowLaunchLat* L) {
+  memset(L, 0, sizeof *L);
+  split62(start, L->base_digit, 9);
+  L->count = count;
+  L->diff = diff;
+  L->thr = diff_thr(diff);
+}
+
+extern "C" {
+
+const char* pow_last_error(void) { return g_err.c_str(); }
+
+int pow_nonce_from_counter(uint64_t ctr, char nonce[POW_NONCE_SIZE]) {
+  if (!nonce) return fail(POW_EINVAL, "null nonce");
+  if (ctr >= POW_COUNTER_LIMIT) return fail(POW_EINVAL, "counter >= 62^9");
+  for (int i = POW_NONCE_SIZE - 2; i >= 0; --i) {
+    nonce[i] = digit_char((unsigned)(ctr % 62));
+    ctr /= 62;
+  }
+  nonce[POW_NONCE_SIZE - 1] = 0;  // block.cpp:71
+  return POW_OK;
+}
+
+int pow_block_to_bytes(const pow_block* b, uint8_t out[POW_MSG_BYTES]) {
+  if (!b || !out) return fail(POW_EINVAL, "null");
+  // block.cpp:81-84: std::string::operator+=(char) keeps the low byte (trap T1)
+  out[0] = (uint8_t)b->index;
+  out[1] = (uint8_t)b->node_owner_number;
+  out[2] = (uint8_t)b->difficulty;
+  out[3] = (uint8_t)b->created_at;
+  memcpy(out + 4, b->nonce, POW_NONCE_SIZE);                        // block.cpp:85
+  memcpy(out + 4 + POW_NONCE_SIZE, b->previous_block_hash, POW_HASH_SIZE);  // block.cpp:86
+  return POW_OK;
+}
+
+int pow_solves_problem(const char* hex, unsigned diff_bits) {
+  if (!hex) return 0;
+  // block.cpp:28-58, 91-96: binary expansion of the hex string (toupper;
+  // non-hex chars count as "1111"), first diff_bits chars must be '0'.
+  const size_t len = strlen(hex);
+  if ((size_t)diff_bits > 4 * len) return 0;
+  for (unsigned i = 0; i < diff_bits; ++i) {
+    char c = hex[i / 4];
+    unsigned v;
+    if (c >= '0' && c <= '9') v = (unsigned)(c - '0');
+    else if ((c >= 'a' && c <= 'e') || (c >= 'A' && c <= 'E')) v = 10u + (unsigned)((c | 0x20) - 'a');
+    else v = 15;
+    if ((v >> (3 - i % 4)) & 1u) return 0;
+  }
+  return 1;
+}
+
+}  // extern "C"

@@ -1,0 +1,39 @@
+// HIP-free host code of the miner (pow_host.cpp): the error string, the
+// clock, the per-template precompute and the launch splitting.  Pure integer
+// code: it compiles with a plain C++ compiler and no ROCm include path, so
+// tests/host_unit.cpp runs it on the CPU under sanitizers.  Library-internal
+// (pow_api.cpp, pow_group.cpp, pow_aql.cpp, pow_hooks.cpp); not part of the C
+// ABI, hence hidden.  pow_build_consts and pow_set_error (pow_template.h) and
+// the host-side helpers of include/pow_gpu.h are defined there too.
+#pragma once
+#include <stdint.h>
+
+#include "../../include/pow_gpu.h"
+#include "pow_template.h"
+
+#pragma GCC visibility push(hidden)
+
+// Record a printf-style message for pow_last_error(); returns `code`.
+int fail(int code, const char* fmt, ...);
+// CLOCK_MONOTONIC in ns: the clock of every deadline in the library.
+uint64_t mono_ns();
+
+uint32_t be32(const uint8_t* p);
+// block.cpp:79-88 + picosha2.h:201-218: the padded 320-byte message.
+void padded_message(const pow_block* b, uint8_t m[320]);
+// The argument of K2' (pow_hash_one): the five chunks' K[i] + W[i] words of
+// b's padded message.
+void pow_build_msg(const pow_block* b, PowMsg* M);
+// picosha2's output_hex (picosha2.h:141-150): big-endian digest bytes
+// (`digest`, may be null) and lowercase hex + NUL (`hex`, may be null).
+void digest_out(const uint32_t* h, uint8_t* digest, char* hex);
+
+// The argument checks shared by the sweep and mine calls.
+int check_range(const pow_block* tmpl, uint64_t start, uint64_t count, unsigned diff);
+// Split [start, start+count) (count <= 2^32) into K1's prefix form.
+int make_launch(uint64_t start, uint64_t count, unsigned diff, uint32_t cap, uint32_t mode, PowLaunch* L);
+// K1''s form of [start, start+count): digits, count, diff and thr; the rest
+// of *L is zeroed (watch, nwg and seq are the caller's).
+void make_launch_lat(uint64_t start, uint64_t count, unsigned diff, PowLaunchLat* L);
+
+#pragma GCC visibility pop

@@ -45,8 +45,9 @@ HOOKS = (b"POW_FAULT_INJECT", b"POW_FORCE_FULL", b"POW_LAT_MAX", b"POW_LAT_WPS",
 def test_shipped_library_has_no_test_hooks():
     """The test and tuning switches (fault injection, forced kernel variants,
     launch geometry, the stand-in RCCL) exist only in libpow_gpu_test.so,
-    built from the same objects plus -DPOW_TEST_HOOKS (build.py); the shipped
-    libpow_gpu.so reads no such variable.  Both export the same ABI."""
+    which is the shipped library's objects plus csrc/pow_hooks.cpp and the
+    rest of build.py's TEST_ONLY; the shipped libpow_gpu.so reads no such
+    variable.  Both export the same ABI."""
     shipped = open(_lib.LIB_PATH, "rb").read()
     test = open(_lib.TEST_LIB_PATH, "rb").read()
     assert [h for h in HOOKS if h in shipped] == []

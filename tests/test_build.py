@@ -407,10 +407,12 @@ STREAM_ARG = {"hipMemcpyAsync": (4, 5), "hipMemsetAsync": (3, 4), "hipMemsetD32A
               "hipStreamWaitEvent": (0, 3), "hipGraphLaunch": (1, 2)}
 NULL_STREAMS = {"0", "0u", "nullptr", "NULL", "hipStreamDefault", "hipStreamLegacy", "hipStreamPerThread",
                 "(hipStream_t)0", "hipStream_t(0)", "hipStream_t{}", "(hipStream_t) 0"}
-SHIPPED_SOURCES = [os.path.join(CSRC, f) for f in ("pow_api.cpp", "pow_aql.cpp", "pow_board.cpp", "pow_group.cpp",
+SHIPPED_SOURCES = [os.path.join(CSRC, f) for f in ("pow_api.cpp", "pow_host.cpp", "pow_hooks.cpp", "pow_aql.cpp",
+                                                    "pow_board.cpp", "pow_group.cpp",
                                                     "pow_kernels.hip", "pow_sort.hip", "valu_peak.hip",
                                                     "pow_test_kernels.hip", "pow_template.h", "sha256_dev.h",
-                                                    "pow_aql.h", os.path.join("node", "pow_node.cpp"))] + \
+                                                    "pow_aql.h", "pow_host.h", "pow_ctx.h",
+                                                    os.path.join("node", "pow_node.cpp"))] + \
     [os.path.join(ROOT, "tests", "stub_rccl", "stub_rccl.cpp")]
 
 

@@ -5,7 +5,7 @@ set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 src=$1; out=$2
 mkdir -p "$out"
+# the shipped library's source list (build.py), taken from the copy in <csrc-dir>
+srcs=$(cd "$R" && python3 -m mpi_blockchain_amd.build --sources | sed "s|.*/|$src/|")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -shared -std=c++17 -mcode-object-version=5 \
-  -I "$R/include" -I "$src" "$src"/pow_api.cpp "$src"/pow_board.cpp "$src"/pow_group.cpp "$src"/pow_kernels.hip \
-  "$src"/pow_sort.hip "$src"/valu_peak.hip "$src"/pow_aql.cpp ${AB_FLAGS:-} -o "$out/libpow_gpu.so" \
-  -L /opt/rocm/lib -lhsa-runtime64 -Wl,-rpath,/opt/rocm/lib
+  -I "$R/include" -I "$src" $srcs ${AB_FLAGS:-} -o "$out/libpow_gpu.so"

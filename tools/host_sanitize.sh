@@ -15,6 +15,8 @@ R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 O="$R/build/san"
 CLANG=/opt/rocm/llvm/bin/clang
 CLANGXX=/opt/rocm/llvm/bin/clang++
+# the test library's sources (the switches and direct dispatch the runs below use): build.py's list
+srcs() { (cd "$R" && python3 -m mpi_blockchain_amd.build --sources --test); }
 SAN="-fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer"
 MPI_INC=/opt/conda/include
 MPI_LIB=/opt/conda/lib
@@ -26,9 +28,8 @@ build)
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O1 -g -fPIC -shared -std=c++17 -mcode-object-version=5 \
     -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
     -Xarch_host -fno-sanitize-recover=undefined -Xarch_host -fno-omit-frame-pointer \
-    -DPOW_TEST_HOOKS -I "$R/include" -I "$C" \
-    "$C/pow_api.cpp" "$C/pow_board.cpp" "$C/pow_group.cpp" "$C/pow_kernels.hip" "$C/pow_sort.hip" \
-    "$C/valu_peak.hip" "$C/pow_aql.cpp" "$C/pow_test_kernels.hip" -o "$O/libpow_gpu.so" -L /opt/rocm/lib -lhsa-runtime64 -Wl,-rpath,/opt/rocm/lib
+    -I "$R/include" -I "$C" \
+    $(srcs) -o "$O/libpow_gpu.so" -L /opt/rocm/lib -lhsa-runtime64 -Wl,-rpath,/opt/rocm/lib
   $CLANG -std=c11 -O1 -g $SAN -I "$R/include" "$R/examples/mine_chain.c" \
     -L "$O" -lpow_gpu -Wl,-rpath,'$ORIGIN' -o "$O/mine_chain"
   $CLANG -std=c11 -D_POSIX_C_SOURCE=200809L -O1 -g $SAN -pthread -I "$R/include" "$R/examples/board_two_ctx.c" \
@@ -86,9 +87,8 @@ tsan-build)
   mkdir -p "$T"
   C="$R/mpi_blockchain_amd/csrc"
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O1 -g -fPIC -shared -std=c++17 -mcode-object-version=5 \
-    -Xarch_host -fsanitize=thread -Xarch_host -fno-omit-frame-pointer -DPOW_TEST_HOOKS -I "$R/include" -I "$C" \
-    "$C/pow_api.cpp" "$C/pow_board.cpp" "$C/pow_group.cpp" "$C/pow_kernels.hip" "$C/pow_sort.hip" \
-    "$C/valu_peak.hip" "$C/pow_aql.cpp" "$C/pow_test_kernels.hip" -o "$T/libpow_gpu.so" -L /opt/rocm/lib -lhsa-runtime64 -Wl,-rpath,/opt/rocm/lib
+    -Xarch_host -fsanitize=thread -Xarch_host -fno-omit-frame-pointer -I "$R/include" -I "$C" \
+    $(srcs) -o "$T/libpow_gpu.so" -L /opt/rocm/lib -lhsa-runtime64 -Wl,-rpath,/opt/rocm/lib
   $CLANGXX -std=c++17 -O1 -g -fsanitize=thread -pthread -DPOW_NODE_TEST_KNOBS -I "$R/include" -I "$MPI_INC" \
     "$R/mpi_blockchain_amd/csrc/node/pow_node.cpp" -L "$T" -lpow_gpu \
     -Wl,-rpath,'$ORIGIN' "$MPI_LIB/libmpi.so" -Wl,-rpath-link,"$MPI_LIB" -o "$T/pow_node_tsan"
