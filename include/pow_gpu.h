@@ -73,7 +73,7 @@ enum {
   POW_ECOMM = -5,     /* RCCL unavailable or a collective failed (pow_group_*) */
 };
 
-/* Per-call statistics of the last pow_mine / pow_sweep / pow_hash_blocks. */
+/* Per-call statistics of the last pow_mine / pow_sweep / pow_hash_blocks / pow_verify_chain. */
 typedef struct pow_stats {
   double kernel_ms;      /* sum of kernel durations on the ctx stream: HIP events around the
                             sweep/mine kernels; the latency kernel (first sub-round of
@@ -136,6 +136,48 @@ int pow_hash_blocks(pow_ctx* ctx, const pow_block* blocks, size_t n,
  * low-latency path: the message travels as a kernel argument and the digest comes
  * back through mapped host memory, no copies (~24 us per call on an MI355X). */
 int pow_hash_block(pow_ctx* ctx, const pow_block* b, uint8_t digest[32], char hex[65]);
+
+/* "Is this chain valid?": one fused pass on the GPU over a chain of n blocks,
+ * tip first, as on the wire (send_blockchain, node.cpp:334-359) and in the
+ * <rank>.out dumps: chain[i + 1] is the parent of chain[i].  n counts real
+ * blocks: the caller trims the reference's padding after a block whose
+ * previous_block_hash is empty.  The raw structs are copied to the GPU as they
+ * are (no per-block host work) and no digests come back.  The reference checks
+ * less: check_first hashes only chain[0] of a migrated chain (node.cpp:111-115)
+ * and neither valid_new_block (block.cpp:13-25) nor check_chain
+ * (node.cpp:117-125) calls solves_problem.  status[i] (n bytes, may be NULL)
+ * is the OR of the flags of block i, each evaluated on its own:
+ *   POW_V_HASH   the lowercase hex of SHA-256 over block_to_str(chain[i])
+ *                differs from block_hash as a C string: the first 64 bytes
+ *                must be equal and block_hash[64] must be NUL;
+ *   POW_V_WORK   the COMPUTED digest (never the stored text) has fewer than
+ *                diff_bits leading zero bits (0..256, as pow_solves_problem);
+ *   POW_V_LINK   i < n - 1 and previous_block_hash of i differs from
+ *                block_hash of i + 1, as the reference's (string) casts
+ *                compare them: C strings cut at the first NUL, at most 256
+ *                bytes (bytes after the NUL are hashed, but not linked);
+ *   POW_V_INDEX  i < n - 1 and chain[i].index - 1 != chain[i + 1].index in
+ *                uint32_t arithmetic (index 0 over 0xFFFFFFFF passes).
+ * The last block gets no link or index check.  The time window of
+ * valid_new_block (created_at within VALIDATION_MINUTES) is the caller's
+ * business: it depends on the caller's clock, not on the chain.
+ * Returns 1 if every block passes, 0 if any flag is set; then *first_bad (may
+ * be NULL) = the lowest flagged index, n if none, and *n_bad (may be NULL) =
+ * the number of flagged blocks.  n = 0 returns 1.  POW_EINVAL for diff_bits >
+ * 256, n > 2^24, a null ctx or a null chain with n > 0.  n above 2^16 runs in
+ * tiles of 2^16 blocks (36 MB of device memory however long the chain).
+ * pow_get_stats: kernel_ms, launches (one per tile), hashes = n.
+ * Cost (MI355X, profiles/verify_chain/README.md): a call takes ~50 us up to
+ * 16 blocks and 78 us at 200 (kernel 23-36 us), 0.72 ms at 2^16 and 11.5 ms
+ * at 2^20 blocks, where it is the copy of the structs.  The reference's own
+ * block_to_hash loop at -O2 takes 2.9 us per block on the same box, so the
+ * call is slower than the CPU below the crossover, measured between 16 blocks
+ * (0.93x the loop's speed) and 32 (1.33x); at 5 blocks it takes 3.3x the
+ * loop's time, at 2^16 and above 1/266 of it. */
+enum { POW_V_HASH = 1, POW_V_WORK = 2, POW_V_LINK = 4, POW_V_INDEX = 8 };
+int pow_verify_chain(pow_ctx* ctx, const pow_block* chain, size_t n, unsigned diff_bits,
+                     uint8_t* status /* n bytes, may be NULL */,
+                     size_t* first_bad /* may be NULL */, size_t* n_bad /* may be NULL */);
 
 /* Mining round: replaces node.cpp:302-308 (nonce -> hash -> test) for every
  * counter in [ctr_start, ctr_start + ctr_count).  The header fields and the

@@ -13,11 +13,15 @@ reference                  here
 ``solves_problem``         :func:`solves_problem` (run-time difficulty)
 ``gen_random_nonce``       :func:`gen_random_nonce` (same alphabet, seeded RNG) and
                            :func:`nonce_from_counter` (the GPU path's counter map)
+``check_chain`` and more   :func:`verify_chain` (host statement of what
+                           ``pow_verify_chain`` checks on the GPU:
+                           :meth:`mpi_blockchain_amd.miner.GpuMiner.verify_chain`)
 =========================  ====================================================
 """
 from __future__ import annotations
 
 import ctypes
+import hashlib
 import random
 
 from ._lib import HASH_SIZE, MSG_BYTES, NONCE_SIZE, Block, check, load
@@ -35,7 +39,7 @@ MAX_BLOCKS = 200
 ALPHABET = "abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789"
 
 __all__ = ["Block", "make_block", "block_to_str", "solves_problem", "nonce_from_counter",
-           "gen_random_nonce", "field", "set_field", "DEFAULT_DIFFICULTY", "BLOCKS_TO_MINE",
+           "gen_random_nonce", "field", "set_field", "verify_chain", "V_HASH", "V_WORK", "V_LINK", "V_INDEX", "DEFAULT_DIFFICULTY", "BLOCKS_TO_MINE",
            "VALIDATION_MINUTES", "VALIDATION_BLOCKS", "HASH_SIZE", "NONCE_SIZE", "MSG_BYTES"]
 
 
@@ -90,3 +94,46 @@ def gen_random_nonce(rng: random.Random | None = None) -> bytes:
     """block.cpp:61-72 with a Python RNG in place of glibc rand()."""
     rng = rng or random
     return "".join(ALPHABET[rng.randrange(62)] for _ in range(NONCE_SIZE - 1)).encode() + b"\0"
+
+
+# pow_verify_chain's status flags (include/pow_gpu.h POW_V_*)
+V_HASH, V_WORK, V_LINK, V_INDEX = 1, 2, 4, 8
+
+
+def _c_string(raw: bytes) -> bytes:
+    """A char[] field as the reference's (string) cast reads it: cut at the
+    first NUL, at most the whole field."""
+    return raw.split(b"\0", 1)[0]
+
+
+def verify_chain(blocks, difficulty: int = DEFAULT_DIFFICULTY) -> list[int]:
+    """The status byte of every block of a chain, tip first (``blocks[i + 1]``
+    is the parent of ``blocks[i]``): what ``pow_verify_chain`` computes on the
+    GPU, stated on the host with hashlib.  Flags, each on its own:
+
+    * ``V_HASH``  the hex of SHA-256 over ``block_to_str(b)`` is not ``block_hash`` as a C
+      string (64 equal bytes, then NUL);
+    * ``V_WORK``  the computed digest has fewer than `difficulty` leading zero bits (0..256);
+    * ``V_LINK``  ``previous_block_hash`` is not the parent's ``block_hash``, both as C strings;
+    * ``V_INDEX`` ``index - 1`` is not the parent's index, in 32-bit arithmetic.
+
+    The last block has no parent in the chain: no link or index check."""
+    if not 0 <= difficulty <= 256:
+        raise ValueError(f"difficulty {difficulty} not in 0..256")
+    n = len(blocks)
+    stored = [field(b, "block_hash") for b in blocks]
+    status = []
+    for i, b in enumerate(blocks):
+        digest = hashlib.sha256(block_to_str(b)).digest()
+        flags = 0
+        if stored[i][:64] != digest.hex().encode() or stored[i][64] != 0:
+            flags |= V_HASH
+        if 256 - int.from_bytes(digest, "big").bit_length() < difficulty:
+            flags |= V_WORK
+        if i < n - 1:
+            if _c_string(field(b, "previous_block_hash")) != _c_string(stored[i + 1]):
+                flags |= V_LINK
+            if (b.index - 1) & 0xFFFFFFFF != blocks[i + 1].index:
+                flags |= V_INDEX
+        status.append(flags)
+    return status

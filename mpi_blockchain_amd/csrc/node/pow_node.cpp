@@ -39,6 +39,21 @@
 // reference.
 //
 //   pow_node [--difficulty D] [--blocks N] [--device G] [--round LOG2] [--serial-init 0|1]
+//            [--verify-chain 0|1]
+//
+// --verify-chain 1 (default 0: the reference's checks only, output unchanged).
+// The reference adopts a migrated chain after hashing only its first block
+// (check_first, node.cpp:111-115) and never tests any received block's proof of
+// work.  With 1, verificar_y_migrar_cadena also passes the received blocks
+// (up to and including the first with an empty previous_block_hash, at most 5)
+// through pow_verify_chain on the receive context, and adopts the chain only if
+// that returns 1 as well: every hash, every block's work, every link.  One
+// batch launch per migration: a strictness option, not a speed-up
+// (INTEGRATION.md).  Each rank reports its running totals on stderr after every
+// such call, and the finishing rank once more as it terminates:
+//   pow_node verify {"rank": R, "calls": C, "blocks": B, "rejected": J, "ms": T}
+// (the other ranks are killed by the finisher's MPI_Abort, node.cpp:330, and
+// have no exit to report at: a rank's last line is its total).
 //
 // Test knobs.  bin/pow_node behaves only as node.cpp does.  The race-shaping
 // switches the protocol tests need are compiled only into bin/pow_node_test
@@ -107,6 +122,7 @@ struct Options {
   unsigned round_log2 = 32; // counters per pow_mine call
   bool serial_init = false; // --serial-init 1: GPU set-up before MPI_Init instead of beside it
                             // (and no start barrier: mixed jobs with reference ranks)
+  bool verify_chain = false; // --verify-chain 1: a migrated chain must also pass pow_verify_chain
 #ifdef POW_NODE_TEST_KNOBS
   TestKnobs t;
 #endif
@@ -188,6 +204,9 @@ class Node {
   int device_ = -1, visible_gpus_ = 0, local_rank_ = 0;
   const char* local_rank_from_ = nullptr;    // the launcher variable the device came from (null: none)
   std::deque<std::pair<pow_block, MPI_Status>> deferred_;
+  // --verify-chain: this rank's totals (written by the receive thread under mu_)
+  unsigned long long verify_calls_ = 0, verify_blocks_ = 0, verify_rejected_ = 0;
+  double verify_ms_ = 0;
 #ifdef POW_NODE_TEST_KNOBS
   std::atomic<int> rivals1_{0};  // --hold-first: peers' blocks 1 this rank has processed
   MPI_Comm test_comm_ = MPI_COMM_NULL;  // --private-lead: the receive thread's own barrier
@@ -249,6 +268,29 @@ class Node {
       ok = prev_of(chain[i]) == hash_of(chain[i + 1]) && chain[i].index - 1 == chain[i + 1].index && ok;
     }
     return ok;
+  }
+  // --verify-chain 1: every received block's hash, work, link and index, in
+  // one launch on the receive context (mu_ is held).
+  bool verify_received(const pow_block* chain) {
+    size_t m = 0;
+    while (m < (size_t)kValidationBlocks && !prev_of(chain[m++]).empty()) {
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = pow_verify_chain(recv_ctx_, chain, m, opt_.difficulty, nullptr, nullptr, nullptr);
+    if (rc < 0) {
+      fprintf(stderr, "[%d] pow_verify_chain: %s\n", rank_, pow_last_error());
+      MPI_Abort(MPI_COMM_WORLD, 1);
+    }
+    verify_ms_ += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    verify_calls_ += 1;
+    verify_blocks_ += m;
+    verify_rejected_ += rc == 0;
+    report_verify();
+    return rc == 1;
+  }
+  void report_verify() {
+    fprintf(stderr, "pow_node verify {\"rank\": %d, \"calls\": %llu, \"blocks\": %llu, \"rejected\": %llu, \"ms\": %.3f}\n",
+            rank_, verify_calls_, verify_blocks_, verify_rejected_, verify_ms_);
   }
   // node.cpp:127-129
   static bool equal(const pow_block& a, const pow_block& b) {
@@ -324,7 +366,8 @@ class Node {
         deferred_.emplace_back(buf, st);
       }
     }
-    const bool checks = check_first(chain.data(), r) && check_chain(chain.data());
+    bool checks = check_first(chain.data(), r) && check_chain(chain.data());
+    if (opt_.verify_chain) checks = verify_received(chain.data()) && checks;
     const int i = find_block(chain.data());
     printf("[%d]: find = %d | received_blockchain_checks = %d\n", rank_, i, checks ? 1 : 0);
     if (checks && i > -1) {
@@ -482,6 +525,7 @@ class Node {
         if (last_->index >= opt_.blocks) {  // node.cpp:286-290
           log_msg("Terminé con la siguiente cadena");
           log_chain("");
+          if (opt_.verify_chain) report_verify();
           break;
         }
         tmpl = *last_;
@@ -593,6 +637,13 @@ int Node::init_gpu() {
       pow_warmup(mine_ctx_) != POW_OK || pow_warmup(recv_ctx_) != POW_OK) {
     fprintf(stderr, "pow_init(%d): %s\n", dev, pow_last_error());
     return 1;
+  }
+  if (opt_.verify_chain) {  // load K3 and size its buffers now, not inside the first migration
+    std::vector<pow_block> warm(kValidationBlocks);
+    if (pow_verify_chain(recv_ctx_, warm.data(), warm.size(), 0, nullptr, nullptr, nullptr) < 0) {
+      fprintf(stderr, "pow_verify_chain(%d): %s\n", dev, pow_last_error());
+      return 1;
+    }
   }
   return 0;
 }
@@ -709,6 +760,7 @@ int main(int argc, char** argv) {
     else if (k == "--device") o.device = (int)v;
     else if (k == "--round") o.round_log2 = (unsigned)std::min(40l, std::max(12l, v));
     else if (k == "--serial-init") o.serial_init = v != 0;
+    else if (k == "--verify-chain") o.verify_chain = v != 0;
 #ifdef POW_NODE_TEST_KNOBS
     else if (k == "--pause-ms") o.t.pause_us = (unsigned)v * 1000u;
     else if (k == "--pause-us") o.t.pause_us = (unsigned)v;

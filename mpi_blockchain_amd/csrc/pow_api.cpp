@@ -412,6 +412,10 @@ void pow_destroy(pow_ctx* ctx) {
   (void)hipFree(ctx->d_sort_tmp);
   (void)hipFree(ctx->d_msgs);
   (void)hipFree(ctx->d_dig);
+  (void)hipFree(ctx->d_vblk);
+  (void)hipFree(ctx->d_vstatus);
+  (void)hipFree(ctx->d_vres);
+  if (ctx->h_vres) (void)hipHostFree(ctx->h_vres);
   if (ctx->h_res) (void)hipHostFree(ctx->h_res);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -537,6 +541,65 @@ int pow_hash_blocks(pow_ctx* ctx, const pow_block* blocks, size_t n, uint8_t* di
 
 int pow_hash_block(pow_ctx* ctx, const pow_block* b, uint8_t digest[32], char hex[65]) {
   return pow_hash_blocks(ctx, b, 1, digest, hex);
+}
+
+// K3 over the raw structs: no per-block host work.  Chains longer than a host
+// tile (2^16 blocks) run tile by tile through the same device buffers, each
+// tile carrying the next one's first block as its halo (the parent of its
+// last block), so device memory stays at 36 MB however long the chain is.
+int pow_verify_chain(pow_ctx* ctx, const pow_block* chain, size_t n, unsigned diff_bits, uint8_t* status,
+                     size_t* first_bad, size_t* n_bad) {
+  if (diff_bits > 256) return fail(POW_EINVAL, "diff_bits %u > 256", diff_bits);
+  if (n > (1u << 24)) return fail(POW_EINVAL, "chain too large (%zu blocks > 2^24)", n);
+  if (!ctx || (!chain && n)) return fail(POW_EINVAL, "null");
+  ctx->stats = pow_stats{};
+  if (first_bad) *first_bad = n;
+  if (n_bad) *n_bad = 0;
+  if (n == 0) return 1;
+  if (int rc = set_dev(ctx)) return rc;
+  const size_t kTile = 1u << 16;
+  const size_t want = std::min(n, kTile);
+  if (want > ctx->verify_cap) {
+    (void)hipFree(ctx->d_vblk);
+    (void)hipFree(ctx->d_vstatus);
+    ctx->d_vblk = nullptr;
+    ctx->d_vstatus = nullptr;
+    ctx->verify_cap = 0;
+    HIP_OK(hipMalloc(&ctx->d_vblk, (want + 1) * sizeof(pow_block)));  // + the halo block
+    HIP_OK(hipMalloc(&ctx->d_vstatus, want));
+    ctx->verify_cap = want;
+  }
+  if (!ctx->d_vres) HIP_OK(hipMalloc(&ctx->d_vres, sizeof(PowVerifyRes)));
+  if (!ctx->h_vres) HIP_OK(hipHostMalloc(&ctx->h_vres, sizeof(PowVerifyRes), hipHostMallocDefault));
+  size_t lowest = n, bad = 0;
+  for (size_t t0 = 0; t0 < n; t0 += kTile) {
+    const size_t tn = std::min(kTile, n - t0);
+    const size_t avail = tn + (t0 + tn < n ? 1 : 0);
+    *ctx->h_vres = PowVerifyRes{~0u, 0u};
+    HIP_OK(hipMemcpyAsync(ctx->d_vres, ctx->h_vres, sizeof(PowVerifyRes), hipMemcpyHostToDevice, ctx->stream));
+    HIP_OK(hipMemcpyAsync(ctx->d_vblk, chain + t0, avail * sizeof(pow_block), hipMemcpyHostToDevice, ctx->stream));
+    if (pow_hooks)
+      if (int rc = pow_hooks->before_launch(ctx)) return rc;
+    HIP_OK(hipEventRecord(ctx->ev0, ctx->stream));
+    HIP_OK(pow_launch_verify((uint32_t)tn, (uint32_t)avail, diff_bits, ctx->stream, ctx->d_vblk, ctx->d_vstatus,
+                             ctx->d_vres));
+    HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_OK(hipMemcpyAsync(ctx->h_vres, ctx->d_vres, sizeof(PowVerifyRes), hipMemcpyDeviceToHost, ctx->stream));
+    if (status) HIP_OK(hipMemcpyAsync(status + t0, ctx->d_vstatus, tn, hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = stream_wait_for(ctx, "chain verify kernel", 100ull * avail)) return rc;  // + 100 ns per block
+    float ms = 0;
+    HIP_OK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    ctx->stats.kernel_ms += ms;
+    ctx->stats.launches += 1;
+    ctx->stats.hashes += tn;
+    if (ctx->h_vres->n_bad) {
+      lowest = std::min(lowest, t0 + ctx->h_vres->first_bad);
+      bad += ctx->h_vres->n_bad;
+    }
+  }
+  if (first_bad) *first_bad = lowest;
+  if (n_bad) *n_bad = bad;
+  return bad == 0 ? 1 : 0;
 }
 
 int pow_sweep_device(pow_ctx* ctx, const pow_block* tmpl, uint64_t ctr_start, uint64_t ctr_count,

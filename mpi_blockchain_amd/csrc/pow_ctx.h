@@ -18,6 +18,12 @@
 
 struct pow_aql;  // the direct dispatcher (pow_aql.h): test library only
 
+// Result words of K3 (pow_verify_kernel): reset by the host before a launch.
+struct PowVerifyRes {
+  unsigned int first_bad;  // lowest flagged block of the launch (atomic min); ~0 = none
+  unsigned int n_bad;      // flagged blocks (atomic add)
+};
+
 struct pow_ctx {
   int device = 0;
   int cu_count = 0;
@@ -61,6 +67,11 @@ struct pow_ctx {
   uint32_t* d_msgs = nullptr;
   uint32_t* d_dig = nullptr;
   size_t hash_cap = 0;
+  uint32_t* d_vblk = nullptr;        // pow_verify_chain: one host tile of raw structs + its halo block,
+  uint8_t* d_vstatus = nullptr;      // the tile's status bytes ...
+  size_t verify_cap = 0;             // ... both sized for this many blocks
+  PowVerifyRes* d_vres = nullptr;    // K3's result words ...
+  PowVerifyRes* h_vres = nullptr;    // ... and their pinned twin: reset value up, result down
   unsigned grid_full = 0;  // workgroups that fill the chip (8 per CU)
   // Set only by the test library's hooks (pow_hooks.cpp, at pow_init):
   bool force_full = false;        // use the d > 32 kernel for every d
@@ -91,6 +102,8 @@ hipError_t pow_launch_search(int mode, bool full, unsigned grid, hipStream_t str
                              const PowLaunch& L, uint32_t* out, PowResult* res);
 hipError_t pow_launch_hash(uint32_t n, hipStream_t stream, const uint32_t* msgs, uint32_t* digests);
 hipError_t pow_launch_hash_one(hipStream_t stream, const PowMsg& M, PowHashOut* hout, uint32_t seq);
+hipError_t pow_launch_verify(uint32_t n_check, uint32_t n_avail, unsigned diff, hipStream_t stream,
+                             const uint32_t* blocks, uint8_t* status, PowVerifyRes* res);
 hipError_t pow_sort_u32(void* temp, size_t* temp_bytes, uint32_t* keys, uint32_t* alt, uint32_t n,
                         uint32_t** sorted, hipStream_t stream);
 hipError_t pow_launch_search_lat(bool full, bool any, bool asm_groups, unsigned grid, hipStream_t stream,

@@ -24,6 +24,14 @@ class MineResult:
     kernel_ms: float      # GPU time of the call
 
 
+@dataclass
+class VerifyResult:
+    ok: bool              # every block passed (pow_verify_chain returned 1)
+    first_bad: int        # lowest flagged index; len(chain) if none
+    n_bad: int            # flagged blocks
+    status: np.ndarray    # np.uint8 per block: OR of block.V_HASH / V_WORK / V_LINK / V_INDEX
+
+
 def refresh_template(last: Block, rank: int, difficulty: int = DEFAULT_DIFFICULTY,
                      now: int | None = None) -> Block:
     """node.cpp:292-299: copy the last block, index+1, owner = rank,
@@ -116,6 +124,19 @@ class GpuMiner:
         dg = ctypes.create_string_buffer(32)
         check(self.L.pow_hash_block(self.ctx, ctypes.byref(b), dg, None), self.L)
         return dg.raw
+
+    # ---- chain audit (check_first + check_chain + solves_problem for every block) ----
+    def verify_chain(self, blocks, difficulty: int = DEFAULT_DIFFICULTY) -> VerifyResult:
+        """pow_verify_chain over a chain, tip first: a list of Blocks or a
+        ctypes ``Block * n`` array (passed as it is).  The host statement of
+        the result is :func:`mpi_blockchain_amd.block.verify_chain`."""
+        n = len(blocks)
+        arr = blocks if isinstance(blocks, ctypes.Array) else (Block * n)(*blocks)
+        status = np.zeros(n, dtype=np.uint8)
+        first, bad = ctypes.c_size_t(), ctypes.c_size_t()
+        rc = check(self.L.pow_verify_chain(self.ctx, arr, n, difficulty, status.ctypes.data_as(ctypes.c_void_p),
+                                           ctypes.byref(first), ctypes.byref(bad)), self.L)
+        return VerifyResult(rc == 1, first.value, bad.value, status)
 
     # ---- mining ----
     def cancel(self) -> None:
@@ -243,5 +264,5 @@ def block_hex(b: Block) -> str:
     return field(b, "block_hash").split(b"\0", 1)[0].decode()
 
 
-__all__ = ["GpuMiner", "DeviceBuffer", "StopBoard", "MineResult", "refresh_template", "proof_of_work_round", "block_hex",
+__all__ = ["GpuMiner", "DeviceBuffer", "StopBoard", "MineResult", "VerifyResult", "refresh_template", "proof_of_work_round", "block_hex",
            "nonce_from_counter"]
