@@ -200,6 +200,52 @@ int pow_mine(pow_ctx* ctx, const pow_block* tmpl, uint64_t ctr_start, uint64_t c
              unsigned diff_bits, const volatile uint32_t* cancel_word, uint32_t epoch,
              pow_block* out, uint64_t* found_ctr, uint64_t* hashes_done);
 
+/* Mine n blocks on top of *parent, each the child of the one before: the loop
+ * of proof_of_work (node.cpp:285-327) for one solo miner, without a host step
+ * between two blocks.  The producing counterpart of pow_verify_chain.
+ * Block k (mining order, k = 0..n-1) is what the host sequence gives: with
+ * `last` = *parent for k = 0, else block k - 1, the template is `last` copied
+ * whole (all 552 bytes, padding included), then index = last.index + 1
+ * (uint32_t wrap), node_owner_number = owner, difficulty = diff_bits,
+ * created_at = created_at[k] (created_at NULL: time(NULL), read once at entry,
+ * for every block) and previous_block_hash = all 256 bytes of last.block_hash
+ * (node.cpp:299, trap T5; the parent's block_hash may be any 256 bytes).  The
+ * block is the result of pow_mine on that template over [ctr_start, ctr_start
+ * + ctr_count): the LOWEST solving counter, nonce = its 9 base-62 characters +
+ * NUL, block_hash = 64 hex + NUL with bytes 65..255 kept from the template
+ * (node.cpp:318).  Every block searches the same counter window.
+ * Blocks are written tip first, as pow_verify_chain and the wire expect: block
+ * k goes to out[n - 1 - k].  After the call out + (n - *n_mined) is a
+ * tip-first chain of *n_mined blocks whose oldest block is a child of *parent;
+ * the entries below it are not touched.
+ * Returns 1 if all n blocks were mined; 0 if it stopped early, because a
+ * block's window held no solution or because the cancel word (optional)
+ * differs from `epoch`; *n_mined (may be NULL) then says how far it got.
+ * n = 0 returns 1.  POW_EINVAL for diff_bits > 256, ctr_count == 0 or > 2^32,
+ * ctr_start + ctr_count > 62^9, n > 2^24, a null ctx, a null parent or out
+ * with n > 0 (all checked before the context is touched), and for a context
+ * bound to a stop board: boards and pow_cancel's in-flight path are not part
+ * of this call.
+ * Up to d = POW_CHAIN_FUSED_MAX_D (csrc/pow_ctx.h; never above 32) the blocks
+ * run fused: one launch per block, each reading the block the launch before it
+ * sealed from device memory, queued in batches of about 2^26 expected trials
+ * (1..64 blocks) with one bounded wait (10 s + 2 ns per counter of the batch's
+ * windows) and one copy back per batch.  The cancel word is read at entry and
+ * between batches, so a cancel takes up to one batch, a handful of
+ * milliseconds.  Above that difficulty the call runs the host loop itself:
+ * the refresh, then pow_mine with the same window and cancel word, block by
+ * block.  Both give the same bytes.
+ * *hashes_done (may be NULL) = trials issued.  pow_get_stats: launches,
+ * kernel_ms (fused: events around each batch) and hashes.
+ * pow_warmup does not launch this call's kernel (nor pow_verify_chain's): the
+ * first fused call of a process also loads its code object.
+ * Cost (MI355X): profiles/mine_chain/README.md. */
+int pow_mine_chain(pow_ctx* ctx, const pow_block* parent, size_t n, unsigned diff_bits,
+                   uint32_t owner, const uint64_t* created_at /* n entries, or NULL */,
+                   uint64_t ctr_start, uint64_t ctr_count,
+                   const volatile uint32_t* cancel_word, uint32_t epoch,
+                   pow_block* out /* n blocks */, size_t* n_mined, uint64_t* hashes_done);
+
 /* In-flight cancellation (the reference re-checks its chain only after a
  * trial, node.cpp:315).  Publishes `epoch`, the caller's current value of the
  * cancel word, to the GPU: a pow_mine / pow_mine_any launch of this ctx whose

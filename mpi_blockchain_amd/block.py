@@ -16,6 +16,9 @@ reference                  here
 ``check_chain`` and more   :func:`verify_chain` (host statement of what
                            ``pow_verify_chain`` checks on the GPU:
                            :meth:`mpi_blockchain_amd.miner.GpuMiner.verify_chain`)
+``proof_of_work``, solo    :func:`mine_chain` (host statement of the blocks
+                           ``pow_mine_chain`` mines on the GPU:
+                           :meth:`mpi_blockchain_amd.miner.GpuMiner.mine_chain`)
 =========================  ====================================================
 """
 from __future__ import annotations
@@ -23,6 +26,7 @@ from __future__ import annotations
 import ctypes
 import hashlib
 import random
+import time
 
 from ._lib import HASH_SIZE, MSG_BYTES, NONCE_SIZE, Block, check, load
 
@@ -39,7 +43,7 @@ MAX_BLOCKS = 200
 ALPHABET = "abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789"
 
 __all__ = ["Block", "make_block", "block_to_str", "solves_problem", "nonce_from_counter",
-           "gen_random_nonce", "field", "set_field", "verify_chain", "V_HASH", "V_WORK", "V_LINK", "V_INDEX", "DEFAULT_DIFFICULTY", "BLOCKS_TO_MINE",
+           "gen_random_nonce", "field", "set_field", "verify_chain", "mine_chain", "V_HASH", "V_WORK", "V_LINK", "V_INDEX", "DEFAULT_DIFFICULTY", "BLOCKS_TO_MINE",
            "VALIDATION_MINUTES", "VALIDATION_BLOCKS", "HASH_SIZE", "NONCE_SIZE", "MSG_BYTES"]
 
 
@@ -137,3 +141,48 @@ def verify_chain(blocks, difficulty: int = DEFAULT_DIFFICULTY) -> list[int]:
                 flags |= V_INDEX
         status.append(flags)
     return status
+
+
+def mine_chain(parent: Block, n: int, difficulty: int = DEFAULT_DIFFICULTY, owner: int = 0, created_at=None,
+               ctr_start: int = 0, ctr_count: int = 1 << 32) -> list[Block]:
+    """The blocks ``pow_mine_chain`` produces, stated on the host with hashlib:
+    `n` blocks on top of `parent`, each the child of the one before, returned
+    tip first (``result[i + 1]`` is the parent of ``result[i]``).
+
+    Block k's template is the block before it copied whole (node.cpp:292-299),
+    then ``index + 1`` in 32 bits, `owner`, `difficulty`, ``created_at[k]`` (one
+    ``time.time()`` for every block if `created_at` is None) and all 256 bytes
+    of the parent's ``block_hash`` as ``previous_block_hash``.  It is sealed
+    with the lowest counter of ``[ctr_start, ctr_start + ctr_count)`` whose
+    digest has `difficulty` leading zero bits: its nonce, and the digest's hex
+    + NUL over the first 65 bytes of ``block_hash`` (node.cpp:318).  Mining
+    stops at the first block whose window holds no solution, so the result may
+    be shorter than `n`."""
+    if not 0 <= difficulty <= 256:
+        raise ValueError(f"difficulty {difficulty} not in 0..256")
+    if created_at is None:
+        created_at = [int(time.time())] * n
+    chain: list[Block] = []
+    last = parent
+    for k in range(n):
+        b = Block()
+        ctypes.memmove(ctypes.addressof(b), ctypes.addressof(last), ctypes.sizeof(Block))  # padding included
+        b.index = (last.index + 1) & 0xFFFFFFFF
+        b.node_owner_number = owner & 0xFFFFFFFF
+        b.difficulty = difficulty & 0xFFFFFFFF
+        b.created_at = created_at[k] & 0xFFFFFFFFFFFFFFFF
+        set_field(b, "previous_block_hash", field(last, "block_hash"))
+        msg = bytearray(block_to_str(b))
+        for ctr in range(ctr_start, ctr_start + ctr_count):
+            nonce = nonce_from_counter(ctr)
+            msg[4:4 + NONCE_SIZE] = nonce
+            digest = hashlib.sha256(msg).digest()
+            if 256 - int.from_bytes(digest, "big").bit_length() >= difficulty:
+                break
+        else:
+            break
+        set_field(b, "nonce", nonce)
+        ctypes.memmove(ctypes.addressof(b) + Block.block_hash.offset, digest.hex().encode() + b"\0", 65)
+        chain.insert(0, b)
+        last = b
+    return chain

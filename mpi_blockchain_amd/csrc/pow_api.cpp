@@ -11,6 +11,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <ctime>
 #include <thread>
 #include <vector>
 
@@ -416,6 +417,9 @@ void pow_destroy(pow_ctx* ctx) {
   (void)hipFree(ctx->d_vstatus);
   (void)hipFree(ctx->d_vres);
   if (ctx->h_vres) (void)hipHostFree(ctx->h_vres);
+  (void)hipFree(ctx->d_chain);
+  (void)hipFree(ctx->d_cslot);
+  if (ctx->h_chain) (void)hipHostFree(ctx->h_chain);
   if (ctx->h_res) (void)hipHostFree(ctx->h_res);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -792,6 +796,150 @@ int pow_mine_any(pow_ctx* ctx, const pow_block* tmpl, uint64_t ctr_start, uint64
                  pow_block* out, uint64_t* found_ctr, uint64_t* hashes_done) {
   return mine_impl(ctx, tmpl, ctr_start, ctr_count, diff_bits, cancel_word, epoch, out, found_ctr,
                    hashes_done, true);
+}
+
+namespace {
+
+static_assert(offsetof(PowChainBuf, ctl) == sizeof(pow_block) &&
+                  offsetof(PowChainBuf, blk) == offsetof(PowChainBuf, ctl) + sizeof(PowChainCtl),
+              "parent + ctl go up, ctl + blocks come down: one copy each");
+
+// The buffers of the fused path, made at the first call that needs them.
+int ensure_chain(pow_ctx* ctx) {
+  if (!ctx->d_chain) HIP_OK(hipMalloc(&ctx->d_chain, sizeof(PowChainBuf)));
+  if (!ctx->h_chain) HIP_OK(hipHostMalloc(&ctx->h_chain, sizeof(PowChainBuf), hipHostMallocDefault));
+  if (!ctx->d_cslot) {
+    // One workgroup (four waves, one per SIMD) per CU at most: a trial is one
+    // dependent chain that keeps its SIMD's VALU busy alone, so further waves
+    // only stretch every trial.
+    const unsigned cap = (unsigned)std::max(1, ctx->cu_count);
+    HIP_OK(hipMalloc(&ctx->d_cslot, (size_t)cap * sizeof(PowChainSlot)));
+    ctx->chain_grid_max = cap;
+  }
+  return POW_OK;
+}
+
+// The template refresh of node.cpp:292-299 on the host (the host loop's).
+void refresh(pow_block* t, const pow_block* last, uint32_t owner, unsigned diff, uint64_t created_at) {
+  memcpy(t, last, sizeof *t);  // whole: padding included
+  t->index = last->index + 1u;
+  t->node_owner_number = owner;
+  t->difficulty = diff;
+  t->created_at = created_at;
+  memcpy(t->previous_block_hash, last->block_hash, POW_HASH_SIZE);  // all 256 bytes (trap T5)
+}
+
+}  // namespace
+
+// K4, one launch per block, in batches queued without a host wait; above
+// ctx->chain_fused_max the same blocks through refresh + pow_mine.
+int pow_mine_chain(pow_ctx* ctx, const pow_block* parent, size_t n, unsigned diff_bits, uint32_t owner,
+                   const uint64_t* created_at, uint64_t ctr_start, uint64_t ctr_count,
+                   const volatile uint32_t* cancel_word, uint32_t epoch, pow_block* out, size_t* n_mined,
+                   uint64_t* hashes_done) {
+  if (diff_bits > 256) return fail(POW_EINVAL, "diff_bits %u > 256", diff_bits);
+  if (ctr_count == 0 || ctr_count > (1ull << 32))
+    return fail(POW_EINVAL, "ctr_count %llu not in 1..2^32", (unsigned long long)ctr_count);
+  if (ctr_start >= POW_COUNTER_LIMIT || ctr_count > POW_COUNTER_LIMIT - ctr_start)
+    return fail(POW_EINVAL, "counter range past 62^9");
+  if (n > (1u << 24)) return fail(POW_EINVAL, "chain too large (%zu blocks > 2^24)", n);
+  if (!ctx || ((!parent || !out) && n)) return fail(POW_EINVAL, "null");
+  if (ctx->board) return fail(POW_EINVAL, "pow_mine_chain does not run on a context bound to a stop board");
+  ctx->stats = pow_stats{};
+  if (n_mined) *n_mined = 0;
+  if (hashes_done) *hashes_done = 0;
+  if (n == 0) return 1;
+  if (int rc = set_dev(ctx)) return rc;
+  const uint64_t now = created_at ? 0 : (uint64_t)time(nullptr);
+  pow_stats total{};
+  size_t done = 0;
+  auto finish = [&](int rc) {
+    ctx->stats = total;
+    if (n_mined) *n_mined = done;
+    if (hashes_done) *hashes_done = total.hashes;
+    return rc;
+  };
+  if (diff_bits > 32 || (int)diff_bits > ctx->chain_fused_max) {
+    pow_block last = *parent;
+    while (done < n && !cancel_moved(cancel_word, epoch)) {
+      pow_block tmpl, blk;
+      refresh(&tmpl, &last, owner, diff_bits, created_at ? created_at[done] : now);
+      const int rc = mine_impl(ctx, &tmpl, ctr_start, ctr_count, diff_bits, cancel_word, epoch, &blk, nullptr, nullptr,
+                               false);
+      total.kernel_ms += ctx->stats.kernel_ms;
+      total.launches += ctx->stats.launches;
+      total.hashes += ctx->stats.hashes;
+      if (rc < 0) return finish(rc);
+      if (rc == 0) break;
+      out[n - 1 - done] = last = blk;
+      ++done;
+    }
+    return finish(done == n ? 1 : 0);
+  }
+  if (cancel_moved(cancel_word, epoch)) return finish(0);
+  if (int rc = ensure_chain(ctx)) return rc;
+  PowChainLaunch L;
+  {
+    PowLaunchLat digits;
+    make_launch_lat(ctr_start, ctr_count, diff_bits, &digits);
+    memset(&L, 0, sizeof L);
+    memcpy(L.base_digit, digits.base_digit, sizeof L.base_digit);
+    L.thr = digits.thr;
+    L.owner = owner;
+    L.diff = diff_bits;
+    L.count = ctr_count;
+  }
+  // The grid follows the difficulty: lanes for four times the expected 2^d
+  // trials (a block then costs one trial's latency but for 1 in e^4; at d = 9
+  // and 13 two times measured 1.4 and 0.6 us per block slower, eight times 0.3
+  // and 2.2 us: more workgroups to start and to count out), no more than the
+  // window has counters or the chip takes at one wave per SIMD; the lanes of a
+  // full grid walk on through the window.
+  {
+    const uint64_t lanes = std::min<uint64_t>(1ull << (diff_bits + ctx->chain_lanes_log2), ctr_count);
+    L.nwg = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((lanes + 255) / 256, ctx->chain_grid_max));
+  }
+  // A batch is about 2^26 expected trials (a handful of ms: the cancel latency).
+  const size_t batch =
+      ctx->chain_batch ? std::min<size_t>(ctx->chain_batch, POW_CHAIN_MAX_BATCH)
+                       : std::max<size_t>(1, std::min<size_t>(POW_CHAIN_MAX_BATCH, (size_t)1 << (26 - std::min(diff_bits, 26u))));
+  PowChainBuf* const H = ctx->h_chain;
+  PowChainBuf* const D = ctx->d_chain;
+  H->parent = *parent;
+  while (done < n) {
+    if (cancel_moved(cancel_word, epoch)) return finish(0);
+    const size_t nb = std::min(batch, n - done);
+    memset(&H->ctl, 0, sizeof H->ctl);
+    H->ctl.min_rel = ~0ull;
+    HIP_OK(hipMemcpyAsync(D, H, offsetof(PowChainBuf, blk), hipMemcpyHostToDevice, ctx->stream));
+    if (pow_hooks)
+      if (int rc = pow_hooks->before_launch(ctx)) return rc;
+    HIP_OK(hipEventRecord(ctx->ev0, ctx->stream));
+    for (size_t j = 0; j < nb; ++j) {
+      L.created_at = created_at ? created_at[done + j] : now;
+      const pow_block* const prev = j == 0 ? &D->parent : &D->blk[nb - j];
+      HIP_OK(pow_launch_chain(ctx->stream, L, (const uint32_t*)prev, (uint32_t*)&D->blk[nb - 1 - j], &D->ctl,
+                              ctx->d_cslot));
+    }
+    HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_OK(hipMemcpyAsync(&H->ctl, &D->ctl, sizeof(PowChainCtl) + nb * sizeof(pow_block), hipMemcpyDeviceToHost,
+                          ctx->stream));
+    if (int rc = stream_wait_for(ctx, "chain mining batch", 2ull * nb * ctr_count)) return rc;  // 2 ns per counter
+    float ms = 0;
+    HIP_OK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    total.kernel_ms += ms;
+    total.launches += (uint32_t)nb;
+    total.hashes += H->ctl.hashes;
+    const size_t m = H->ctl.n_done;
+    if (m > nb || (m < nb && !H->ctl.stop)) return fail(POW_EHIP, "chain mining batch: %zu of %zu blocks and no stop word", m, nb);
+    // Block done + j is blk[nb - 1 - j] and goes to out[n - 1 - done - j]:
+    // the m sealed ones are the batch's upper m slots, contiguous in both.
+    if (m) memcpy(out + (n - done - m), &H->blk[nb - m], m * sizeof(pow_block));
+    done += m;
+    if (m < nb) return finish(0);  // a window without a solution
+    H->parent = H->blk[0];         // the tip: the next batch's parent
+  }
+  return finish(1);
 }
 
 int pow_cancel(pow_ctx* ctx, uint32_t epoch) {

@@ -24,6 +24,44 @@ struct PowVerifyRes {
   unsigned int n_bad;      // flagged blocks (atomic add)
 };
 
+// K4 (pow_chain_kernel, pow_chain.hip), one launch per block of pow_mine_chain.
+#define POW_CHAIN_MAX_BATCH 64   // launches queued without a host wait
+// pow_mine_chain: above it the host loop over pow_mine.  The largest measured d
+// at which the fused call beat the host loop (profiles/mine_chain/README.md).
+#define POW_CHAIN_FUSED_MAX_D 23
+// Control words of a batch: reset by the host before the batch; min_rel and
+// exits are reset again by each launch's sealing workgroup for the next one.
+struct PowChainCtl {
+  unsigned long long min_rel;  // lowest solving (counter - ctr_start) of the running launch (atomic min); ~0 = none
+  unsigned long long hashes;   // trials computed, all launches of the batch (added by each launch's sealer)
+  unsigned long long exits;    // the running launch: workgroups that have left (low 24 bits), their trials above
+  unsigned int stop;           // a launch's window held no solution: every later launch exits at once
+  unsigned int n_done;         // blocks sealed by the batch
+};
+// One workgroup's lowest hit of a launch, written before it leaves (rel = ~0: none).
+struct PowChainSlot {
+  unsigned long long rel;
+  unsigned int digest[8];
+};
+// A batch in device memory, and its pinned twin: parent and ctl go up in one
+// copy, ctl and the sealed blocks come down in one.  Block j of the batch is
+// blk[nb - 1 - j] (tip first); its launch reads blk[nb - j], the first parent.
+struct PowChainBuf {
+  pow_block parent;
+  PowChainCtl ctl;
+  pow_block blk[POW_CHAIN_MAX_BATCH];
+};
+// The arguments of one launch.
+struct PowChainLaunch {
+  uint32_t base_digit[9];  // base-62 digits of ctr_start (nonce[0..8])
+  uint32_t thr;            // a digest solves iff H0 <= thr (d <= 32)
+  uint32_t owner, diff;    // the template's node_owner_number and difficulty
+  uint32_t nwg;            // workgroups of the launch (= gridDim.x)
+  uint32_t pad;
+  uint64_t count;          // counters [ctr_start, ctr_start + count), count <= 2^32
+  uint64_t created_at;     // the template's created_at
+};
+
 struct pow_ctx {
   int device = 0;
   int cu_count = 0;
@@ -72,6 +110,10 @@ struct pow_ctx {
   size_t verify_cap = 0;             // ... both sized for this many blocks
   PowVerifyRes* d_vres = nullptr;    // K3's result words ...
   PowVerifyRes* h_vres = nullptr;    // ... and their pinned twin: reset value up, result down
+  PowChainBuf* d_chain = nullptr;    // pow_mine_chain: a batch on the device ...
+  PowChainBuf* h_chain = nullptr;    // ... its pinned twin ...
+  PowChainSlot* d_cslot = nullptr;   // ... and one slot per workgroup of a launch
+  unsigned chain_grid_max = 0;       // slots allocated = the largest grid of a K4 launch
   unsigned grid_full = 0;  // workgroups that fill the chip (8 per CU)
   // Set only by the test library's hooks (pow_hooks.cpp, at pow_init):
   bool force_full = false;        // use the d > 32 kernel for every d
@@ -80,6 +122,9 @@ struct pow_ctx {
   unsigned lat_wps = 0;           // K1' waves per SIMD at every d (0 = the plan)
   bool sentinel_idle = false;     // K1 mine launches: the sentinel wave takes no chunk (POW_LAUNCH_SENTINEL_IDLE)
   unsigned test_stall_us = 0;     // a bounded stall kernel in front of every HIP launch (watchdog tests)
+  unsigned chain_batch = 0;       // pow_mine_chain: blocks per batch (0 = the plan)
+  unsigned chain_lanes_log2 = 2;  // K4's grid: lanes = 2^this x the expected 2^d trials
+  int chain_fused_max = POW_CHAIN_FUSED_MAX_D;  // pow_mine_chain: highest d on the fused path (-1 = host loop only)
   // K1' and K2' launches as AQL packets (pow_aql.cpp) instead of
   // hipLaunchKernel: test library only, opt-in there; null = the HIP launch
   // path, the only one the shipped library has.
@@ -104,6 +149,8 @@ hipError_t pow_launch_hash(uint32_t n, hipStream_t stream, const uint32_t* msgs,
 hipError_t pow_launch_hash_one(hipStream_t stream, const PowMsg& M, PowHashOut* hout, uint32_t seq);
 hipError_t pow_launch_verify(uint32_t n_check, uint32_t n_avail, unsigned diff, hipStream_t stream,
                              const uint32_t* blocks, uint8_t* status, PowVerifyRes* res);
+hipError_t pow_launch_chain(hipStream_t stream, const PowChainLaunch& L, const uint32_t* prev, uint32_t* dst,
+                            PowChainCtl* ctl, PowChainSlot* slots);
 hipError_t pow_sort_u32(void* temp, size_t* temp_bytes, uint32_t* keys, uint32_t* alt, uint32_t n,
                         uint32_t** sorted, hipStream_t stream);
 hipError_t pow_launch_search_lat(bool full, bool any, bool asm_groups, unsigned grid, hipStream_t stream,

@@ -27,6 +27,11 @@ void configure(pow_ctx* ctx) {
   if (const char* lw = getenv("POW_LAT_WPS")) ctx->lat_wps = (unsigned)std::min(8ul, strtoul(lw, nullptr, 0));
   if (const char* si = getenv("POW_TEST_SENTINEL_IDLE")) ctx->sentinel_idle = si[0] == '1';
   if (const char* ts = getenv("POW_TEST_STALL_US")) ctx->test_stall_us = (unsigned)strtoul(ts, nullptr, 0);
+  // pow_mine_chain: blocks per batch, and the highest d on the fused path (-1: the host loop at every d)
+  if (const char* cb = getenv("POW_CHAIN_BATCH")) ctx->chain_batch = (unsigned)std::min(64ul, strtoul(cb, nullptr, 0));
+  if (const char* cf = getenv("POW_CHAIN_FUSED_MAX")) ctx->chain_fused_max = (int)std::max(-1l, std::min(32l, strtol(cf, nullptr, 0)));
+  // K4's grid: lanes = 2^n times the expected trials (the result must not depend on it)
+  if (const char* cl = getenv("POW_CHAIN_LANES_LOG2")) ctx->chain_lanes_log2 = (unsigned)std::min(8ul, strtoul(cl, nullptr, 0));
   if (const char* g = getenv("POW_GRID_PER_CU")) {  // launch-geometry experiments
     const int per = atoi(g);
     if (per > 0 && per <= 64) ctx->grid_full = (unsigned)ctx->cu_count * (unsigned)per;

@@ -32,6 +32,15 @@ class VerifyResult:
     status: np.ndarray    # np.uint8 per block: OR of block.V_HASH / V_WORK / V_LINK / V_INDEX
 
 
+@dataclass
+class MineChainResult:
+    blocks: ctypes.Array  # the mined chain, tip first: Block * n_mined
+    n_mined: int          # blocks mined
+    complete: bool        # all n were mined (pow_mine_chain returned 1)
+    hashes: int           # trials issued
+    kernel_ms: float      # GPU time of the call
+
+
 def refresh_template(last: Block, rank: int, difficulty: int = DEFAULT_DIFFICULTY,
                      now: int | None = None) -> Block:
     """node.cpp:292-299: copy the last block, index+1, owner = rank,
@@ -173,6 +182,32 @@ class GpuMiner:
             return None
         return MineResult(out, ctr.value, hashes.value, self.stats()["kernel_ms"])
 
+    def mine_chain(self, parent: Block, n: int, difficulty: int = DEFAULT_DIFFICULTY, owner: int = 0,
+                   created_at=None, ctr_start: int = 0, ctr_count: int = 1 << 32,
+                   epoch: int | None = None) -> MineChainResult:
+        """pow_mine_chain: `n` blocks on top of `parent`, each the child of the
+        one before, every one the lowest solving counter of the same window.
+        ``blocks`` is the mined chain tip first, a ctypes ``Block * n_mined``
+        array (what :meth:`verify_chain` takes); it is shorter than `n` if a
+        window held no solution or :meth:`cancel` was called meanwhile.  The
+        host statement of the result is :func:`mpi_blockchain_amd.block.mine_chain`."""
+        out = (Block * max(n, 1))()
+        times = None
+        if created_at is not None:
+            if len(created_at) != n:
+                raise ValueError(f"created_at has {len(created_at)} entries for {n} blocks")
+            times = (ctypes.c_uint64 * max(n, 1))(*created_at)
+        mined, hashes = ctypes.c_size_t(), ctypes.c_uint64()
+        ep = self._cancel.value if epoch is None else epoch
+        rc = check(self.L.pow_mine_chain(self.ctx, ctypes.byref(parent), n, difficulty, owner, times, ctr_start,
+                                         ctr_count, ctypes.byref(self._cancel), ep, out, ctypes.byref(mined),
+                                         ctypes.byref(hashes)), self.L)
+        m = mined.value
+        blocks = (Block * m)()
+        if m:
+            ctypes.memmove(blocks, ctypes.byref(out, (n - m) * ctypes.sizeof(Block)), m * ctypes.sizeof(Block))
+        return MineChainResult(blocks, m, rc == 1, hashes.value, self.stats()["kernel_ms"])
+
     def sweep(self, tmpl: Block, start: int, count: int, difficulty: int, cap: int | None = None) -> np.ndarray:
         """Ascending (counter - start) of every solving counter (count <= 2^32)."""
         if cap is None:  # pow_sweep sorts on the device: at most 2^31 - 1 entries
@@ -264,5 +299,5 @@ def block_hex(b: Block) -> str:
     return field(b, "block_hash").split(b"\0", 1)[0].decode()
 
 
-__all__ = ["GpuMiner", "DeviceBuffer", "StopBoard", "MineResult", "VerifyResult", "refresh_template", "proof_of_work_round", "block_hex",
+__all__ = ["GpuMiner", "DeviceBuffer", "StopBoard", "MineResult", "MineChainResult", "VerifyResult", "refresh_template", "proof_of_work_round", "block_hex",
            "nonce_from_counter"]

@@ -1,0 +1,98 @@
+"""Codegen and source guards for the chain-mining kernel K4
+(csrc/pow_chain.hip; CPU only: hipcc cross-compiles gfx950)."""
+import os
+import re
+import subprocess
+import tempfile
+
+import pytest
+
+from mpi_blockchain_amd import _lib
+
+from test_build import CSRC, ROOT, null_stream_calls
+
+KERNEL = "_Z16pow_chain_kernel"
+SWITCHES = (b"POW_CHAIN_BATCH", b"POW_CHAIN_FUSED_MAX", b"POW_CHAIN_LANES_LOG2")
+
+
+@pytest.fixture(scope="module")
+def isa():
+    from mpi_blockchain_amd.build import hipcc
+
+    with tempfile.TemporaryDirectory() as td:
+        subprocess.run([hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-mcode-object-version=5",
+                        "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-c",
+                        os.path.join(CSRC, "pow_chain.hip"), "-o", os.path.join(td, "c.o"),
+                        "-save-temps=obj"], check=True, cwd=td, capture_output=True)
+        s = [f for f in os.listdir(td) if f.endswith("gfx950.s")]
+        assert s
+        return open(os.path.join(td, s[0])).read()
+
+
+def kernel_metadata(isa: str) -> dict:
+    for blk in isa.split("  - .agpr_count")[1:]:
+        nm = re.search(r"\.name:\s+(\S+)", blk)
+        if nm and nm.group(1).startswith(KERNEL):
+            return {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*$", blk, flags=re.M)}
+    raise AssertionError(KERNEL)
+
+
+def test_chain_kernel_has_no_scratch(isa):
+    md = kernel_metadata(isa)
+    assert md["private_segment_fixed_size"] == 0, md
+    assert md["vgpr_spill_count"] == 0 and md["sgpr_spill_count"] == 0, md
+    # four waves per SIMD, the most pow_mine_chain launches, need at most 128 VGPRs
+    assert md["vgpr_count"] <= 128, md
+    assert md["wavefront_size"] == 64 and md["max_flat_workgroup_size"] == 256, md
+    # the parent, the message, the sealed block and a few words: nowhere near a CU's LDS
+    assert 2 * 552 + 320 <= md["group_segment_fixed_size"] <= 4096, md
+    m = re.search(rf"^({KERNEL}\w*):[^\n]*\n(.*?)s_endpgm", isa, flags=re.S | re.M)
+    assert m and not re.search(r"^\s+scratch_", m.group(2), flags=re.M)
+
+
+def test_chain_kernel_is_in_both_libraries():
+    from mpi_blockchain_amd import build
+
+    for test in (False, True):
+        assert os.path.join(CSRC, "pow_chain.hip") in build.sources(test=test)
+
+
+def test_no_null_stream_in_chain_sources():
+    found = {}
+    for f in ("pow_chain.hip", "pow_api.cpp", "pow_ctx.h"):
+        hits = null_stream_calls(open(os.path.join(CSRC, f)).read())
+        if hits:
+            found[f] = hits
+    assert not found, found
+    api = open(os.path.join(CSRC, "pow_api.cpp")).read()
+    body = api[api.index("int pow_mine_chain("):]
+    body = body[:body.index("\n}\n")]
+    assert not null_stream_calls(body)
+    # plain stream launches behind one bounded wait per batch; no graph
+    assert "pow_launch_chain(ctx->stream" in body and body.count("stream_wait_for(") == 1
+    assert "hipGraph" not in api and "hipGraph" not in open(os.path.join(CSRC, "pow_chain.hip")).read()
+
+
+def test_chain_kernel_never_waits_for_another_workgroup():
+    """No grid barrier and no loop on a word another workgroup writes: the only
+    loops of the kernel are the lane's walk of its counters, the chunk loop and
+    the sealer's strided passes."""
+    src = open(os.path.join(CSRC, "pow_chain.hip")).read()
+    assert "cooperative_groups" not in src and "grid.sync" not in src
+    loops = re.findall(r"\b(?:while|for)\s*\(([^\n]*)\)\s*\{?\s*$", src, flags=re.M)
+    assert loops
+    for cond in loops:
+        assert "exits" not in cond and "stop" not in cond and "n_done" not in cond, cond
+
+
+def test_switches_only_in_the_test_library():
+    shipped = open(_lib.LIB_PATH, "rb").read()
+    test = open(_lib.TEST_LIB_PATH, "rb").read()
+    assert [s for s in SWITCHES if s in shipped] == []
+    assert all(s in test for s in SWITCHES)
+    hooks = open(os.path.join(CSRC, "pow_hooks.cpp")).read()
+    for f in os.listdir(CSRC):
+        p = os.path.join(CSRC, f)
+        if os.path.isfile(p) and f != "pow_hooks.cpp":
+            assert 'getenv("POW_CHAIN' not in open(p).read(), f
+    assert 'getenv("POW_CHAIN_BATCH")' in hooks and 'getenv("POW_CHAIN_FUSED_MAX")' in hooks
