@@ -2,7 +2,8 @@
 // libpow_gpu_test.so only (build.py TEST_ONLY), never into the shipped
 // libpow_gpu.so.  The test and tuning switches read from the environment at
 // pow_init, the direct-dispatch launch path (pow_aql.cpp, POW_AQL=1), the stall
-// kernel of the watchdog tests and the stand-in RCCL of the shard tests.
+// kernel of the watchdog tests, the stand-in RCCL of the shard tests and
+// pow_test_leading_zero_bits, the only export the shipped library does not have.
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -16,6 +17,7 @@
 #include "pow_ctx.h"
 
 hipError_t pow_launch_test_stall(hipStream_t stream, unsigned us, int realtime_khz);  // pow_test_kernels.hip
+hipError_t pow_launch_test_lz(hipStream_t stream, const uint32_t* digests, uint32_t n, uint32_t* out);
 
 namespace {
 
@@ -150,3 +152,30 @@ const pow_test_hooks kHooks = {configure,   open_path, before_launch, dispatch_l
 const bool kRegistered = (pow_hooks = &kHooks, true);  // as the library loads
 
 }  // namespace
+
+// The kernels' leading-zero count (sha256_dev.h leading_zero_bits) of n digests
+// of the caller's choosing: digests = n x 8 words, most significant first;
+// out = n counts.  One launch of pow_test_lz on the context's stream.
+extern "C" int pow_test_leading_zero_bits(pow_ctx* ctx, const uint32_t* digests, size_t n, uint32_t* out) {
+  if (!ctx || ((!digests || !out) && n)) return fail(POW_EINVAL, "null");
+  if (n > (1u << 20)) return fail(POW_EINVAL, "too many digests (%zu > 2^20)", n);
+  if (n == 0) return POW_OK;
+  HIP_OK(hipSetDevice(ctx->device));
+  uint32_t* d_in = nullptr;
+  uint32_t* d_out = nullptr;
+  int rc = POW_OK;
+  auto step = [&](hipError_t e, const char* what) {
+    if (rc == POW_OK && e != hipSuccess) rc = fail(POW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
+  };
+  step(hipMalloc(&d_in, n * 32), "hipMalloc");
+  step(hipMalloc(&d_out, n * 4), "hipMalloc");
+  if (rc == POW_OK) step(hipMemcpyAsync(d_in, digests, n * 32, hipMemcpyHostToDevice, ctx->stream), "copy in");
+  if (rc == POW_OK) step(pow_launch_test_lz(ctx->stream, d_in, (uint32_t)n, d_out), "pow_test_lz");
+  if (rc == POW_OK) step(hipMemcpyAsync(out, d_out, n * 4, hipMemcpyDeviceToHost, ctx->stream), "copy out");
+  if (rc == POW_OK) rc = pow_ctx_stream_wait(ctx, "pow_test_lz", 0);
+  if (rc == POW_OK || !ctx->wedged) {  // after a watchdog the launch may still write
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+  }
+  return rc;
+}

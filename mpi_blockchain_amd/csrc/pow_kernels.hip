@@ -264,14 +264,7 @@ __device__ __forceinline__ void publish_hit(const PowWatch& w, unsigned long lon
 }
 
 // Leading zero bits of the 256-bit digest H[0..7] >= d  (d > 32 path only).
-__device__ __forceinline__ bool full_test(const uint32_t H[8], uint32_t d) {
-  uint32_t lz = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    if (lz == 32u * i) lz += (H[i] == 0u) ? 32u : (uint32_t)__builtin_clz(H[i]);
-  }
-  return lz >= d;
-}
+__device__ __forceinline__ bool full_test(const uint32_t H[8], uint32_t d) { return leading_zero_bits(H) >= d; }
 
 }  // namespace
 

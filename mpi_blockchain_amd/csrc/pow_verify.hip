@@ -57,17 +57,6 @@ __device__ __forceinline__ uint32_t hex_of16(uint32_t x) {
   return hex4(((x >> 12) & 0xFu) | ((x & 0xF00u)) | ((x & 0xF0u) << 12) | ((x & 0xFu) << 24));
 }
 
-// Leading zero bits of the 256-bit digest, over all eight words (the same
-// full-width form as K1's d > 32 test), for every difficulty 0..256.
-__device__ __forceinline__ uint32_t leading_zero_bits(const uint32_t H[8]) {
-  uint32_t lz = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    if (lz == 32u * i) lz += (H[i] == 0u) ? 32u : (uint32_t)__builtin_clz(H[i]);
-  }
-  return lz;
-}
-
 }  // namespace
 
 // blocks: n_avail structs, of which the first n_check are verified; block

@@ -46,6 +46,18 @@ __device__ constexpr uint32_t K[64] = {
 __device__ constexpr uint32_t IV[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef372, 0xa54ff53a,
                                        0x510e527f, 0x9b05688c, 0x1f83d9ab, 0x5be0cd19};
 
+// Leading zero bits of the 256-bit digest H[0..7] (0..256): a word counts
+// only while every word before it was zero.  K1 and K1' (their d > 32 test),
+// K3 (every difficulty) and the test library's pow_test_lz share it.
+__device__ __forceinline__ uint32_t leading_zero_bits(const uint32_t H[8]) {
+  uint32_t lz = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    if (lz == 32u * i) lz += (H[i] == 0u) ? 32u : (uint32_t)__builtin_clz(H[i]);
+  }
+  return lz;
+}
+
 // Working variables of one compression.  Rounds "rename" instead of moving:
 // in the fully unrolled code the shifts below are SSA renames, not v_mov.
 struct St {
