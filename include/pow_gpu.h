@@ -246,6 +246,68 @@ int pow_mine_chain(pow_ctx* ctx, const pow_block* parent, size_t n, unsigned dif
                    const volatile uint32_t* cancel_word, uint32_t epoch,
                    pow_block* out /* n blocks */, size_t* n_mined, uint64_t* hashes_done);
 
+/* Mine n independent templates in one call: the reference's own workload, N
+ * ranks each on its own template over the same parent (node.cpp:292-302), and
+ * every other caller that holds many templates at once (a difficulty ladder,
+ * the candidates after a fork, a simulated network on one GPU).
+ * For every i < n the call gives exactly what pow_mine(ctx, &tmpls[i],
+ * ctr_start, ctr_count, diff_bits, ...) gives; the templates share the window
+ * and the difficulty, and one window without a solution stops nothing else.
+ *   solved:   out[i] = tmpls[i] copied whole (552 bytes, padding included)
+ *             with nonce = the 9 base-62 characters + NUL of the LOWEST
+ *             solving counter of [ctr_start, ctr_start + ctr_count) and
+ *             block_hash[0..64] = the 64 hex characters + NUL of the digest
+ *             the GPU computed (bytes 65..255 stay the template's,
+ *             node.cpp:318); found_ctr[i] = that counter.
+ *   unsolved, or unreached (the call was cancelled before the template's
+ *             launch): out[i] is not touched, found_ctr[i] = UINT64_MAX.
+ * found_ctr (may be NULL): all n entries are written on every return >= 0.
+ * out == tmpls (exactly the same array: sealing in place) is allowed; any
+ * other overlap is not.
+ * Returns 1 if all n were solved; 0 if some window held no solution or the
+ * cancel word (optional; read at entry and between launches) differs from
+ * `epoch`; *n_solved (may be NULL) says how many were solved.  n = 0 returns 1.
+ * POW_EINVAL, checked in this order before the context is touched and with
+ * nothing written: diff_bits > 256; ctr_count == 0 or > 2^32; ctr_start +
+ * ctr_count > 62^9; n > 2^24; a null ctx, or null tmpls or out with n > 0; a
+ * context bound to a stop board (boards and pow_cancel's in-flight path are
+ * not part of this call).
+ * Paths (all give the same bytes): n == 1 is pow_mine itself.  Above d =
+ * POW_BATCH_FUSED_MAX_D (csrc/pow_ctx.h; never above 32) the call runs the
+ * host loop itself: pow_mine template by template with the same cancel word.
+ * Otherwise the templates run fused, in tiles: per tile one copy up of the raw
+ * structs, ONE launch whose grid holds every template of the tile (256 lanes
+ * per workgroup; per template lanes for four times the expected 2^d trials,
+ * lowered to twice and then once while the launch's workgroups exceed one per
+ * CU, and at most one workgroup per CU per template), one copy back of 48 bytes per
+ * template and one bounded wait (10 s + 2 ns per counter of the tile's
+ * windows); the host seals the blocks from the GPU's digests.  A tile is the
+ * largest number of templates for which expected trials stay at or below
+ * 2^26 (the cancel latency, a handful of milliseconds), workgroups at or
+ * below 2^16, tile x ctr_count at or below 2^38 (so the watchdog stays a real
+ * bound: 550 s at worst) and the tile at or below 2^14.  A 2^32 window
+ * therefore gives tiles of 64 templates: a caller who wants large tiles passes
+ * a window near what it needs, e.g. 2^(d + 7) counters.
+ * Device memory: 12.7 MB, made at the first fused call, however large n is.
+ * *hashes_done (may be NULL) = trials issued.  pow_get_stats: launches,
+ * kernel_ms (fused: events around each launch) and hashes.
+ * pow_warmup does not launch this call's kernel (nor pow_verify_chain's or
+ * pow_mine_chain's): the first fused call of a process also loads its code
+ * object and makes the buffers.
+ * Cost (MI355X, profiles/mine_batch/README.md; medians of 9 calls, per
+ * template, against the loop around pow_mine from C): 64 templates take 1.20 us
+ * each at d = 9 (the loop: 35.7), 4.03 at d = 13 (34.7), 37.1 at d = 17 (51.9),
+ * 97.7 at d = 19 (113.1), 346 at d = 21 (500) and 1,082 at d = 23 (3,035);
+ * 1,024 templates at d = 9 take 0.36 us each over a 2^16 window (one launch)
+ * and 1.28 over 2^32 (tiles of 64).  Two templates save one launch at d = 9
+ * (26.9 against 39.8 us each) and nothing at d = 19 (135 against 132).
+ * Nothing above d = 23 was measured. */
+int pow_mine_batch(pow_ctx* ctx, const pow_block* tmpls, size_t n, unsigned diff_bits,
+                   uint64_t ctr_start, uint64_t ctr_count,
+                   const volatile uint32_t* cancel_word, uint32_t epoch,
+                   pow_block* out /* n */, uint64_t* found_ctr /* n, may be NULL */,
+                   size_t* n_solved /* may be NULL */, uint64_t* hashes_done /* may be NULL */);
+
 /* In-flight cancellation (the reference re-checks its chain only after a
  * trial, node.cpp:315).  Publishes `epoch`, the caller's current value of the
  * cancel word, to the GPU: a pow_mine / pow_mine_any launch of this ctx whose

@@ -19,7 +19,10 @@ reference                  here
 ``proof_of_work``, solo    :func:`mine_chain` (host statement of the blocks
                            ``pow_mine_chain`` mines on the GPU:
                            :meth:`mpi_blockchain_amd.miner.GpuMiner.mine_chain`)
-=========================  ====================================================
+``proof_of_work``, N       :func:`mine_batch` (host statement of what
+ranks on one parent        ``pow_mine_batch`` mines on the GPU for many templates:
+                           :meth:`mpi_blockchain_amd.miner.GpuMiner.mine_batch`)
+=============================================================================
 """
 from __future__ import annotations
 
@@ -43,7 +46,7 @@ MAX_BLOCKS = 200
 ALPHABET = "abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789"
 
 __all__ = ["Block", "make_block", "block_to_str", "solves_problem", "nonce_from_counter",
-           "gen_random_nonce", "field", "set_field", "verify_chain", "mine_chain", "V_HASH", "V_WORK", "V_LINK", "V_INDEX", "DEFAULT_DIFFICULTY", "BLOCKS_TO_MINE",
+           "gen_random_nonce", "field", "set_field", "verify_chain", "mine_chain", "mine_batch", "V_HASH", "V_WORK", "V_LINK", "V_INDEX", "DEFAULT_DIFFICULTY", "BLOCKS_TO_MINE",
            "VALIDATION_MINUTES", "VALIDATION_BLOCKS", "HASH_SIZE", "NONCE_SIZE", "MSG_BYTES"]
 
 
@@ -186,3 +189,55 @@ def mine_chain(parent: Block, n: int, difficulty: int = DEFAULT_DIFFICULTY, owne
         chain.insert(0, b)
         last = b
     return chain
+
+
+def mine_batch(tmpls, difficulty: int = DEFAULT_DIFFICULTY, ctr_start: int = 0,
+               ctr_count: int = 1 << 32) -> list[tuple[Block | None, int | None]]:
+    """What ``pow_mine_batch`` produces, stated on the host with hashlib: for
+    every template of `tmpls`, on its own, ``(block, counter)`` with the lowest
+    counter of ``[ctr_start, ctr_start + ctr_count)`` whose digest has
+    `difficulty` leading zero bits, or ``(None, None)`` if the window holds
+    none (the other templates are mined all the same).
+
+    The block is the template copied whole (padding included) with the
+    counter's nonce (9 base-62 characters + NUL) and the digest's hex + NUL
+    over the first 65 bytes of ``block_hash`` (node.cpp:318: the bytes behind
+    them stay the template's).  The nonce is made here, in Python, from the
+    alphabet of block.cpp:61-72."""
+    if not 0 <= difficulty <= 256:
+        raise ValueError(f"difficulty {difficulty} not in 0..256")
+    if ctr_start < 0 or ctr_count < 0 or ctr_start + ctr_count > 62 ** 9:
+        raise ValueError("counter range past 62^9")
+    limit = 1 << (256 - difficulty)  # a digest solves iff it is below
+    abc = ALPHABET.encode()
+    results: list[tuple[Block | None, int | None]] = []
+    for t in tmpls:
+        msg = bytearray(block_to_str(t))
+        msg[4 + NONCE_SIZE - 1] = 0
+        found = None
+        c, idx = ctr_start, [0] * 9  # the counter's base-62 digits, most significant first
+        for i in range(8, -1, -1):
+            c, idx[i] = divmod(c, 62)
+        digits = bytearray(abc[k] for k in idx)
+        for ctr in range(ctr_start, ctr_start + ctr_count):
+            if ctr != ctr_start:  # + 1 with carry
+                i = 8
+                while idx[i] == 61:
+                    idx[i], digits[i] = 0, abc[0]
+                    i -= 1
+                idx[i] += 1
+                digits[i] = abc[idx[i]]
+            msg[4:13] = digits
+            digest = hashlib.sha256(msg).digest()
+            if int.from_bytes(digest, "big") < limit:
+                found = ctr
+                break
+        if found is None:
+            results.append((None, None))
+            continue
+        b = Block()
+        ctypes.memmove(ctypes.addressof(b), ctypes.addressof(t), ctypes.sizeof(Block))  # padding included
+        set_field(b, "nonce", bytes(digits) + b"\0")
+        ctypes.memmove(ctypes.addressof(b) + Block.block_hash.offset, digest.hex().encode() + b"\0", 65)
+        results.append((b, found))
+    return results

@@ -420,6 +420,11 @@ void pow_destroy(pow_ctx* ctx) {
   (void)hipFree(ctx->d_chain);
   (void)hipFree(ctx->d_cslot);
   if (ctx->h_chain) (void)hipHostFree(ctx->h_chain);
+  (void)hipFree(ctx->d_batch);
+  (void)hipFree(ctx->d_brec);
+  (void)hipFree(ctx->d_bslot);
+  if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
+  if (ctx->h_brec) (void)hipHostFree(ctx->h_brec);
   if (ctx->h_res) (void)hipHostFree(ctx->h_res);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -940,6 +945,145 @@ int pow_mine_chain(pow_ctx* ctx, const pow_block* parent, size_t n, unsigned dif
     H->parent = H->blk[0];         // the tip: the next batch's parent
   }
   return finish(1);
+}
+
+namespace {
+
+// The buffers of pow_mine_batch's fused path, made at the first call that
+// needs them and sized for the largest tile: 12.7 MB of device memory (9.3 MB
+// control words and structs, 0.8 MB records, 2.6 MB slots) however many
+// templates a call has, and 10.1 MB of pinned host memory.
+int ensure_batch(pow_ctx* ctx) {
+  const size_t tile_bytes = (size_t)POW_BATCH_MAX_TILE * (sizeof(PowBatchCtl) + sizeof(pow_block));
+  const size_t rec_bytes = (size_t)POW_BATCH_MAX_TILE * sizeof(PowBatchRec);
+  if (!ctx->d_batch) HIP_OK(hipMalloc(&ctx->d_batch, tile_bytes));
+  if (!ctx->h_batch) HIP_OK(hipHostMalloc(&ctx->h_batch, tile_bytes, hipHostMallocDefault));
+  if (!ctx->d_brec) HIP_OK(hipMalloc(&ctx->d_brec, rec_bytes));
+  if (!ctx->h_brec) HIP_OK(hipHostMalloc(&ctx->h_brec, rec_bytes, hipHostMallocDefault));
+  if (!ctx->d_bslot) HIP_OK(hipMalloc(&ctx->d_bslot, (size_t)POW_BATCH_MAX_WG * sizeof(PowChainSlot)));
+  return POW_OK;
+}
+
+}  // namespace
+
+// K5, one launch per tile of templates; n == 1 is pow_mine, and above
+// ctx->batch_fused_max the same templates one by one through pow_mine.
+int pow_mine_batch(pow_ctx* ctx, const pow_block* tmpls, size_t n, unsigned diff_bits, uint64_t ctr_start,
+                   uint64_t ctr_count, const volatile uint32_t* cancel_word, uint32_t epoch, pow_block* out,
+                   uint64_t* found_ctr, size_t* n_solved, uint64_t* hashes_done) {
+  if (diff_bits > 256) return fail(POW_EINVAL, "diff_bits %u > 256", diff_bits);
+  if (ctr_count == 0 || ctr_count > (1ull << 32))
+    return fail(POW_EINVAL, "ctr_count %llu not in 1..2^32", (unsigned long long)ctr_count);
+  if (ctr_start >= POW_COUNTER_LIMIT || ctr_count > POW_COUNTER_LIMIT - ctr_start)
+    return fail(POW_EINVAL, "counter range past 62^9");
+  if (n > (1u << 24)) return fail(POW_EINVAL, "batch too large (%zu templates > 2^24)", n);
+  if (!ctx || ((!tmpls || !out) && n)) return fail(POW_EINVAL, "null");
+  if (ctx->board) return fail(POW_EINVAL, "pow_mine_batch does not run on a context bound to a stop board");
+  ctx->stats = pow_stats{};
+  if (n_solved) *n_solved = 0;
+  if (hashes_done) *hashes_done = 0;
+  if (found_ctr) std::fill(found_ctr, found_ctr + n, UINT64_MAX);
+  if (n == 0) return 1;
+  if (int rc = set_dev(ctx)) return rc;
+  pow_stats total{};
+  size_t solved = 0;
+  auto finish = [&](int rc) {
+    ctx->stats = total;
+    if (n_solved) *n_solved = solved;
+    if (hashes_done) *hashes_done = total.hashes;
+    return rc;
+  };
+  if (n == 1 || diff_bits > 32 || (int)diff_bits > ctx->batch_fused_max) {
+    for (size_t i = 0; i < n && !cancel_moved(cancel_word, epoch); ++i) {
+      uint64_t ctr = UINT64_MAX;
+      const int rc = mine_impl(ctx, &tmpls[i], ctr_start, ctr_count, diff_bits, cancel_word, epoch, &out[i], &ctr, nullptr,
+                               false);
+      total.kernel_ms += ctx->stats.kernel_ms;
+      total.launches += ctx->stats.launches;
+      total.hashes += ctx->stats.hashes;
+      if (rc < 0) return finish(rc);
+      if (rc == 1) {
+        if (found_ctr) found_ctr[i] = ctr;
+        ++solved;
+      }
+    }
+    return finish(solved == n ? 1 : 0);
+  }
+  if (cancel_moved(cancel_word, epoch)) return finish(0);
+  if (int rc = ensure_batch(ctx)) return rc;
+  PowBatchLaunch L;
+  {
+    PowLaunchLat digits;
+    make_launch_lat(ctr_start, ctr_count, diff_bits, &digits);
+    memset(&L, 0, sizeof L);
+    memcpy(L.base_digit, digits.base_digit, sizeof L.base_digit);
+    L.thr = digits.thr;
+    L.count = ctr_count;
+  }
+  // Templates per launch: about 2^26 expected trials (a handful of ms: the
+  // cancel latency), a grid of at most 2^16 workgroups, and windows of at most
+  // 2^38 counters in all, which keeps the watchdog's 2 ns per counter a bound
+  // worth having (550 s, K4's own worst case).
+  size_t tile = ctx->batch_tile ? ctx->batch_tile : (size_t)((1ull << 26) / std::min<uint64_t>(1ull << std::min(diff_bits, 26u), ctr_count));
+  tile = std::min<size_t>(tile, (size_t)((1ull << 38) / ctr_count));
+  tile = std::max<size_t>(1, std::min<size_t>(tile, POW_BATCH_MAX_TILE));
+  {
+    // Lanes for 2^lanes_log2 times the expected 2^d trials of a template: no
+    // more than the window has counters or the chip takes at one wave per SIMD.
+    // Four times, as K4, while the launch leaves CUs idle (a template then costs
+    // one trial's latency but for 1 in e^4); every lane computes at least one
+    // trial, so once the launch's workgroups exceed one per CU the surplus
+    // lanes are only surplus work: twice, then once the expected trials
+    // (d = 13, 64 templates: 8.8 us per template at four times, 4.1 at once).
+    const uint64_t cus = (uint64_t)std::max(1, ctx->cu_count);
+    const auto nwg_for = [&](unsigned lanes_log2) {
+      const uint64_t lanes = std::min<uint64_t>(1ull << (diff_bits + lanes_log2), ctr_count);
+      return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((lanes + 255) / 256, cus));
+    };
+    unsigned lanes_log2 = ctx->batch_lanes_log2 < 0 ? 2u : (unsigned)ctx->batch_lanes_log2;
+    if (ctx->batch_lanes_log2 < 0)
+      while (lanes_log2 > 0 && std::min(tile, n) * nwg_for(lanes_log2) > cus) --lanes_log2;
+    L.nwg_t = nwg_for(lanes_log2);
+  }
+  tile = std::max<size_t>(1, std::min<size_t>(tile, POW_BATCH_MAX_WG / L.nwg_t));
+  for (size_t t0 = 0; t0 < n; t0 += tile) {
+    if (cancel_moved(cancel_word, epoch)) return finish(0);
+    const size_t tn = std::min(tile, n - t0);
+    // The tile as it goes up: tn control words, then the tn raw structs.
+    const size_t ctl_bytes = tn * sizeof(PowBatchCtl);
+    PowBatchCtl* const hctl = (PowBatchCtl*)ctx->h_batch;
+    for (size_t i = 0; i < tn; ++i) hctl[i] = PowBatchCtl{~0ull, 0ull};
+    memcpy(ctx->h_batch + ctl_bytes, tmpls + t0, tn * sizeof(pow_block));
+    HIP_OK(hipMemcpyAsync(ctx->d_batch, ctx->h_batch, ctl_bytes + tn * sizeof(pow_block), hipMemcpyHostToDevice,
+                          ctx->stream));
+    if (pow_hooks)
+      if (int rc = pow_hooks->before_launch(ctx)) return rc;
+    HIP_OK(hipEventRecord(ctx->ev0, ctx->stream));
+    HIP_OK(pow_launch_batch(ctx->stream, L, (uint32_t)tn, (const uint32_t*)(ctx->d_batch + ctl_bytes),
+                            (PowBatchCtl*)ctx->d_batch, ctx->d_bslot, ctx->d_brec));
+    HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_OK(hipMemcpyAsync(ctx->h_brec, ctx->d_brec, tn * sizeof(PowBatchRec), hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = stream_wait_for(ctx, "batch mining tile", 2ull * tn * ctr_count)) return rc;  // 2 ns per counter
+    float ms = 0;
+    HIP_OK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    total.kernel_ms += ms;
+    total.launches += 1;
+    for (size_t i = 0; i < tn; ++i) {
+      const PowBatchRec& r = ctx->h_brec[i];
+      total.hashes += r.trials;
+      if (r.rel == ~0ull) continue;
+      if (r.rel >= ctr_count) return fail(POW_EHIP, "batch mining tile: template %zu reports counter %llu outside its window", t0 + i, (unsigned long long)r.rel);
+      pow_block* const o = &out[t0 + i];
+      if (o != &tmpls[t0 + i]) memcpy(o, &tmpls[t0 + i], sizeof *o);  // whole: padding included
+      pow_nonce_from_counter(ctr_start + r.rel, o->nonce);
+      char hx[65];
+      digest_out(r.digest, nullptr, hx);
+      memcpy(o->block_hash, hx, 65);  // strcpy semantics (node.cpp:318)
+      if (found_ctr) found_ctr[t0 + i] = ctr_start + r.rel;
+      ++solved;
+    }
+  }
+  return finish(solved == n ? 1 : 0);
 }
 
 int pow_cancel(pow_ctx* ctx, uint32_t epoch) {

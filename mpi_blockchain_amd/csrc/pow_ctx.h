@@ -62,6 +62,33 @@ struct PowChainLaunch {
   uint64_t created_at;     // the template's created_at
 };
 
+// K5 (pow_batch_kernel, pow_batch.hip), one launch per tile of pow_mine_batch's templates.
+#define POW_BATCH_MAX_TILE (1u << 14)  // templates per launch
+#define POW_BATCH_MAX_WG (1u << 16)    // workgroups per launch
+// pow_mine_batch: above it the host loop over pow_mine.  The largest measured d
+// at which the fused call beat the C loop at n = 64 by more than the two
+// interquartile ranges combined (profiles/mine_batch/README.md); -1 = nowhere.
+#define POW_BATCH_FUSED_MAX_D 23
+// Control words of one template of a tile: reset by the host before the launch.
+struct PowBatchCtl {
+  unsigned long long min_rel;  // lowest solving (counter - ctr_start) of the template (atomic min); ~0 = none
+  unsigned long long exits;    // the template's workgroups that have left (low 24 bits), their trials above
+};
+// One template's result, written by the last of its workgroups to leave.
+struct PowBatchRec {
+  unsigned long long rel;  // lowest solving (counter - ctr_start); ~0 = the window holds none
+  unsigned int digest[8];  // its digest
+  unsigned long long trials;
+};
+// The arguments of a launch: the tile's templates share window and difficulty.
+struct PowBatchLaunch {
+  uint32_t base_digit[9];  // base-62 digits of ctr_start (nonce[0..8])
+  uint32_t thr;            // a digest solves iff H0 <= thr (d <= 32)
+  uint32_t nwg_t;          // workgroups per template; gridDim.x = nwg_t x the tile's templates
+  uint32_t pad;
+  uint64_t count;          // counters [ctr_start, ctr_start + count), count <= 2^32
+};
+
 struct pow_ctx {
   int device = 0;
   int cu_count = 0;
@@ -114,6 +141,11 @@ struct pow_ctx {
   PowChainBuf* h_chain = nullptr;    // ... its pinned twin ...
   PowChainSlot* d_cslot = nullptr;   // ... and one slot per workgroup of a launch
   unsigned chain_grid_max = 0;       // slots allocated = the largest grid of a K4 launch
+  uint8_t* d_batch = nullptr;        // pow_mine_batch: a tile's control words, then its raw structs ...
+  uint8_t* h_batch = nullptr;        // ... and the pinned twin they go up from in one copy
+  PowBatchRec* d_brec = nullptr;     // the tile's result records ...
+  PowBatchRec* h_brec = nullptr;     // ... and their pinned twin
+  PowChainSlot* d_bslot = nullptr;   // one slot per workgroup of a K5 launch (POW_BATCH_MAX_WG)
   unsigned grid_full = 0;  // workgroups that fill the chip (8 per CU)
   // Set only by the test library's hooks (pow_hooks.cpp, at pow_init):
   bool force_full = false;        // use the d > 32 kernel for every d
@@ -125,6 +157,9 @@ struct pow_ctx {
   unsigned chain_batch = 0;       // pow_mine_chain: blocks per batch (0 = the plan)
   unsigned chain_lanes_log2 = 2;  // K4's grid: lanes = 2^this x the expected 2^d trials
   int chain_fused_max = POW_CHAIN_FUSED_MAX_D;  // pow_mine_chain: highest d on the fused path (-1 = host loop only)
+  unsigned batch_tile = 0;        // pow_mine_batch: templates per launch (0 = the plan)
+  int batch_lanes_log2 = -1;      // K5's lanes per template = 2^this x the expected 2^d trials (-1 = the plan: 2 down to 0)
+  int batch_fused_max = POW_BATCH_FUSED_MAX_D;  // pow_mine_batch: highest d on the fused path (-1 = host loop only)
   // K1' and K2' launches as AQL packets (pow_aql.cpp) instead of
   // hipLaunchKernel: test library only, opt-in there; null = the HIP launch
   // path, the only one the shipped library has.
@@ -151,6 +186,8 @@ hipError_t pow_launch_verify(uint32_t n_check, uint32_t n_avail, unsigned diff, 
                              const uint32_t* blocks, uint8_t* status, PowVerifyRes* res);
 hipError_t pow_launch_chain(hipStream_t stream, const PowChainLaunch& L, const uint32_t* prev, uint32_t* dst,
                             PowChainCtl* ctl, PowChainSlot* slots);
+hipError_t pow_launch_batch(hipStream_t stream, const PowBatchLaunch& L, uint32_t n_tmpl, const uint32_t* tmpls,
+                            PowBatchCtl* ctl, PowChainSlot* slots, PowBatchRec* rec);
 hipError_t pow_sort_u32(void* temp, size_t* temp_bytes, uint32_t* keys, uint32_t* alt, uint32_t n,
                         uint32_t** sorted, hipStream_t stream);
 hipError_t pow_launch_search_lat(bool full, bool any, bool asm_groups, unsigned grid, hipStream_t stream,

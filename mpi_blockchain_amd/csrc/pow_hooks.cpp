@@ -34,6 +34,11 @@ void configure(pow_ctx* ctx) {
   if (const char* cf = getenv("POW_CHAIN_FUSED_MAX")) ctx->chain_fused_max = (int)std::max(-1l, std::min(32l, strtol(cf, nullptr, 0)));
   // K4's grid: lanes = 2^n times the expected trials (the result must not depend on it)
   if (const char* cl = getenv("POW_CHAIN_LANES_LOG2")) ctx->chain_lanes_log2 = (unsigned)std::min(8ul, strtoul(cl, nullptr, 0));
+  // pow_mine_batch: the highest d on the fused path (-1: the host loop at every d), templates per
+  // launch (the workgroup and window caps still hold) and K5's lanes per template (as K4's; unset: the plan)
+  if (const char* bf = getenv("POW_BATCH_FUSED_MAX")) ctx->batch_fused_max = (int)std::max(-1l, std::min(32l, strtol(bf, nullptr, 0)));
+  if (const char* bt = getenv("POW_BATCH_TILE")) ctx->batch_tile = (unsigned)std::min((unsigned long)POW_BATCH_MAX_TILE, strtoul(bt, nullptr, 0));
+  if (const char* bl = getenv("POW_BATCH_LANES_LOG2")) ctx->batch_lanes_log2 = (int)std::min(8ul, strtoul(bl, nullptr, 0));
   if (const char* g = getenv("POW_GRID_PER_CU")) {  // launch-geometry experiments
     const int per = atoi(g);
     if (per > 0 && per <= 64) ctx->grid_full = (unsigned)ctx->cu_count * (unsigned)per;

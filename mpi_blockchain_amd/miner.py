@@ -41,6 +41,16 @@ class MineChainResult:
     kernel_ms: float      # GPU time of the call
 
 
+@dataclass
+class MineBatchResult:
+    blocks: list          # per template: the sealed Block, or None where unsolved or unreached
+    counters: list        # per template: the lowest solving counter, or None
+    n_solved: int         # templates solved
+    complete: bool        # all were solved (pow_mine_batch returned 1)
+    hashes: int           # trials issued
+    kernel_ms: float      # GPU time of the call
+
+
 def refresh_template(last: Block, rank: int, difficulty: int = DEFAULT_DIFFICULTY,
                      now: int | None = None) -> Block:
     """node.cpp:292-299: copy the last block, index+1, owner = rank,
@@ -208,6 +218,35 @@ class GpuMiner:
             ctypes.memmove(blocks, ctypes.byref(out, (n - m) * ctypes.sizeof(Block)), m * ctypes.sizeof(Block))
         return MineChainResult(blocks, m, rc == 1, hashes.value, self.stats()["kernel_ms"])
 
+    def mine_batch(self, tmpls, difficulty: int = DEFAULT_DIFFICULTY, ctr_start: int = 0, ctr_count: int = 1 << 32,
+                   epoch: int | None = None) -> MineBatchResult:
+        """pow_mine_batch: every template of `tmpls` (a sequence of Blocks or a
+        ctypes ``Block`` array) mined on its own over the same window, each the
+        lowest solving counter, in one call.  ``blocks[i]`` is the sealed block
+        of template i, or None where its window held no solution or
+        :meth:`cancel` was called before it was reached.  The host statement of
+        the result is :func:`mpi_blockchain_amd.block.mine_batch`."""
+        n = len(tmpls)
+        arr = (Block * max(n, 1))()
+        for i, t in enumerate(tmpls):
+            ctypes.memmove(ctypes.byref(arr, i * ctypes.sizeof(Block)), ctypes.addressof(t), ctypes.sizeof(Block))
+        out = (Block * max(n, 1))()
+        ctrs = (ctypes.c_uint64 * max(n, 1))()
+        solved, hashes = ctypes.c_size_t(), ctypes.c_uint64()
+        ep = self._cancel.value if epoch is None else epoch
+        rc = check(self.L.pow_mine_batch(self.ctx, arr, n, difficulty, ctr_start, ctr_count, ctypes.byref(self._cancel),
+                                         ep, out, ctrs, ctypes.byref(solved), ctypes.byref(hashes)), self.L)
+        blocks, counters = [], []
+        for i in range(n):
+            hit = ctrs[i] != 0xFFFFFFFFFFFFFFFF
+            b = None
+            if hit:
+                b = Block()
+                ctypes.memmove(ctypes.addressof(b), ctypes.byref(out, i * ctypes.sizeof(Block)), ctypes.sizeof(Block))
+            blocks.append(b)
+            counters.append(ctrs[i] if hit else None)
+        return MineBatchResult(blocks, counters, solved.value, rc == 1, hashes.value, self.stats()["kernel_ms"])
+
     def sweep(self, tmpl: Block, start: int, count: int, difficulty: int, cap: int | None = None) -> np.ndarray:
         """Ascending (counter - start) of every solving counter (count <= 2^32)."""
         if cap is None:  # pow_sweep sorts on the device: at most 2^31 - 1 entries
@@ -299,5 +338,5 @@ def block_hex(b: Block) -> str:
     return field(b, "block_hash").split(b"\0", 1)[0].decode()
 
 
-__all__ = ["GpuMiner", "DeviceBuffer", "StopBoard", "MineResult", "MineChainResult", "VerifyResult", "refresh_template", "proof_of_work_round", "block_hex",
+__all__ = ["GpuMiner", "DeviceBuffer", "StopBoard", "MineResult", "MineChainResult", "MineBatchResult", "VerifyResult", "refresh_template", "proof_of_work_round", "block_hex",
            "nonce_from_counter"]
