@@ -308,6 +308,88 @@ int pow_mine_batch(pow_ctx* ctx, const pow_block* tmpls, size_t n, unsigned diff
                    pow_block* out /* n */, uint64_t* found_ctr /* n, may be NULL */,
                    size_t* n_solved /* may be NULL */, uint64_t* hashes_done /* may be NULL */);
 
+/* Run the reference's race in one call: n_rivals miners each refresh their own
+ * template on the current tip (node.cpp:292-302), the first to solve wins the
+ * height, and its block is the tip of the next.  n heights on top of *parent.
+ * Templates.  With `last` = *parent for height k = 0, else the winning block of
+ * height k - 1, rival r's template at height k is `last` refreshed exactly as
+ * pow_mine_chain does it: copied whole (all 552 bytes, padding included), index
+ * = last.index + 1 (uint32_t wrap), node_owner_number = owners[r], difficulty =
+ * diff_bits, created_at = created_at[k * n_rivals + r] (height-major;
+ * created_at NULL: time(NULL), read once at entry, for every rival and height)
+ * and previous_block_hash = all 256 bytes of last.block_hash (trap T5).
+ * Winner.  Let c_r be what pow_mine gives rival r on its template over
+ * [ctr_start, ctr_start + ctr_count): its LOWEST solving counter.  The winner
+ * of the height is the rival with the lowest (c_r, r): the fewest trials, ties
+ * in the counter to the lowest POSITION in owners[] (not the lowest owner
+ * number).  Ties are real: only the low byte of node_owner_number and of
+ * created_at is hashed, so owners 5 and 261 with equal created_at have
+ * identical digests at every counter.
+ * Outputs, tip first as pow_mine_chain's: the winner's sealed block goes to
+ * out[n - 1 - k], with the bytes pow_mine gives on the winning template (nonce
+ * = the 9 base-62 characters + NUL of c_r, block_hash = 64 hex + NUL, bytes
+ * 65..255 of block_hash the template's, node.cpp:318); winners[n - 1 - k] (may
+ * be NULL) = the winner's position r; found_ctr[n - 1 - k] (may be NULL) = its
+ * absolute counter c_r.  After the call out + (n - *n_mined) is a tip-first
+ * chain of *n_mined blocks whose oldest block is a child of *parent.
+ * Returns 1 if all n heights were mined; 0 if it stopped early, because at some
+ * height no rival's window held a solution or because the cancel word
+ * (optional; read at entry and between batches) differs from `epoch`; *n_mined
+ * (may be NULL) then says how far it got, as pow_mine_chain sets it, and the
+ * entries of out, winners and found_ctr below that are not touched.  n = 0
+ * returns 1.
+ * POW_EINVAL, checked in this order before the context is touched and with
+ * nothing written: diff_bits > 256; ctr_count == 0 or > 2^32; ctr_start +
+ * ctr_count > 62^9; n > 2^24; n_rivals == 0 or > POW_RACE_MAX_RIVALS; a null
+ * ctx, or a null parent, out or owners with n > 0; a context bound to a stop
+ * board (boards and pow_cancel's in-flight path are not part of this call).
+ * Paths (all give the same bytes).  n_rivals == 1 is pow_mine_chain itself.
+ * Above d = POW_RACE_FUSED_MAX_D (csrc/pow_ctx.h; never above 32) the call runs
+ * the host loop: per height it walks the rivals in position order, refresh and
+ * then pow_mine with the same cancel word; every rival after the first hit
+ * searches only [ctr_start, best counter so far), since a later position loses
+ * a tie, and an empty remainder is skipped.  Otherwise the heights run fused:
+ * ONE launch per height whose grid holds every rival (256 lanes per workgroup;
+ * lanes for four times the expected 2^d trials split evenly over the rivals,
+ * each rival at least one workgroup and at most its share of one per CU, so
+ * the grid is at most max(n_rivals, CUs) workgroups).  All rivals of a launch
+ * share one minimum of (counter, position), and a lane stops once its next pair
+ * lies above it: a height costs about the trials of ONE solo block, not
+ * n_rivals times that, and every pair below the answer is always tested.
+ * Launches are queued in batches as pow_mine_chain's, about 2^26 expected
+ * trials and at most 64 launches, the largest batch for which batch x n_rivals
+ * x ctr_count stays at or below 2^38 (never below one height); per batch one
+ * copy up of the parent, one of the owners and created_at, one copy back and
+ * one bounded wait: 10 s + 2 ns per (counter, rival) pair of the batch, which
+ * is 560 s at worst for a batch of several heights and 2,209 s for the one
+ * height of 256 rivals over a 2^32 window.  A caller who wants a tighter bound
+ * passes a window near what it needs, e.g. 2^(d + 7) counters.
+ * Device memory: about 180 KB, made at the first fused call.
+ * *hashes_done (may be NULL) = trials issued.  pow_get_stats: launches (fused:
+ * one per height), kernel_ms (fused: events around each batch) and hashes.
+ * pow_warmup does not launch this call's kernel (nor pow_verify_chain's,
+ * pow_mine_chain's or pow_mine_batch's): the first fused call of a process
+ * also loads its code object and makes the buffers.
+ * Cost (MI355X, profiles/mine_race/README.md; medians of 9 calls of 8 heights,
+ * per height, window 2^(d + 7)): fused, 3 and 64 rivals: 36 and 36 us at d = 9,
+ * 40 and 40 at d = 13, 46 and 58 at d = 17, 133 and 135 at d = 19, 320 and 353
+ * at d = 21, 1,100 and 2,237 at d = 23 (that race needed twice the pairs).  From
+ * d = 19 the trials are within 13% of the (counter, rival) pairs the race needs;
+ * at d <= 13 a height is one launch boundary and costs no less than 36 us.  The
+ * host loop measured 74 us to 7.1 ms with 3 rivals and 1.3 to 103 ms with 64
+ * (one launch per rival): it is slower than the loop of examples/mine_race.c
+ * around pow_mine_batch at d <= 13 and at d = 23, faster only between.  The
+ * fused path won at every measured d; nothing above d = 23 was measured. */
+#define POW_RACE_MAX_RIVALS 256
+int pow_mine_race(pow_ctx* ctx, const pow_block* parent, size_t n, unsigned diff_bits,
+                  const uint32_t* owners, size_t n_rivals,
+                  const uint64_t* created_at /* n * n_rivals, height-major, or NULL */,
+                  uint64_t ctr_start, uint64_t ctr_count,
+                  const volatile uint32_t* cancel_word, uint32_t epoch,
+                  pow_block* out /* n, tip first */,
+                  uint32_t* winners /* n, may be NULL */, uint64_t* found_ctr /* n, may be NULL */,
+                  size_t* n_mined, uint64_t* hashes_done);
+
 /* In-flight cancellation (the reference re-checks its chain only after a
  * trial, node.cpp:315).  Publishes `epoch`, the caller's current value of the
  * cancel word, to the GPU: a pow_mine / pow_mine_any launch of this ctx whose

@@ -241,3 +241,74 @@ def mine_batch(tmpls, difficulty: int = DEFAULT_DIFFICULTY, ctr_start: int = 0,
         ctypes.memmove(ctypes.addressof(b) + Block.block_hash.offset, digest.hex().encode() + b"\0", 65)
         results.append((b, found))
     return results
+
+
+def mine_race(parent: Block, n: int, difficulty: int = DEFAULT_DIFFICULTY, owners=(0,), created_at=None,
+              ctr_start: int = 0, ctr_count: int = 1 << 32) -> tuple[list[Block], list[int], list[int]]:
+    """What ``pow_mine_race`` produces, stated on the host with hashlib:
+    ``(blocks, winners, counters)`` of a race of ``len(owners)`` rival miners
+    over `n` heights on top of `parent`, all three tip first (entry ``i + 1``
+    is the height below entry ``i``).
+
+    At every height rival r's template is the block before it (`parent`, then
+    the winner of the height below) copied whole (node.cpp:292-299), then
+    ``index + 1`` in 32 bits, ``owners[r]``, `difficulty`,
+    ``created_at[k * len(owners) + r]`` for height k in mining order (one
+    ``time.time()`` for every rival and height if `created_at` is None) and all
+    256 bytes of the parent's ``block_hash`` as ``previous_block_hash``.  The
+    pairs (counter, r) are tried in ascending order over ``[ctr_start, ctr_start
+    + ctr_count)``: the first whose digest has `difficulty` leading zero bits
+    wins the height, so the winner needed the fewest trials and a tie in the
+    counter goes to the lowest position in `owners`.  Its block is sealed with
+    its nonce and the digest's hex + NUL over the first 65 bytes of
+    ``block_hash`` (node.cpp:318).  The race stops at the first height at which
+    no rival's window holds a solution, so the result may be shorter than `n`."""
+    if not 0 <= difficulty <= 256:
+        raise ValueError(f"difficulty {difficulty} not in 0..256")
+    if ctr_start < 0 or ctr_count < 0 or ctr_start + ctr_count > 62 ** 9:
+        raise ValueError("counter range past 62^9")
+    R = len(owners)
+    if not 1 <= R <= 256:
+        raise ValueError(f"{R} rivals not in 1..256")
+    if created_at is None:
+        created_at = [int(time.time())] * (n * R)
+    if len(created_at) != n * R:
+        raise ValueError(f"created_at has {len(created_at)} entries for {n} heights of {R} rivals")
+    limit = 1 << (256 - difficulty)  # a digest solves iff it is below
+    blocks: list[Block] = []
+    winners: list[int] = []
+    counters: list[int] = []
+    last = parent
+    for k in range(n):
+        tmpls, msgs = [], []
+        for r in range(R):
+            b = Block()
+            ctypes.memmove(ctypes.addressof(b), ctypes.addressof(last), ctypes.sizeof(Block))  # padding included
+            b.index = (last.index + 1) & 0xFFFFFFFF
+            b.node_owner_number = owners[r] & 0xFFFFFFFF
+            b.difficulty = difficulty & 0xFFFFFFFF
+            b.created_at = created_at[k * R + r] & 0xFFFFFFFFFFFFFFFF
+            set_field(b, "previous_block_hash", field(last, "block_hash"))
+            tmpls.append(b)
+            msgs.append(bytearray(block_to_str(b)))
+        won = None
+        for ctr in range(ctr_start, ctr_start + ctr_count):
+            nonce = nonce_from_counter(ctr)
+            for r in range(R):
+                msgs[r][4:4 + NONCE_SIZE] = nonce
+                digest = hashlib.sha256(msgs[r]).digest()
+                if int.from_bytes(digest, "big") < limit:
+                    won = r
+                    break
+            if won is not None:
+                break
+        if won is None:
+            break
+        b = tmpls[won]
+        set_field(b, "nonce", nonce)
+        ctypes.memmove(ctypes.addressof(b) + Block.block_hash.offset, digest.hex().encode() + b"\0", 65)
+        blocks.insert(0, b)
+        winners.insert(0, won)
+        counters.insert(0, ctr)
+        last = b
+    return blocks, winners, counters

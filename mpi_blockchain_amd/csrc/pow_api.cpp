@@ -425,6 +425,11 @@ void pow_destroy(pow_ctx* ctx) {
   (void)hipFree(ctx->d_bslot);
   if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
   if (ctx->h_brec) (void)hipHostFree(ctx->h_brec);
+  (void)hipFree(ctx->d_race);
+  (void)hipFree(ctx->d_rin);
+  (void)hipFree(ctx->d_rslot);
+  if (ctx->h_race) (void)hipHostFree(ctx->h_race);
+  if (ctx->h_rin) (void)hipHostFree(ctx->h_rin);
   if (ctx->h_res) (void)hipHostFree(ctx->h_res);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -1084,6 +1089,193 @@ int pow_mine_batch(pow_ctx* ctx, const pow_block* tmpls, size_t n, unsigned diff
     }
   }
   return finish(solved == n ? 1 : 0);
+}
+
+namespace {
+
+static_assert(offsetof(PowRaceBuf, ctl) == sizeof(pow_block) &&
+                  offsetof(PowRaceBuf, rec) == offsetof(PowRaceBuf, ctl) + sizeof(PowRaceCtl) &&
+                  offsetof(PowRaceBuf, blk) == offsetof(PowRaceBuf, rec) + sizeof(PowRaceRec) * POW_RACE_MAX_BATCH,
+              "parent + ctl go up; ctl, records and blocks come down: one copy each");
+
+// The buffers of pow_mine_race's fused path, made at the first call that needs
+// them: about 180 KB of device memory (170 KB of it pinned too), one slot per workgroup.
+int ensure_race(pow_ctx* ctx) {
+  if (!ctx->d_race) HIP_OK(hipMalloc(&ctx->d_race, sizeof(PowRaceBuf)));
+  if (!ctx->h_race) HIP_OK(hipHostMalloc(&ctx->h_race, sizeof(PowRaceBuf), hipHostMallocDefault));
+  if (!ctx->d_rin) HIP_OK(hipMalloc(&ctx->d_rin, sizeof(PowRaceIn)));
+  if (!ctx->h_rin) HIP_OK(hipHostMalloc(&ctx->h_rin, sizeof(PowRaceIn), hipHostMallocDefault));
+  if (!ctx->d_rslot) {
+    // The plan's largest grid: one workgroup per rival, or per CU (pow_race_plan).
+    const unsigned cap = (unsigned)std::max(POW_RACE_MAX_RIVALS, ctx->cu_count);
+    HIP_OK(hipMalloc(&ctx->d_rslot, (size_t)cap * sizeof(PowChainSlot)));
+    ctx->race_grid_max = cap;
+  }
+  return POW_OK;
+}
+
+// The counter of a nonce pow_nonce_from_counter made (block.cpp:61-72's alphabet).
+uint64_t counter_of_nonce(const char* nonce) {
+  uint64_t c = 0;
+  for (int i = 0; i < 9; ++i) {
+    const char ch = nonce[i];
+    c = c * 62 + (uint64_t)(ch >= 'a' ? ch - 'a' : ch >= 'A' ? ch - 'A' + 26 : ch - '0' + 52);
+  }
+  return c;
+}
+
+}  // namespace
+
+// K6, one launch per height, in batches queued without a host wait; one rival
+// is pow_mine_chain, and above ctx->race_fused_max the same heights through
+// refresh + pow_mine, rival by rival under the best counter so far.
+int pow_mine_race(pow_ctx* ctx, const pow_block* parent, size_t n, unsigned diff_bits, const uint32_t* owners,
+                  size_t n_rivals, const uint64_t* created_at, uint64_t ctr_start, uint64_t ctr_count,
+                  const volatile uint32_t* cancel_word, uint32_t epoch, pow_block* out, uint32_t* winners,
+                  uint64_t* found_ctr, size_t* n_mined, uint64_t* hashes_done) {
+  if (diff_bits > 256) return fail(POW_EINVAL, "diff_bits %u > 256", diff_bits);
+  if (ctr_count == 0 || ctr_count > (1ull << 32))
+    return fail(POW_EINVAL, "ctr_count %llu not in 1..2^32", (unsigned long long)ctr_count);
+  if (ctr_start >= POW_COUNTER_LIMIT || ctr_count > POW_COUNTER_LIMIT - ctr_start)
+    return fail(POW_EINVAL, "counter range past 62^9");
+  if (n > (1u << 24)) return fail(POW_EINVAL, "race too large (%zu heights > 2^24)", n);
+  if (n_rivals == 0 || n_rivals > POW_RACE_MAX_RIVALS)
+    return fail(POW_EINVAL, "n_rivals %zu not in 1..%d", n_rivals, POW_RACE_MAX_RIVALS);
+  if (!ctx || ((!parent || !out || !owners) && n)) return fail(POW_EINVAL, "null");
+  if (ctx->board) return fail(POW_EINVAL, "pow_mine_race does not run on a context bound to a stop board");
+  const size_t R = n_rivals;
+  if (R == 1) {
+    size_t m = 0;
+    const int rc = pow_mine_chain(ctx, parent, n, diff_bits, n ? owners[0] : 0u, created_at, ctr_start, ctr_count,
+                                  cancel_word, epoch, out, &m, hashes_done);
+    if (rc < 0) return rc;
+    if (n_mined) *n_mined = m;
+    for (size_t k = 0; k < m; ++k) {
+      if (winners) winners[n - 1 - k] = 0u;
+      if (found_ctr) found_ctr[n - 1 - k] = counter_of_nonce(out[n - 1 - k].nonce);
+    }
+    return rc;
+  }
+  ctx->stats = pow_stats{};
+  if (n_mined) *n_mined = 0;
+  if (hashes_done) *hashes_done = 0;
+  if (n == 0) return 1;
+  if (int rc = set_dev(ctx)) return rc;
+  const uint64_t now = created_at ? 0 : (uint64_t)time(nullptr);
+  pow_stats total{};
+  size_t done = 0;
+  auto finish = [&](int rc) {
+    ctx->stats = total;
+    if (n_mined) *n_mined = done;
+    if (hashes_done) *hashes_done = total.hashes;
+    return rc;
+  };
+  if (diff_bits > 32 || (int)diff_bits > ctx->race_fused_max) {
+    pow_block last = *parent;
+    while (done < n && !cancel_moved(cancel_word, epoch)) {
+      pow_block best;
+      uint64_t best_ctr = UINT64_MAX;
+      uint32_t best_r = 0;
+      bool cancelled = false;
+      for (size_t r = 0; r < R; ++r) {
+        // A later position loses a tie: it searches only below the best counter so far.
+        const uint64_t window = best_ctr == UINT64_MAX ? ctr_count : best_ctr - ctr_start;
+        if (window == 0) break;  // ctr_start itself solved: nothing lies below it
+        pow_block tmpl, blk;
+        uint64_t ctr = UINT64_MAX;
+        refresh(&tmpl, &last, owners[r], diff_bits, created_at ? created_at[done * R + r] : now);
+        const int rc = mine_impl(ctx, &tmpl, ctr_start, window, diff_bits, cancel_word, epoch, &blk, &ctr, nullptr, false);
+        total.kernel_ms += ctx->stats.kernel_ms;
+        total.launches += ctx->stats.launches;
+        total.hashes += ctx->stats.hashes;
+        if (rc < 0) return finish(rc);
+        if (rc == 1) {
+          best = blk;
+          best_ctr = ctr;
+          best_r = (uint32_t)r;
+        } else if (cancel_moved(cancel_word, epoch)) {  // this rival's window was not searched to its end
+          cancelled = true;
+          break;
+        }
+      }
+      if (cancelled || best_ctr == UINT64_MAX) break;
+      out[n - 1 - done] = last = best;
+      if (winners) winners[n - 1 - done] = best_r;
+      if (found_ctr) found_ctr[n - 1 - done] = best_ctr;
+      ++done;
+    }
+    return finish(done == n ? 1 : 0);
+  }
+  if (cancel_moved(cancel_word, epoch)) return finish(0);
+  if (int rc = ensure_race(ctx)) return rc;
+  PowRacePlan plan;
+  pow_race_plan(diff_bits, (uint32_t)R, ctr_count, (uint32_t)std::max(1, ctx->cu_count), ctx->race_lanes_log2,
+                ctx->race_batch, &plan);
+  PowRaceLaunch L;
+  {
+    PowLaunchLat digits;
+    make_launch_lat(ctr_start, ctr_count, diff_bits, &digits);
+    memset(&L, 0, sizeof L);
+    memcpy(L.base_digit, digits.base_digit, sizeof L.base_digit);
+    L.thr = digits.thr;
+    L.diff = diff_bits;
+    L.n_rivals = (uint32_t)R;
+    L.nwg_r = plan.nwg_r;
+    L.count = ctr_count;
+  }
+  if ((uint64_t)L.nwg_r * R > ctx->race_grid_max)
+    return fail(POW_EHIP, "race plan: %u workgroups for %u slots", (unsigned)(L.nwg_r * R), ctx->race_grid_max);
+  PowRaceBuf* const H = ctx->h_race;
+  PowRaceBuf* const D = ctx->d_race;
+  PowRaceIn* const HI = ctx->h_rin;
+  H->parent = *parent;
+  memcpy(HI->owner, owners, R * sizeof(uint32_t));
+  while (done < n) {
+    if (cancel_moved(cancel_word, epoch)) return finish(0);
+    const size_t nb = std::min<size_t>(plan.batch, n - done);
+    memset(&H->ctl, 0, sizeof H->ctl);
+    H->ctl.min_key = ~0ull;
+    for (size_t i = 0; i < nb * R; ++i) HI->created_at[i] = created_at ? created_at[done * R + i] : now;
+    HIP_OK(hipMemcpyAsync(D, H, offsetof(PowRaceBuf, rec), hipMemcpyHostToDevice, ctx->stream));
+    HIP_OK(hipMemcpyAsync(ctx->d_rin, HI, offsetof(PowRaceIn, created_at) + nb * R * sizeof(uint64_t),
+                          hipMemcpyHostToDevice, ctx->stream));
+    if (pow_hooks)
+      if (int rc = pow_hooks->before_launch(ctx)) return rc;
+    HIP_OK(hipEventRecord(ctx->ev0, ctx->stream));
+    for (size_t j = 0; j < nb; ++j) {
+      L.height = (uint32_t)j;
+      const pow_block* const prev = j == 0 ? &D->parent : &D->blk[nb - j];
+      HIP_OK(pow_launch_race(ctx->stream, L, (const uint32_t*)prev, (uint32_t*)&D->blk[nb - 1 - j], ctx->d_rin, &D->ctl,
+                             ctx->d_rslot, D->rec));
+    }
+    HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_OK(hipMemcpyAsync(&H->ctl, &D->ctl, offsetof(PowRaceBuf, blk) - offsetof(PowRaceBuf, ctl) + nb * sizeof(pow_block),
+                          hipMemcpyDeviceToHost, ctx->stream));
+    // 2 ns per (counter, rival) pair of the batch
+    if (int rc = stream_wait_for(ctx, "race mining batch", 2ull * nb * R * ctr_count)) return rc;
+    float ms = 0;
+    HIP_OK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    total.kernel_ms += ms;
+    total.launches += (uint32_t)nb;
+    total.hashes += H->ctl.hashes;
+    const size_t m = H->ctl.n_done;
+    if (m > nb || (m < nb && !H->ctl.stop)) return fail(POW_EHIP, "race mining batch: %zu of %zu heights and no stop word", m, nb);
+    for (size_t j = 0; j < m; ++j) {
+      const PowRaceRec& rec = H->rec[j];
+      if (rec.winner >= R || rec.rel >= ctr_count)
+        return fail(POW_EHIP, "race mining batch: height %zu reports rival %u at counter %llu", done + j, rec.winner,
+                    (unsigned long long)rec.rel);
+      if (winners) winners[n - 1 - done - j] = rec.winner;
+      if (found_ctr) found_ctr[n - 1 - done - j] = ctr_start + rec.rel;
+    }
+    // Height done + j is blk[nb - 1 - j] and goes to out[n - 1 - done - j]:
+    // the m sealed ones are the batch's upper m slots, contiguous in both.
+    if (m) memcpy(out + (n - done - m), &H->blk[nb - m], m * sizeof(pow_block));
+    done += m;
+    if (m < nb) return finish(0);  // a height nobody solved
+    H->parent = H->blk[0];         // the tip: the next batch's parent
+  }
+  return finish(1);
 }
 
 int pow_cancel(pow_ctx* ctx, uint32_t epoch) {

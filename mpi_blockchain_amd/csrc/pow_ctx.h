@@ -89,6 +89,55 @@ struct PowBatchLaunch {
   uint64_t count;          // counters [ctr_start, ctr_start + count), count <= 2^32
 };
 
+// K6 (pow_race_kernel, pow_race.hip), one launch per height of pow_mine_race.
+#define POW_RACE_MAX_BATCH 64       // launches queued without a host wait
+#define POW_RACE_MAX_WG (1u << 16)  // workgroups per launch: the exit word counts them in 16 bits
+// pow_mine_race: above it the host loop over pow_mine.  The largest measured d
+// at which the fused call beat the host loop at 3 and at 64 rivals by more than
+// the two interquartile ranges combined (profiles/mine_race/README.md); -1 = nowhere.
+#define POW_RACE_FUSED_MAX_D 23
+// Control words of a batch: reset by the host before the batch; min_key and
+// exits are reset again by each launch's sealing workgroup for the next one.
+struct PowRaceCtl {
+  unsigned long long min_key;  // lowest solving ((counter - ctr_start) << 8 | rival) of the running launch (atomic min); ~0 = none
+  unsigned long long hashes;   // trials computed, all launches of the batch (added by each launch's sealer)
+  unsigned long long exits;    // the running launch: workgroups that have left (low 16 bits), their trials above
+  unsigned int stop;           // a launch in which no rival's window held a solution: every later launch exits at once
+  unsigned int n_done;         // heights sealed by the batch
+};
+// One height's result, written by the launch's sealing workgroup.
+struct PowRaceRec {
+  unsigned long long rel;  // the winner's (counter - ctr_start)
+  unsigned int winner;     // its position in owners[]
+  unsigned int pad;
+};
+// A batch in device memory, and its pinned twin: parent and ctl go up in one
+// copy; ctl, the records and the sealed blocks come down in one.  Height j of
+// the batch is rec[j] and blk[nb - 1 - j] (tip first); its launch reads
+// blk[nb - j], the first parent.
+struct PowRaceBuf {
+  pow_block parent;
+  PowRaceCtl ctl;
+  PowRaceRec rec[POW_RACE_MAX_BATCH];
+  pow_block blk[POW_RACE_MAX_BATCH];
+};
+// What the rivals differ in, as it goes up once per batch: rival r of the
+// batch's height j has owner[r] and created_at[j * n_rivals + r].
+struct PowRaceIn {
+  uint32_t owner[POW_RACE_MAX_RIVALS];
+  uint64_t created_at[POW_RACE_MAX_BATCH * POW_RACE_MAX_RIVALS];
+};
+// The arguments of one launch.
+struct PowRaceLaunch {
+  uint32_t base_digit[9];  // base-62 digits of ctr_start (nonce[0..8])
+  uint32_t thr;            // a digest solves iff H0 <= thr (d <= 32)
+  uint32_t diff;           // the templates' difficulty
+  uint32_t n_rivals;       // 1..256
+  uint32_t nwg_r;          // workgroups per rival; gridDim.x = nwg_r x n_rivals
+  uint32_t height;         // of the batch: the row of PowRaceIn::created_at, and the record to write
+  uint64_t count;          // counters [ctr_start, ctr_start + count), count <= 2^32
+};
+
 struct pow_ctx {
   int device = 0;
   int cu_count = 0;
@@ -146,6 +195,12 @@ struct pow_ctx {
   PowBatchRec* d_brec = nullptr;     // the tile's result records ...
   PowBatchRec* h_brec = nullptr;     // ... and their pinned twin
   PowChainSlot* d_bslot = nullptr;   // one slot per workgroup of a K5 launch (POW_BATCH_MAX_WG)
+  PowRaceBuf* d_race = nullptr;      // pow_mine_race: a batch on the device ...
+  PowRaceBuf* h_race = nullptr;      // ... its pinned twin ...
+  PowRaceIn* d_rin = nullptr;        // ... the rivals' owners and created_at ...
+  PowRaceIn* h_rin = nullptr;        // ... and the pinned twin they go up from
+  PowChainSlot* d_rslot = nullptr;   // one slot per workgroup of a K6 launch ...
+  unsigned race_grid_max = 0;        // ... = max(POW_RACE_MAX_RIVALS, cu_count)
   unsigned grid_full = 0;  // workgroups that fill the chip (8 per CU)
   // Set only by the test library's hooks (pow_hooks.cpp, at pow_init):
   bool force_full = false;        // use the d > 32 kernel for every d
@@ -160,6 +215,9 @@ struct pow_ctx {
   unsigned batch_tile = 0;        // pow_mine_batch: templates per launch (0 = the plan)
   int batch_lanes_log2 = -1;      // K5's lanes per template = 2^this x the expected 2^d trials (-1 = the plan: 2 down to 0)
   int batch_fused_max = POW_BATCH_FUSED_MAX_D;  // pow_mine_batch: highest d on the fused path (-1 = host loop only)
+  unsigned race_batch = 0;        // pow_mine_race: heights per batch (0 = the plan)
+  unsigned race_lanes_log2 = 2;   // K6's grid: lanes over all rivals = 2^this x the expected 2^d trials
+  int race_fused_max = POW_RACE_FUSED_MAX_D;  // pow_mine_race: highest d on the fused path (-1 = host loop only)
   // K1' and K2' launches as AQL packets (pow_aql.cpp) instead of
   // hipLaunchKernel: test library only, opt-in there; null = the HIP launch
   // path, the only one the shipped library has.
@@ -188,6 +246,8 @@ hipError_t pow_launch_chain(hipStream_t stream, const PowChainLaunch& L, const u
                             PowChainCtl* ctl, PowChainSlot* slots);
 hipError_t pow_launch_batch(hipStream_t stream, const PowBatchLaunch& L, uint32_t n_tmpl, const uint32_t* tmpls,
                             PowBatchCtl* ctl, PowChainSlot* slots, PowBatchRec* rec);
+hipError_t pow_launch_race(hipStream_t stream, const PowRaceLaunch& L, const uint32_t* prev, uint32_t* dst,
+                           const PowRaceIn* in, PowRaceCtl* ctl, PowChainSlot* slots, PowRaceRec* rec);
 hipError_t pow_sort_u32(void* temp, size_t* temp_bytes, uint32_t* keys, uint32_t* alt, uint32_t n,
                         uint32_t** sorted, hipStream_t stream);
 hipError_t pow_launch_search_lat(bool full, bool any, bool asm_groups, unsigned grid, hipStream_t stream,

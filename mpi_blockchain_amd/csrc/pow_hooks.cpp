@@ -39,6 +39,11 @@ void configure(pow_ctx* ctx) {
   if (const char* bf = getenv("POW_BATCH_FUSED_MAX")) ctx->batch_fused_max = (int)std::max(-1l, std::min(32l, strtol(bf, nullptr, 0)));
   if (const char* bt = getenv("POW_BATCH_TILE")) ctx->batch_tile = (unsigned)std::min((unsigned long)POW_BATCH_MAX_TILE, strtoul(bt, nullptr, 0));
   if (const char* bl = getenv("POW_BATCH_LANES_LOG2")) ctx->batch_lanes_log2 = (int)std::min(8ul, strtoul(bl, nullptr, 0));
+  // pow_mine_race: the highest d on the fused path (-1: the host loop at every d), heights per batch
+  // (the window cap still holds) and K6's lanes over all rivals (as K4's)
+  if (const char* rf = getenv("POW_RACE_FUSED_MAX")) ctx->race_fused_max = (int)std::max(-1l, std::min(32l, strtol(rf, nullptr, 0)));
+  if (const char* rb = getenv("POW_RACE_BATCH")) ctx->race_batch = (unsigned)std::min((unsigned long)POW_RACE_MAX_BATCH, strtoul(rb, nullptr, 0));
+  if (const char* rl = getenv("POW_RACE_LANES_LOG2")) ctx->race_lanes_log2 = (unsigned)std::min(8ul, strtoul(rl, nullptr, 0));
   if (const char* g = getenv("POW_GRID_PER_CU")) {  // launch-geometry experiments
     const int per = atoi(g);
     if (per > 0 && per <= 64) ctx->grid_full = (unsigned)ctx->cu_count * (unsigned)per;

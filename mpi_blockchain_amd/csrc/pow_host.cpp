@@ -214,6 +214,35 @@ void make_launch_lat(uint64_t start, uint64_t count, unsigned diff, PowLaunchLat
   L->thr = diff_thr(diff);
 }
 
+void pow_race_plan(unsigned diff, uint32_t n_rivals, uint64_t ctr_count, uint32_t cu_count, unsigned lanes_log2,
+                   unsigned batch_override, PowRacePlan* p) {
+  const uint64_t R = n_rivals < 1 ? 1 : n_rivals;
+  const uint64_t cus = cu_count < 1 ? 1 : cu_count;
+  const unsigned d = diff > 32 ? 32 : diff;
+  // Lanes over all rivals for 2^lanes_log2 times the 2^d trials a height is
+  // expected to cost, split evenly: a rival gets no more lanes than its window
+  // has counters, at least one workgroup, and no more workgroups than its share
+  // of one per CU.
+  const uint64_t total = 1ull << (d + (lanes_log2 > 8 ? 8 : lanes_log2));
+  uint64_t lanes = (total + R - 1) / R;
+  if (lanes > ctr_count) lanes = ctr_count;
+  uint64_t nwg = (lanes + 255) / 256;
+  const uint64_t share = cus / R < 1 ? 1 : cus / R;
+  if (nwg > share) nwg = share;
+  if (nwg < 1) nwg = 1;
+  p->nwg_r = (uint32_t)nwg;
+  // A batch is about 2^26 expected trials (a handful of ms: the cancel
+  // latency), at most 64 heights, and the largest for which the windows of all
+  // rivals of all its heights hold 2^38 counters at most; never below one.
+  uint64_t batch = batch_override ? batch_override : 1ull << (26 - (d > 26 ? 26 : d));
+  if (batch > 64) batch = 64;
+  const uint64_t per_height = R * (ctr_count < 1 ? 1 : ctr_count);  // <= 2^40
+  const uint64_t cap = (1ull << 38) / per_height;
+  if (batch > cap) batch = cap;
+  if (batch < 1) batch = 1;
+  p->batch = (uint32_t)batch;
+}
+
 extern "C" {
 
 const char* pow_last_error(void) { return g_err.c_str(); }

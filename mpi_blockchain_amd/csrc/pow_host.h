@@ -36,4 +36,18 @@ int make_launch(uint64_t start, uint64_t count, unsigned diff, uint32_t cap, uin
 // of *L is zeroed (watch, nwg and seq are the caller's).
 void make_launch_lat(uint64_t start, uint64_t count, unsigned diff, PowLaunchLat* L);
 
+// The plan of pow_mine_race's fused path (K6, one launch per height): the
+// workgroups a rival gets and the heights queued per batch.  Pure: its inputs
+// are the difficulty (<= 32), the rivals (1..256), the window (1..2^32) and the
+// chip's CUs, and the test library's two overrides (lanes_log2: 2 is the
+// shipped value; batch_override: 0 = none).  It holds that nwg_r >= 1, nwg_r x
+// n_rivals <= max(n_rivals, cu_count), 1 <= batch <= 64, and batch x n_rivals x
+// ctr_count <= 2^38 whenever batch > 1.
+struct PowRacePlan {
+  uint32_t nwg_r;  // workgroups per rival
+  uint32_t batch;  // heights per batch
+};
+void pow_race_plan(unsigned diff, uint32_t n_rivals, uint64_t ctr_count, uint32_t cu_count, unsigned lanes_log2,
+                   unsigned batch_override, PowRacePlan* p);
+
 #pragma GCC visibility pop

@@ -51,6 +51,17 @@ class MineBatchResult:
     kernel_ms: float      # GPU time of the call
 
 
+@dataclass
+class MineRaceResult:
+    blocks: ctypes.Array  # the winners' chain, tip first: Block * n_mined
+    winners: list         # per mined height, tip first: the winner's position in `owners`
+    counters: list        # per mined height, tip first: the winner's counter
+    n_mined: int          # heights mined
+    complete: bool        # all n were mined (pow_mine_race returned 1)
+    hashes: int           # trials issued
+    kernel_ms: float      # GPU time of the call
+
+
 def refresh_template(last: Block, rank: int, difficulty: int = DEFAULT_DIFFICULTY,
                      now: int | None = None) -> Block:
     """node.cpp:292-299: copy the last block, index+1, owner = rank,
@@ -246,6 +257,40 @@ class GpuMiner:
             blocks.append(b)
             counters.append(ctrs[i] if hit else None)
         return MineBatchResult(blocks, counters, solved.value, rc == 1, hashes.value, self.stats()["kernel_ms"])
+
+    def mine_race(self, parent: Block, n: int, difficulty: int = DEFAULT_DIFFICULTY, owners=(0,), created_at=None,
+                  ctr_start: int = 0, ctr_count: int = 1 << 32, epoch: int | None = None) -> MineRaceResult:
+        """pow_mine_race: ``len(owners)`` rival miners race over `n` heights on
+        top of `parent`; at every height the rival with the lowest solving
+        counter wins (ties to the lowest position in `owners`) and its block is
+        the next height's parent.  `created_at` has ``n * len(owners)`` entries,
+        height-major.  ``blocks`` is the winners' chain tip first, a ctypes
+        ``Block * n_mined`` array (what :meth:`verify_chain` takes), with
+        ``winners`` and ``counters`` beside it; all are shorter than `n` if at
+        some height no window held a solution or :meth:`cancel` was called
+        meanwhile.  The host statement of the result is
+        :func:`mpi_blockchain_amd.block.mine_race`."""
+        R = len(owners)
+        own = (ctypes.c_uint32 * max(R, 1))(*[o & 0xFFFFFFFF for o in owners])
+        out = (Block * max(n, 1))()
+        times = None
+        if created_at is not None:
+            if len(created_at) != n * R:
+                raise ValueError(f"created_at has {len(created_at)} entries for {n} heights of {R} rivals")
+            times = (ctypes.c_uint64 * max(n * R, 1))(*created_at)
+        win = (ctypes.c_uint32 * max(n, 1))()
+        ctrs = (ctypes.c_uint64 * max(n, 1))()
+        mined, hashes = ctypes.c_size_t(), ctypes.c_uint64()
+        ep = self._cancel.value if epoch is None else epoch
+        rc = check(self.L.pow_mine_race(self.ctx, ctypes.byref(parent), n, difficulty, own, R, times, ctr_start,
+                                        ctr_count, ctypes.byref(self._cancel), ep, out, win, ctrs,
+                                        ctypes.byref(mined), ctypes.byref(hashes)), self.L)
+        m = mined.value
+        blocks = (Block * m)()
+        if m:
+            ctypes.memmove(blocks, ctypes.byref(out, (n - m) * ctypes.sizeof(Block)), m * ctypes.sizeof(Block))
+        return MineRaceResult(blocks, list(win)[n - m:n], list(ctrs)[n - m:n], m, rc == 1, hashes.value,
+                              self.stats()["kernel_ms"])
 
     def sweep(self, tmpl: Block, start: int, count: int, difficulty: int, cap: int | None = None) -> np.ndarray:
         """Ascending (counter - start) of every solving counter (count <= 2^32)."""
