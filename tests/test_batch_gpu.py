@@ -179,7 +179,7 @@ def test_layout_traps(fused):
 
 
 # ---- 7: counter edges ----
-@pytest.mark.parametrize("start", [62 ** 4 - 3, 62 ** 9 - (1 << 12)])
+@pytest.mark.parametrize("start", [62 ** 4 - 3, 62 ** 6 - 3, 62 ** 7 - 3, 62 ** 8 - 3, 62 ** 9 - (1 << 12)])
 def test_counter_edges(fused, start):
     check_against_statement(fused, mixed_templates(3), 4, start, 1 << 12)
 

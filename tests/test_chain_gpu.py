@@ -134,7 +134,7 @@ def test_layout_traps(miner_batch4, index):
 
 
 # ---- 6: counter edges ----
-@pytest.mark.parametrize("start", [62 ** 4 - 3, 62 ** 9 - (1 << 12)])
+@pytest.mark.parametrize("start", [62 ** 4 - 3, 62 ** 6 - 3, 62 ** 7 - 3, 62 ** 8 - 3, 62 ** 9 - (1 << 12)])
 def test_counter_edges(miner, start):
     check_against_statement(miner, cu.genesis(), 3, 4, 0, times(3), start, 1 << 12)
 

@@ -200,7 +200,7 @@ def test_layout_traps(fused):
 
 
 # ---- 10: counter edges ----
-@pytest.mark.parametrize("start", [62 ** 4 - 3, 62 ** 9 - (1 << 12)])
+@pytest.mark.parametrize("start", [62 ** 4 - 3, 62 ** 6 - 3, 62 ** 7 - 3, 62 ** 8 - 3, 62 ** 9 - (1 << 12)])
 def test_counter_edges(fused, start):
     check_against_statement(fused, ru.genesis(), 3, 4, [2, 0, 1], ru.times(3, 3), start, 1 << 12)
 

@@ -1,12 +1,14 @@
 """The 32-bit difficulty seam on the GPU.  Every kernel changes its
 proof-of-work test there: K1 and K1' go from H0 <= thr (thr = 0 at d = 32) to
-the full-width count above 32, K3 counts over eight words at every d, K4
-compares H0 <= thr up to 32 and leaves d > 32 to the host loop.  The witnesses
+the full-width count above 32, K3 counts over eight words at every d, K4, K5
+and K6 (pow_mine_chain, pow_mine_batch, pow_mine_race) compare H0 <= thr up to
+32 and leave d > 32 to their host loops over pow_mine.  The witnesses
 (tests/golden/lz_witnesses.json) are digests with exactly 31, 32 and 33 leading
 zero bits, so each side of the seam has an accept and a reject.
 
 Every expected value is hashlib's (seam_util, the host statements
-block.mine_chain and block.verify_chain) or Python's bit_length."""
+block.mine_chain, block.mine_batch, block.mine_race and block.verify_chain) or
+Python's bit_length."""
 import contextlib
 import ctypes
 import os
@@ -15,19 +17,22 @@ import numpy as np
 import pytest
 
 from mpi_blockchain_amd._lib import Block, load
-from mpi_blockchain_amd.block import V_WORK, field, make_block, mine_chain, set_field
-from mpi_blockchain_amd.miner import GpuMiner
+from mpi_blockchain_amd.block import V_WORK, field, make_block, mine_batch, mine_chain, mine_race, set_field
+from mpi_blockchain_amd.miner import GpuMiner, refresh_template
 from oracle.oracle import py_nonce_from_counter
 
+import batch_util as bu
 import chain_util as cu
 import helpers
+import race_util as ru
 import seam_util as su
 import verify_util as vu
 
 pytestmark = pytest.mark.gpu
 
 SWITCHES = ("POW_FORCE_FULL", "POW_LAT_MAX", "POW_LAT_WPS", "POW_CHAIN_BATCH", "POW_CHAIN_FUSED_MAX",
-            "POW_CHAIN_LANES_LOG2")
+            "POW_CHAIN_LANES_LOG2", "POW_BATCH_FUSED_MAX", "POW_BATCH_TILE", "POW_BATCH_LANES_LOG2", "POW_RACE_FUSED_MAX",
+            "POW_RACE_BATCH", "POW_RACE_LANES_LOG2")
 # The shipped library; K1 only (no latency kernel); the d > 32 variants at every
 # d; and K1' at 4 waves per SIMD (its asm-group variant) with the d > 32 test:
 # pow_mine runs K1' only at d <= 21, so this is its only route to K1'<FULL>.
@@ -260,3 +265,101 @@ def test_chain_above_32_bits_takes_the_host_loop():
     with GpuMiner(0) as m:
         check_chain_window(m, 33, "solves", fused=False)
         check_chain_window(m, 33, "misses", fused=False)
+
+
+# ---- G: K5 and K6 at d = 31 and 32, their host loops at 33 ----
+def check_batch_window(m, d, kind, fused):
+    """pow_mine_batch with the refreshed templates of owners 5 and 261 (the
+    same message: the witness decides both) over a witness's window against
+    the host statement, all 552 bytes of both."""
+    parent, owner, created, start, w = chain_case(d, kind)
+    assert owner == 5
+    tmpls = [refresh_template(parent, o, d, created[0]) for o in (5, 261)]
+    stated = mine_batch(tmpls, d, start, su.WINDOW)
+    rc, solved, hashes, ctrs, out = bu.call(m.L, m.ctx, tmpls, d, start, su.WINDOW)
+    if kind == "solves":
+        assert [c for _, c in stated] == [w["counter"]] * 2  # the statement says which counter of the window wins
+        assert (rc, solved) == (1, 2), (rc, solved, m.L.pow_last_error())
+        assert ctrs == [w["counter"]] * 2
+    else:
+        assert stated == [(None, None)] * 2, "the witness's window holds a real solution: pick another witness"
+        assert (rc, solved) == (0, 0), (rc, solved, m.L.pow_last_error())
+        assert ctrs == [bu.NONE] * 2
+    assert bytes(out) == bu.expected_bytes(stated)  # the fill where nothing solved
+    s = m.stats()
+    assert s["hashes"] == hashes
+    if fused:
+        assert s["launches"] == 1 and 2 <= hashes <= 2 * su.WINDOW  # one K5 launch; a lane tests a counter at most once
+    return bytes(out), ctrs
+
+
+def check_race_window(m, d, kind, owners, fused):
+    """pow_mine_race for one height with equal created_at over a witness's
+    window against the host statement, which hashes rival 6's window too and so
+    says who wins."""
+    parent, owner, created, start, w = chain_case(d, kind)
+    assert owner == 5
+    stated = mine_race(parent, 1, d, owners, created * 2, start, su.WINDOW)
+    rc, mined, hashes, winners, ctrs, out = ru.call(m.L, m.ctx, parent, 1, d, owners, created * 2, start, su.WINDOW)
+    k = len(stated[0])
+    if kind == "solves":
+        assert k == 1 and stated[2][0] <= w["counter"]  # owner 5 solves at the witness, unless owner 6 does below it
+        if stated[2][0] == w["counter"]:
+            assert owners[stated[1][0]] == 5
+    elif k == 1:
+        assert owners[stated[1][0]] == 6  # owner 5's window is empty: only owner 6 can have solved
+    assert (rc, mined) == (k, k), (rc, mined, m.L.pow_last_error())
+    want_bytes, want_winners, want_ctrs = ru.expected(stated, 1)
+    assert (winners, ctrs) == (want_winners, want_ctrs)
+    assert bytes(out) == want_bytes
+    s = m.stats()
+    assert s["hashes"] == hashes
+    if fused:
+        assert s["launches"] == 1 and 1 <= hashes <= 2 * su.WINDOW  # one K6 launch
+    return bytes(out), winners, ctrs
+
+
+@pytest.mark.parametrize("d", [31, 32])
+def test_fused_batch_at_the_seam(d):
+    got = {}
+    with miner_with(POW_BATCH_FUSED_MAX=32) as m:
+        for kind in ("solves", "misses"):
+            got[kind] = check_batch_window(m, d, kind, fused=True)
+    with miner_with(POW_BATCH_FUSED_MAX=-1) as h:  # the host loop over pow_mine: the same bytes
+        for kind in ("solves", "misses"):
+            assert check_batch_window(h, d, kind, fused=False) == got[kind]
+
+
+@pytest.mark.parametrize("owners", [[5, 6], [6, 5]])
+@pytest.mark.parametrize("d", [31, 32])
+def test_fused_race_at_the_seam(d, owners):
+    got = {}
+    with miner_with(POW_RACE_FUSED_MAX=32) as m:
+        for kind in ("solves", "misses"):
+            got[kind] = check_race_window(m, d, kind, owners, fused=True)
+    with miner_with(POW_RACE_FUSED_MAX=-1) as h:  # the host loop over pow_mine: the same bytes
+        for kind in ("solves", "misses"):
+            assert check_race_window(h, d, kind, owners, fused=False) == got[kind]
+
+
+def test_batch_above_32_bits_takes_the_host_loop():
+    """d = 33 never runs K5, whose test is H0 <= thr: thr = 0 would accept the
+    "misses" witness (32 leading zero bits).  The host loop's K1 <FULL> rejects
+    it and accepts the 33-bit one, as the statement does."""
+    with miner_with(POW_BATCH_FUSED_MAX=32) as m:
+        check_batch_window(m, 33, "solves", fused=False)
+        check_batch_window(m, 33, "misses", fused=False)
+    with GpuMiner(0) as m:
+        check_batch_window(m, 33, "solves", fused=False)
+        check_batch_window(m, 33, "misses", fused=False)
+
+
+@pytest.mark.parametrize("owners", [[5, 6], [6, 5]])
+def test_race_above_32_bits_takes_the_host_loop(owners):
+    """As the batch: K6's H0 <= 0 would accept the 32-bit "misses" witness at d = 33."""
+    with miner_with(POW_RACE_FUSED_MAX=32) as m:
+        check_race_window(m, 33, "solves", owners, fused=False)
+        check_race_window(m, 33, "misses", owners, fused=False)
+    with GpuMiner(0) as m:
+        check_race_window(m, 33, "solves", owners, fused=False)
+        check_race_window(m, 33, "misses", owners, fused=False)
