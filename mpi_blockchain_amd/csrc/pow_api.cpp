@@ -810,8 +810,37 @@ int pow_mine_any(pow_ctx* ctx, const pow_block* tmpl, uint64_t ctr_start, uint64
 
 namespace {
 
+// The argument checks that pow_mine_chain, pow_mine_batch and pow_mine_race
+// open with; `what` is the call's noun and `items` what its n counts.
+int check_fused_args(unsigned diff_bits, uint64_t ctr_start, uint64_t ctr_count, size_t n, const char* what,
+                     const char* items) {
+  if (diff_bits > 256) return fail(POW_EINVAL, "diff_bits %u > 256", diff_bits);
+  if (ctr_count == 0 || ctr_count > (1ull << 32))
+    return fail(POW_EINVAL, "ctr_count %llu not in 1..2^32", (unsigned long long)ctr_count);
+  if (ctr_start >= POW_COUNTER_LIMIT || ctr_count > POW_COUNTER_LIMIT - ctr_start)
+    return fail(POW_EINVAL, "counter range past 62^9");
+  if (n > (1u << 24)) return fail(POW_EINVAL, "%s too large (%zu %s > 2^24)", what, n, items);
+  return POW_OK;
+}
+
+// The head of a K4, K5 or K6 launch's arguments (the caller has zeroed them).
+void fill_head(PowWalkHead* w, uint64_t ctr_start, uint64_t ctr_count, unsigned diff_bits) {
+  PowLaunchLat digits;
+  make_launch_lat(ctr_start, ctr_count, diff_bits, &digits);
+  memcpy(w->base_digit, digits.base_digit, sizeof w->base_digit);
+  w->thr = digits.thr;
+  w->count = ctr_count;
+}
+
+// A pow_mine call's stats (it resets ctx->stats as it starts) into the running total.
+void add_stats(pow_stats* total, const pow_stats& s) {
+  total->kernel_ms += s.kernel_ms;
+  total->launches += s.launches;
+  total->hashes += s.hashes;
+}
+
 static_assert(offsetof(PowChainBuf, ctl) == sizeof(pow_block) &&
-                  offsetof(PowChainBuf, blk) == offsetof(PowChainBuf, ctl) + sizeof(PowChainCtl),
+                  offsetof(PowChainBuf, blk) == offsetof(PowChainBuf, ctl) + sizeof(PowSealCtl),
               "parent + ctl go up, ctl + blocks come down: one copy each");
 
 // The buffers of the fused path, made at the first call that needs them.
@@ -847,12 +876,7 @@ int pow_mine_chain(pow_ctx* ctx, const pow_block* parent, size_t n, unsigned dif
                    const uint64_t* created_at, uint64_t ctr_start, uint64_t ctr_count,
                    const volatile uint32_t* cancel_word, uint32_t epoch, pow_block* out, size_t* n_mined,
                    uint64_t* hashes_done) {
-  if (diff_bits > 256) return fail(POW_EINVAL, "diff_bits %u > 256", diff_bits);
-  if (ctr_count == 0 || ctr_count > (1ull << 32))
-    return fail(POW_EINVAL, "ctr_count %llu not in 1..2^32", (unsigned long long)ctr_count);
-  if (ctr_start >= POW_COUNTER_LIMIT || ctr_count > POW_COUNTER_LIMIT - ctr_start)
-    return fail(POW_EINVAL, "counter range past 62^9");
-  if (n > (1u << 24)) return fail(POW_EINVAL, "chain too large (%zu blocks > 2^24)", n);
+  if (int rc = check_fused_args(diff_bits, ctr_start, ctr_count, n, "chain", "blocks")) return rc;
   if (!ctx || ((!parent || !out) && n)) return fail(POW_EINVAL, "null");
   if (ctx->board) return fail(POW_EINVAL, "pow_mine_chain does not run on a context bound to a stop board");
   ctx->stats = pow_stats{};
@@ -876,9 +900,7 @@ int pow_mine_chain(pow_ctx* ctx, const pow_block* parent, size_t n, unsigned dif
       refresh(&tmpl, &last, owner, diff_bits, created_at ? created_at[done] : now);
       const int rc = mine_impl(ctx, &tmpl, ctr_start, ctr_count, diff_bits, cancel_word, epoch, &blk, nullptr, nullptr,
                                false);
-      total.kernel_ms += ctx->stats.kernel_ms;
-      total.launches += ctx->stats.launches;
-      total.hashes += ctx->stats.hashes;
+      add_stats(&total, ctx->stats);
       if (rc < 0) return finish(rc);
       if (rc == 0) break;
       out[n - 1 - done] = last = blk;
@@ -889,16 +911,10 @@ int pow_mine_chain(pow_ctx* ctx, const pow_block* parent, size_t n, unsigned dif
   if (cancel_moved(cancel_word, epoch)) return finish(0);
   if (int rc = ensure_chain(ctx)) return rc;
   PowChainLaunch L;
-  {
-    PowLaunchLat digits;
-    make_launch_lat(ctr_start, ctr_count, diff_bits, &digits);
-    memset(&L, 0, sizeof L);
-    memcpy(L.base_digit, digits.base_digit, sizeof L.base_digit);
-    L.thr = digits.thr;
-    L.owner = owner;
-    L.diff = diff_bits;
-    L.count = ctr_count;
-  }
+  memset(&L, 0, sizeof L);
+  fill_head(&L.w, ctr_start, ctr_count, diff_bits);
+  L.owner = owner;
+  L.diff = diff_bits;
   // The grid follows the difficulty: lanes for four times the expected 2^d
   // trials (a block then costs one trial's latency but for 1 in e^4; at d = 9
   // and 13 two times measured 1.4 and 0.6 us per block slower, eight times 0.3
@@ -920,7 +936,7 @@ int pow_mine_chain(pow_ctx* ctx, const pow_block* parent, size_t n, unsigned dif
     if (cancel_moved(cancel_word, epoch)) return finish(0);
     const size_t nb = std::min(batch, n - done);
     memset(&H->ctl, 0, sizeof H->ctl);
-    H->ctl.min_rel = ~0ull;
+    H->ctl.min_key = ~0ull;
     HIP_OK(hipMemcpyAsync(D, H, offsetof(PowChainBuf, blk), hipMemcpyHostToDevice, ctx->stream));
     if (pow_hooks)
       if (int rc = pow_hooks->before_launch(ctx)) return rc;
@@ -932,7 +948,7 @@ int pow_mine_chain(pow_ctx* ctx, const pow_block* parent, size_t n, unsigned dif
                               ctx->d_cslot));
     }
     HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_OK(hipMemcpyAsync(&H->ctl, &D->ctl, sizeof(PowChainCtl) + nb * sizeof(pow_block), hipMemcpyDeviceToHost,
+    HIP_OK(hipMemcpyAsync(&H->ctl, &D->ctl, sizeof(PowSealCtl) + nb * sizeof(pow_block), hipMemcpyDeviceToHost,
                           ctx->stream));
     if (int rc = stream_wait_for(ctx, "chain mining batch", 2ull * nb * ctr_count)) return rc;  // 2 ns per counter
     float ms = 0;
@@ -976,12 +992,7 @@ int ensure_batch(pow_ctx* ctx) {
 int pow_mine_batch(pow_ctx* ctx, const pow_block* tmpls, size_t n, unsigned diff_bits, uint64_t ctr_start,
                    uint64_t ctr_count, const volatile uint32_t* cancel_word, uint32_t epoch, pow_block* out,
                    uint64_t* found_ctr, size_t* n_solved, uint64_t* hashes_done) {
-  if (diff_bits > 256) return fail(POW_EINVAL, "diff_bits %u > 256", diff_bits);
-  if (ctr_count == 0 || ctr_count > (1ull << 32))
-    return fail(POW_EINVAL, "ctr_count %llu not in 1..2^32", (unsigned long long)ctr_count);
-  if (ctr_start >= POW_COUNTER_LIMIT || ctr_count > POW_COUNTER_LIMIT - ctr_start)
-    return fail(POW_EINVAL, "counter range past 62^9");
-  if (n > (1u << 24)) return fail(POW_EINVAL, "batch too large (%zu templates > 2^24)", n);
+  if (int rc = check_fused_args(diff_bits, ctr_start, ctr_count, n, "batch", "templates")) return rc;
   if (!ctx || ((!tmpls || !out) && n)) return fail(POW_EINVAL, "null");
   if (ctx->board) return fail(POW_EINVAL, "pow_mine_batch does not run on a context bound to a stop board");
   ctx->stats = pow_stats{};
@@ -1003,9 +1014,7 @@ int pow_mine_batch(pow_ctx* ctx, const pow_block* tmpls, size_t n, unsigned diff
       uint64_t ctr = UINT64_MAX;
       const int rc = mine_impl(ctx, &tmpls[i], ctr_start, ctr_count, diff_bits, cancel_word, epoch, &out[i], &ctr, nullptr,
                                false);
-      total.kernel_ms += ctx->stats.kernel_ms;
-      total.launches += ctx->stats.launches;
-      total.hashes += ctx->stats.hashes;
+      add_stats(&total, ctx->stats);
       if (rc < 0) return finish(rc);
       if (rc == 1) {
         if (found_ctr) found_ctr[i] = ctr;
@@ -1017,14 +1026,8 @@ int pow_mine_batch(pow_ctx* ctx, const pow_block* tmpls, size_t n, unsigned diff
   if (cancel_moved(cancel_word, epoch)) return finish(0);
   if (int rc = ensure_batch(ctx)) return rc;
   PowBatchLaunch L;
-  {
-    PowLaunchLat digits;
-    make_launch_lat(ctr_start, ctr_count, diff_bits, &digits);
-    memset(&L, 0, sizeof L);
-    memcpy(L.base_digit, digits.base_digit, sizeof L.base_digit);
-    L.thr = digits.thr;
-    L.count = ctr_count;
-  }
+  memset(&L, 0, sizeof L);
+  fill_head(&L.w, ctr_start, ctr_count, diff_bits);
   // Templates per launch: about 2^26 expected trials (a handful of ms: the
   // cancel latency), a grid of at most 2^16 workgroups, and windows of at most
   // 2^38 counters in all, which keeps the watchdog's 2 ns per counter a bound
@@ -1094,7 +1097,7 @@ int pow_mine_batch(pow_ctx* ctx, const pow_block* tmpls, size_t n, unsigned diff
 namespace {
 
 static_assert(offsetof(PowRaceBuf, ctl) == sizeof(pow_block) &&
-                  offsetof(PowRaceBuf, rec) == offsetof(PowRaceBuf, ctl) + sizeof(PowRaceCtl) &&
+                  offsetof(PowRaceBuf, rec) == offsetof(PowRaceBuf, ctl) + sizeof(PowSealCtl) &&
                   offsetof(PowRaceBuf, blk) == offsetof(PowRaceBuf, rec) + sizeof(PowRaceRec) * POW_RACE_MAX_BATCH,
               "parent + ctl go up; ctl, records and blocks come down: one copy each");
 
@@ -1133,12 +1136,7 @@ int pow_mine_race(pow_ctx* ctx, const pow_block* parent, size_t n, unsigned diff
                   size_t n_rivals, const uint64_t* created_at, uint64_t ctr_start, uint64_t ctr_count,
                   const volatile uint32_t* cancel_word, uint32_t epoch, pow_block* out, uint32_t* winners,
                   uint64_t* found_ctr, size_t* n_mined, uint64_t* hashes_done) {
-  if (diff_bits > 256) return fail(POW_EINVAL, "diff_bits %u > 256", diff_bits);
-  if (ctr_count == 0 || ctr_count > (1ull << 32))
-    return fail(POW_EINVAL, "ctr_count %llu not in 1..2^32", (unsigned long long)ctr_count);
-  if (ctr_start >= POW_COUNTER_LIMIT || ctr_count > POW_COUNTER_LIMIT - ctr_start)
-    return fail(POW_EINVAL, "counter range past 62^9");
-  if (n > (1u << 24)) return fail(POW_EINVAL, "race too large (%zu heights > 2^24)", n);
+  if (int rc = check_fused_args(diff_bits, ctr_start, ctr_count, n, "race", "heights")) return rc;
   if (n_rivals == 0 || n_rivals > POW_RACE_MAX_RIVALS)
     return fail(POW_EINVAL, "n_rivals %zu not in 1..%d", n_rivals, POW_RACE_MAX_RIVALS);
   if (!ctx || ((!parent || !out || !owners) && n)) return fail(POW_EINVAL, "null");
@@ -1185,9 +1183,7 @@ int pow_mine_race(pow_ctx* ctx, const pow_block* parent, size_t n, unsigned diff
         uint64_t ctr = UINT64_MAX;
         refresh(&tmpl, &last, owners[r], diff_bits, created_at ? created_at[done * R + r] : now);
         const int rc = mine_impl(ctx, &tmpl, ctr_start, window, diff_bits, cancel_word, epoch, &blk, &ctr, nullptr, false);
-        total.kernel_ms += ctx->stats.kernel_ms;
-        total.launches += ctx->stats.launches;
-        total.hashes += ctx->stats.hashes;
+        add_stats(&total, ctx->stats);
         if (rc < 0) return finish(rc);
         if (rc == 1) {
           best = blk;
@@ -1212,17 +1208,11 @@ int pow_mine_race(pow_ctx* ctx, const pow_block* parent, size_t n, unsigned diff
   pow_race_plan(diff_bits, (uint32_t)R, ctr_count, (uint32_t)std::max(1, ctx->cu_count), ctx->race_lanes_log2,
                 ctx->race_batch, &plan);
   PowRaceLaunch L;
-  {
-    PowLaunchLat digits;
-    make_launch_lat(ctr_start, ctr_count, diff_bits, &digits);
-    memset(&L, 0, sizeof L);
-    memcpy(L.base_digit, digits.base_digit, sizeof L.base_digit);
-    L.thr = digits.thr;
-    L.diff = diff_bits;
-    L.n_rivals = (uint32_t)R;
-    L.nwg_r = plan.nwg_r;
-    L.count = ctr_count;
-  }
+  memset(&L, 0, sizeof L);
+  fill_head(&L.w, ctr_start, ctr_count, diff_bits);
+  L.diff = diff_bits;
+  L.n_rivals = (uint32_t)R;
+  L.nwg_r = plan.nwg_r;
   if ((uint64_t)L.nwg_r * R > ctx->race_grid_max)
     return fail(POW_EHIP, "race plan: %u workgroups for %u slots", (unsigned)(L.nwg_r * R), ctx->race_grid_max);
   PowRaceBuf* const H = ctx->h_race;

@@ -24,47 +24,62 @@ struct PowVerifyRes {
   unsigned int n_bad;      // flagged blocks (atomic add)
 };
 
+// What K4, K5 and K6 share (pow_walk_dev.h: the lowest-key search and the seal).
+// The workgroups that count themselves out on one exit word: the word counts
+// them in its low 16 bits and carries their trials (at most 2^40 + one per
+// lane) above.  Every launch wrapper refuses a larger count.
+#define POW_WALK_MAX_WG (1u << 16)
+// The head of every launch's arguments: the window and the threshold.
+struct PowWalkHead {
+  uint32_t base_digit[9];  // base-62 digits of ctr_start (nonce[0..8])
+  uint32_t thr;            // a digest solves iff H0 <= thr (d <= 32)
+  uint64_t count;          // counters [ctr_start, ctr_start + count), count <= 2^32
+};
+// One workgroup's lowest hit of a launch, written before it leaves (rel = ~0:
+// none).  rel holds the search's key: K4, K5 the relative counter, K6 the race's key.
+struct PowChainSlot {
+  unsigned long long rel;
+  unsigned int digest[8];
+};
+// Control words of a batch of K4 or K6 launches: reset by the host before the
+// batch; min_key and exits are reset again by each launch's sealing workgroup
+// for the next one.
+struct PowSealCtl {
+  // lowest solving key of the running launch (atomic min); ~0 = none.  K4: counter - ctr_start;
+  // K6: (counter - ctr_start) << 8 | rival
+  unsigned long long min_key;
+  unsigned long long hashes;   // trials computed, all launches of the batch (added by each launch's sealer)
+  unsigned long long exits;    // the running launch: workgroups that have left (low 16 bits), their trials above
+  unsigned int stop;           // a launch in which no window held a solution: every later launch exits at once
+  unsigned int n_done;         // blocks sealed by the batch
+};
+
 // K4 (pow_chain_kernel, pow_chain.hip), one launch per block of pow_mine_chain.
 #define POW_CHAIN_MAX_BATCH 64   // launches queued without a host wait
 // pow_mine_chain: above it the host loop over pow_mine.  The largest measured d
 // at which the fused call beat the host loop (profiles/mine_chain/README.md).
 #define POW_CHAIN_FUSED_MAX_D 23
-// Control words of a batch: reset by the host before the batch; min_rel and
-// exits are reset again by each launch's sealing workgroup for the next one.
-struct PowChainCtl {
-  unsigned long long min_rel;  // lowest solving (counter - ctr_start) of the running launch (atomic min); ~0 = none
-  unsigned long long hashes;   // trials computed, all launches of the batch (added by each launch's sealer)
-  unsigned long long exits;    // the running launch: workgroups that have left (low 24 bits), their trials above
-  unsigned int stop;           // a launch's window held no solution: every later launch exits at once
-  unsigned int n_done;         // blocks sealed by the batch
-};
-// One workgroup's lowest hit of a launch, written before it leaves (rel = ~0: none).
-struct PowChainSlot {
-  unsigned long long rel;
-  unsigned int digest[8];
-};
 // A batch in device memory, and its pinned twin: parent and ctl go up in one
 // copy, ctl and the sealed blocks come down in one.  Block j of the batch is
 // blk[nb - 1 - j] (tip first); its launch reads blk[nb - j], the first parent.
 struct PowChainBuf {
   pow_block parent;
-  PowChainCtl ctl;
+  PowSealCtl ctl;
   pow_block blk[POW_CHAIN_MAX_BATCH];
 };
 // The arguments of one launch.
 struct PowChainLaunch {
-  uint32_t base_digit[9];  // base-62 digits of ctr_start (nonce[0..8])
-  uint32_t thr;            // a digest solves iff H0 <= thr (d <= 32)
+  PowWalkHead w;
   uint32_t owner, diff;    // the template's node_owner_number and difficulty
   uint32_t nwg;            // workgroups of the launch (= gridDim.x)
   uint32_t pad;
-  uint64_t count;          // counters [ctr_start, ctr_start + count), count <= 2^32
   uint64_t created_at;     // the template's created_at
 };
 
 // K5 (pow_batch_kernel, pow_batch.hip), one launch per tile of pow_mine_batch's templates.
 #define POW_BATCH_MAX_TILE (1u << 14)  // templates per launch
 #define POW_BATCH_MAX_WG (1u << 16)    // workgroups per launch
+static_assert(POW_BATCH_MAX_WG <= POW_WALK_MAX_WG, "a template's workgroups fit the exit word's count");
 // pow_mine_batch: above it the host loop over pow_mine.  The largest measured d
 // at which the fused call beat the C loop at n = 64 by more than the two
 // interquartile ranges combined (profiles/mine_batch/README.md); -1 = nowhere.
@@ -72,7 +87,7 @@ struct PowChainLaunch {
 // Control words of one template of a tile: reset by the host before the launch.
 struct PowBatchCtl {
   unsigned long long min_rel;  // lowest solving (counter - ctr_start) of the template (atomic min); ~0 = none
-  unsigned long long exits;    // the template's workgroups that have left (low 24 bits), their trials above
+  unsigned long long exits;    // the template's workgroups that have left (low 16 bits), their trials above
 };
 // One template's result, written by the last of its workgroups to leave.
 struct PowBatchRec {
@@ -82,29 +97,18 @@ struct PowBatchRec {
 };
 // The arguments of a launch: the tile's templates share window and difficulty.
 struct PowBatchLaunch {
-  uint32_t base_digit[9];  // base-62 digits of ctr_start (nonce[0..8])
-  uint32_t thr;            // a digest solves iff H0 <= thr (d <= 32)
+  PowWalkHead w;
   uint32_t nwg_t;          // workgroups per template; gridDim.x = nwg_t x the tile's templates
   uint32_t pad;
-  uint64_t count;          // counters [ctr_start, ctr_start + count), count <= 2^32
 };
 
 // K6 (pow_race_kernel, pow_race.hip), one launch per height of pow_mine_race.
 #define POW_RACE_MAX_BATCH 64       // launches queued without a host wait
-#define POW_RACE_MAX_WG (1u << 16)  // workgroups per launch: the exit word counts them in 16 bits
+#define POW_RACE_MAX_WG POW_WALK_MAX_WG  // a launch stays below it: every workgroup counts out on one exit word
 // pow_mine_race: above it the host loop over pow_mine.  The largest measured d
 // at which the fused call beat the host loop at 3 and at 64 rivals by more than
 // the two interquartile ranges combined (profiles/mine_race/README.md); -1 = nowhere.
 #define POW_RACE_FUSED_MAX_D 23
-// Control words of a batch: reset by the host before the batch; min_key and
-// exits are reset again by each launch's sealing workgroup for the next one.
-struct PowRaceCtl {
-  unsigned long long min_key;  // lowest solving ((counter - ctr_start) << 8 | rival) of the running launch (atomic min); ~0 = none
-  unsigned long long hashes;   // trials computed, all launches of the batch (added by each launch's sealer)
-  unsigned long long exits;    // the running launch: workgroups that have left (low 16 bits), their trials above
-  unsigned int stop;           // a launch in which no rival's window held a solution: every later launch exits at once
-  unsigned int n_done;         // heights sealed by the batch
-};
 // One height's result, written by the launch's sealing workgroup.
 struct PowRaceRec {
   unsigned long long rel;  // the winner's (counter - ctr_start)
@@ -117,7 +121,7 @@ struct PowRaceRec {
 // blk[nb - j], the first parent.
 struct PowRaceBuf {
   pow_block parent;
-  PowRaceCtl ctl;
+  PowSealCtl ctl;
   PowRaceRec rec[POW_RACE_MAX_BATCH];
   pow_block blk[POW_RACE_MAX_BATCH];
 };
@@ -129,13 +133,11 @@ struct PowRaceIn {
 };
 // The arguments of one launch.
 struct PowRaceLaunch {
-  uint32_t base_digit[9];  // base-62 digits of ctr_start (nonce[0..8])
-  uint32_t thr;            // a digest solves iff H0 <= thr (d <= 32)
+  PowWalkHead w;
   uint32_t diff;           // the templates' difficulty
   uint32_t n_rivals;       // 1..256
   uint32_t nwg_r;          // workgroups per rival; gridDim.x = nwg_r x n_rivals
   uint32_t height;         // of the batch: the row of PowRaceIn::created_at, and the record to write
-  uint64_t count;          // counters [ctr_start, ctr_start + count), count <= 2^32
 };
 
 struct pow_ctx {
@@ -243,11 +245,11 @@ hipError_t pow_launch_hash_one(hipStream_t stream, const PowMsg& M, PowHashOut* 
 hipError_t pow_launch_verify(uint32_t n_check, uint32_t n_avail, unsigned diff, hipStream_t stream,
                              const uint32_t* blocks, uint8_t* status, PowVerifyRes* res);
 hipError_t pow_launch_chain(hipStream_t stream, const PowChainLaunch& L, const uint32_t* prev, uint32_t* dst,
-                            PowChainCtl* ctl, PowChainSlot* slots);
+                            PowSealCtl* ctl, PowChainSlot* slots);
 hipError_t pow_launch_batch(hipStream_t stream, const PowBatchLaunch& L, uint32_t n_tmpl, const uint32_t* tmpls,
                             PowBatchCtl* ctl, PowChainSlot* slots, PowBatchRec* rec);
 hipError_t pow_launch_race(hipStream_t stream, const PowRaceLaunch& L, const uint32_t* prev, uint32_t* dst,
-                           const PowRaceIn* in, PowRaceCtl* ctl, PowChainSlot* slots, PowRaceRec* rec);
+                           const PowRaceIn* in, PowSealCtl* ctl, PowChainSlot* slots, PowRaceRec* rec);
 hipError_t pow_sort_u32(void* temp, size_t* temp_bytes, uint32_t* keys, uint32_t* alt, uint32_t n,
                         uint32_t** sorted, hipStream_t stream);
 hipError_t pow_launch_search_lat(bool full, bool any, bool asm_groups, unsigned grid, hipStream_t stream,

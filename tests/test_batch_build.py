@@ -81,14 +81,16 @@ def test_no_null_stream_in_batch_sources():
 
 def test_batch_kernel_never_waits_for_another_workgroup():
     """No grid barrier and no loop on a word another workgroup writes: the only
-    loops of the kernel are the lane's walk of its counters, the chunk and
-    schedule loops and the last workgroup's strided pass over the slots."""
-    src = open(os.path.join(CSRC, "pow_batch.hip")).read()
+    loops of the kernel (its own file and the shared pow_walk_dev.h) are the
+    lane's walk of its counters, the chunk and schedule loops and the last
+    workgroup's strided pass over the slots."""
+    src = open(os.path.join(CSRC, "pow_batch.hip")).read() + open(os.path.join(CSRC, "pow_walk_dev.h")).read()
     assert "cooperative_groups" not in src and "grid.sync" not in src
     loops = re.findall(r"\b(?:while|for)\s*\(([^\n]*)\)\s*\{?\s*$", src, flags=re.M)
     assert loops
     for cond in loops:
-        assert "exits" not in cond and "stop" not in cond and "left" not in cond and "seen" not in cond, cond
+        for word in ("exits", "stop", "left", "seen", "min_rel", "min_key", "n_done", "slots"):
+            assert word not in cond, cond
     # the walk's own condition is a lane-local flag
     assert re.search(r"\bwhile \(go\) \{", src)
 

@@ -522,3 +522,20 @@ def test_null_stream_check_catches_seeded_calls():
                "hipLaunchKernelGGL((k<1, 2>), dim3(1), dim3(64), 0, stream, a, b);", "k<<<1, 64, 0, st>>>(a);",
                "// hipMemcpy(h, d, 8, hipMemcpyDeviceToHost); in a comment", 'puts("hipMemset(d, 0, 8)");']:
         assert null_stream_calls("void f() {\n  " + ok + "\n}\n") == [], ok
+
+
+def test_fused_kernels_share_one_copy_of_their_helpers():
+    """K4, K5 and K6 were once copies of each other.  What they share lives in
+    csrc/pow_walk_dev.h and nowhere else: a definition of one of these names in
+    any other file under csrc/ is a copy.  (digit_char also has K1's own
+    arithmetic form in pow_kernels.hip and the host's in pow_host.cpp.)"""
+    elsewhere = {"digit_char": {"pow_kernels.hip": 1, "pow_host.cpp": 1}}
+    for name in ("digit_char", "nonce_chars", "message_word", "load_agent"):
+        definition = re.compile(rf"^[^\n;=#/]*\b{name}\s*\([^;{{}}]*\)\s*\{{", flags=re.M)
+        found = {}
+        for dirpath, _, files in os.walk(CSRC):
+            for f in files:
+                n = len(definition.findall(open(os.path.join(dirpath, f), errors="replace").read()))
+                if n:
+                    found[f] = n
+        assert found == {"pow_walk_dev.h": 1, **elsewhere.get(name, {})}, (name, found)

@@ -75,14 +75,17 @@ def test_no_null_stream_in_chain_sources():
 
 def test_chain_kernel_never_waits_for_another_workgroup():
     """No grid barrier and no loop on a word another workgroup writes: the only
-    loops of the kernel are the lane's walk of its counters, the chunk loop and
-    the sealer's strided passes."""
-    src = open(os.path.join(CSRC, "pow_chain.hip")).read()
+    loops of the kernel (its own file and the shared pow_walk_dev.h) are the
+    lane's walk of its counters, the chunk loop and the sealer's strided passes."""
+    src = open(os.path.join(CSRC, "pow_chain.hip")).read() + open(os.path.join(CSRC, "pow_walk_dev.h")).read()
     assert "cooperative_groups" not in src and "grid.sync" not in src
     loops = re.findall(r"\b(?:while|for)\s*\(([^\n]*)\)\s*\{?\s*$", src, flags=re.M)
     assert loops
     for cond in loops:
-        assert "exits" not in cond and "stop" not in cond and "n_done" not in cond, cond
+        for word in ("exits", "stop", "left", "seen", "min_key", "n_done", "slots"):
+            assert word not in cond, cond
+    # the walk's own condition is a lane-local flag
+    assert re.search(r"\bwhile \(go\) \{", src)
 
 
 def test_switches_only_in_the_test_library():

@@ -85,10 +85,10 @@ def test_no_null_stream_in_race_sources():
 
 def test_race_kernel_never_waits_for_another_workgroup():
     """No grid barrier and no loop on a word another workgroup writes: the only
-    loops of the kernel are the lane's walk of its counters, the chunk and
-    schedule loops, the last workgroup's strided pass over the slots and its
-    pass over the block's bytes."""
-    src = open(os.path.join(CSRC, "pow_race.hip")).read()
+    loops of the kernel (its own file and the shared pow_walk_dev.h) are the
+    lane's walk of its counters, the chunk and schedule loops, the last
+    workgroup's strided pass over the slots and its pass over the block's bytes."""
+    src = open(os.path.join(CSRC, "pow_race.hip")).read() + open(os.path.join(CSRC, "pow_walk_dev.h")).read()
     assert "cooperative_groups" not in src and "grid.sync" not in src
     loops = re.findall(r"\b(?:while|for)\s*\(([^\n]*)\)\s*\{?\s*$", src, flags=re.M)
     assert loops
