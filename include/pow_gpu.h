@@ -73,7 +73,7 @@ enum {
   POW_ECOMM = -5,     /* RCCL unavailable or a collective failed (pow_group_*) */
 };
 
-/* Per-call statistics of the last pow_mine / pow_sweep / pow_hash_blocks / pow_verify_chain. */
+/* Per-call statistics of the last pow_mine / pow_sweep / pow_hash_blocks / pow_verify_chain[s]. */
 typedef struct pow_stats {
   double kernel_ms;      /* sum of kernel durations on the ctx stream: HIP events around the
                             sweep/mine kernels; the latency kernel (first sub-round of
@@ -178,6 +178,57 @@ enum { POW_V_HASH = 1, POW_V_WORK = 2, POW_V_LINK = 4, POW_V_INDEX = 8 };
 int pow_verify_chain(pow_ctx* ctx, const pow_block* chain, size_t n, unsigned diff_bits,
                      uint8_t* status /* n bytes, may be NULL */,
                      size_t* first_bad /* may be NULL */, size_t* n_bad /* may be NULL */);
+
+/* "Which of these chains are valid, and which one wins?": pow_verify_chain's
+ * audit of n_chains independent chains in one call, one launch per tile of
+ * 2^16 blocks however many chains it holds.  `blocks` holds the chains back to
+ * back, each tip first as pow_verify_chain takes it: chain c is the
+ * lengths[c] blocks from position lengths[0] + ... + lengths[c - 1].  A length
+ * of 0 is allowed anywhere.  The raw structs go up as they are; the host work
+ * is per chain (n_chains + 1 offsets up, two words per chain down), never per
+ * block.
+ * status[g] (sum of lengths bytes, may be NULL), g the position in `blocks`,
+ * is exactly what pow_verify_chain gives that block when called on its chain
+ * alone (POW_V_HASH, POW_V_WORK, POW_V_LINK, POW_V_INDEX): the last block of
+ * every chain gets no link or index check, and what follows it in the buffer,
+ * another chain's tip, is not looked at.  first_bad[c] (n_chains entries, may
+ * be NULL) = the lowest flagged index within chain c, lengths[c] if none;
+ * n_bad[c] (n_chains entries, may be NULL) = the flagged blocks of chain c.
+ * *best (may be NULL) = the fork choice: among the chains with lengths[c] > 0
+ * and n_bad[c] == 0, the one whose tip (its first block) has the greatest
+ * index in plain uint32_t comparison, height being what the reference
+ * migrates on (node.cpp:249); ties go to the lowest c, as the reference keeps
+ * what it saw first and moves only to a strictly higher index; SIZE_MAX if no
+ * chain qualifies.
+ * Returns 1 if no block of any chain is flagged, 0 otherwise.  n_chains = 0,
+ * or all lengths 0, returns 1 with *best = SIZE_MAX.  POW_EINVAL, checked in
+ * this order before the context is touched and with nothing written: diff_bits
+ * > 256; n_chains > POW_VERIFY_MAX_CHAINS; the sum of lengths above 2^24; a
+ * null ctx, null lengths with n_chains > 0, or null blocks with a non-zero sum.
+ * Device memory: pow_verify_chain's 36 MB, and 12 bytes per chain (at most
+ * 4 MB of offsets and 8 MB of verdicts) with a pinned host twin of the same
+ * size, which only grow.
+ * pow_get_stats: kernel_ms, launches (one per tile), hashes = the sum of
+ * lengths.  pow_warmup does not launch this call's kernel.
+ * Cost (MI355X, profiles/verify_chains/README.md; chains x length, valid
+ * chains, against the loop of pow_verify_chain calls over the same chains and
+ * against the reference's block_to_hash loop at -O2 over as many blocks on
+ * the same box's CPU): 2 x 5: 72 us against 98 us and 29 us, so the call
+ * gains half a launch boundary on the loop and is still 2.5x slower than the
+ * CPU; 16 x 5: 98 us against 788 us and 229 us; 64 x 5: 105 us (1.6 us per
+ * chain; kernel 37 us) against 3.14 ms (49 us per chain) and 0.91 ms;
+ * 1,024 x 5: 154 us against 50.4 ms and 14.9 ms; 64 x 200: 227 us against
+ * 4.95 ms and 37.4 ms; 2^14 x 5: 1.02 ms (kernel 80 us, the rest is the copy
+ * of 45 MB of structs) against 810 ms and 238 ms.  64 x 5 costs more than one
+ * pow_verify_chain call of 200 blocks (77 us): the offsets' copy and the two
+ * resets are three more operations on the stream in front of the launch. */
+#define POW_VERIFY_MAX_CHAINS (1u << 20)
+int pow_verify_chains(pow_ctx* ctx, const pow_block* blocks, const uint32_t* lengths, size_t n_chains,
+                      unsigned diff_bits,
+                      uint8_t* status     /* sum(lengths) bytes, may be NULL */,
+                      uint32_t* first_bad /* n_chains, may be NULL */,
+                      uint32_t* n_bad     /* n_chains, may be NULL */,
+                      size_t* best        /* may be NULL */);
 
 /* Mining round: replaces node.cpp:302-308 (nonce -> hash -> test) for every
  * counter in [ctr_start, ctr_start + ctr_count).  The header fields and the

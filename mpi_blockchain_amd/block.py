@@ -16,6 +16,9 @@ reference                  here
 ``check_chain`` and more   :func:`verify_chain` (host statement of what
                            ``pow_verify_chain`` checks on the GPU:
                            :meth:`mpi_blockchain_amd.miner.GpuMiner.verify_chain`)
+the same, many chains     :func:`verify_chains` and :func:`best_chain` (host statement of
+                           ``pow_verify_chains``' verdicts and fork choice:
+                           :meth:`mpi_blockchain_amd.miner.GpuMiner.verify_chains`)
 ``proof_of_work``, solo    :func:`mine_chain` (host statement of the blocks
                            ``pow_mine_chain`` mines on the GPU:
                            :meth:`mpi_blockchain_amd.miner.GpuMiner.mine_chain`)
@@ -46,7 +49,7 @@ MAX_BLOCKS = 200
 ALPHABET = "abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789"
 
 __all__ = ["Block", "make_block", "block_to_str", "solves_problem", "nonce_from_counter",
-           "gen_random_nonce", "field", "set_field", "verify_chain", "mine_chain", "mine_batch", "V_HASH", "V_WORK", "V_LINK", "V_INDEX", "DEFAULT_DIFFICULTY", "BLOCKS_TO_MINE",
+           "gen_random_nonce", "field", "set_field", "verify_chain", "verify_chains", "best_chain", "mine_chain", "mine_batch", "V_HASH", "V_WORK", "V_LINK", "V_INDEX", "DEFAULT_DIFFICULTY", "BLOCKS_TO_MINE",
            "VALIDATION_MINUTES", "VALIDATION_BLOCKS", "HASH_SIZE", "NONCE_SIZE", "MSG_BYTES"]
 
 
@@ -144,6 +147,29 @@ def verify_chain(blocks, difficulty: int = DEFAULT_DIFFICULTY) -> list[int]:
                 flags |= V_INDEX
         status.append(flags)
     return status
+
+
+def verify_chains(chains, difficulty: int = DEFAULT_DIFFICULTY) -> list[list[int]]:
+    """The status bytes of every chain of `chains`, each audited on its own:
+    what ``pow_verify_chains`` computes on the GPU in one call.  A chain's
+    last block never links to what follows it in the batch."""
+    return [verify_chain(c, difficulty) for c in chains]
+
+
+def best_chain(chains, statuses) -> int | None:
+    """``pow_verify_chains``' fork choice, stated on the host: among the chains
+    that are not empty and have no flagged block (``statuses[c]`` all zero),
+    the position of the one whose tip, its first block, has the greatest
+    ``index`` as a plain unsigned 32-bit number; the lowest position on a tie
+    (the reference keeps what it saw first and moves only to a strictly higher
+    index, node.cpp:249); None if no chain qualifies."""
+    best = None
+    for c, (chain, status) in enumerate(zip(chains, statuses)):
+        if len(chain) == 0 or any(status):
+            continue
+        if best is None or chain[0].index > chains[best][0].index:
+            best = c
+    return best
 
 
 def mine_chain(parent: Block, n: int, difficulty: int = DEFAULT_DIFFICULTY, owner: int = 0, created_at=None,

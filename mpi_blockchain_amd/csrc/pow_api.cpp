@@ -417,6 +417,9 @@ void pow_destroy(pow_ctx* ctx) {
   (void)hipFree(ctx->d_vstatus);
   (void)hipFree(ctx->d_vres);
   if (ctx->h_vres) (void)hipHostFree(ctx->h_vres);
+  (void)hipFree(ctx->d_voffs);
+  (void)hipFree(ctx->d_vcres);
+  if (ctx->h_vchains) (void)hipHostFree(ctx->h_vchains);
   (void)hipFree(ctx->d_chain);
   (void)hipFree(ctx->d_cslot);
   if (ctx->h_chain) (void)hipHostFree(ctx->h_chain);
@@ -614,6 +617,108 @@ int pow_verify_chain(pow_ctx* ctx, const pow_block* chain, size_t n, unsigned di
   if (first_bad) *first_bad = lowest;
   if (n_bad) *n_bad = bad;
   return bad == 0 ? 1 : 0;
+}
+
+// K7 over the concatenated raw structs: the host work is per chain (the
+// offsets up, two verdict words per chain down, the fork choice), never per
+// block.  Tiles, halo and device buffers are pow_verify_chain's.
+int pow_verify_chains(pow_ctx* ctx, const pow_block* blocks, const uint32_t* lengths, size_t n_chains,
+                      unsigned diff_bits, uint8_t* status, uint32_t* first_bad, uint32_t* n_bad, size_t* best) {
+  if (diff_bits > 256) return fail(POW_EINVAL, "diff_bits %u > 256", diff_bits);
+  if (n_chains > POW_VERIFY_MAX_CHAINS)
+    return fail(POW_EINVAL, "too many chains (%zu > %u)", n_chains, POW_VERIFY_MAX_CHAINS);
+  size_t total = 0;
+  if (lengths)
+    for (size_t c = 0; c < n_chains; ++c)
+      if ((total += lengths[c]) > (1u << 24)) return fail(POW_EINVAL, "chains too large (more than 2^24 blocks)");
+  if (!ctx || (!lengths && n_chains) || (!blocks && total)) return fail(POW_EINVAL, "null");
+  ctx->stats = pow_stats{};
+  if (best) *best = SIZE_MAX;
+  if (total == 0) {
+    for (size_t c = 0; c < n_chains; ++c) {
+      if (first_bad) first_bad[c] = 0;
+      if (n_bad) n_bad[c] = 0;
+    }
+    return 1;
+  }
+  if (int rc = set_dev(ctx)) return rc;
+  const size_t kTile = 1u << 16;
+  const size_t want = std::min(total, kTile);
+  if (want > ctx->verify_cap) {
+    (void)hipFree(ctx->d_vblk);
+    (void)hipFree(ctx->d_vstatus);
+    ctx->d_vblk = nullptr;
+    ctx->d_vstatus = nullptr;
+    ctx->verify_cap = 0;
+    HIP_OK(hipMalloc(&ctx->d_vblk, (want + 1) * sizeof(pow_block)));  // + the halo block
+    HIP_OK(hipMalloc(&ctx->d_vstatus, want));
+    ctx->verify_cap = want;
+  }
+  if (n_chains > ctx->vchains_cap) {
+    (void)hipFree(ctx->d_voffs);
+    (void)hipFree(ctx->d_vcres);
+    if (ctx->h_vchains) (void)hipHostFree(ctx->h_vchains);
+    ctx->d_voffs = nullptr;
+    ctx->d_vcres = nullptr;
+    ctx->h_vchains = nullptr;
+    ctx->vchains_cap = 0;
+    HIP_OK(hipMalloc(&ctx->d_voffs, (n_chains + 1) * sizeof(uint32_t)));
+    HIP_OK(hipMalloc(&ctx->d_vcres, 2 * n_chains * sizeof(uint32_t)));
+    HIP_OK(hipHostMalloc(&ctx->h_vchains, (3 * n_chains + 1) * sizeof(uint32_t), hipHostMallocDefault));
+    ctx->vchains_cap = n_chains;
+  }
+  // first_bad, then n_bad, n_chains words each: one copy brings both down.
+  uint32_t* const d_first = ctx->d_vcres;
+  uint32_t* const d_nbad = ctx->d_vcres + n_chains;
+  uint32_t* const offs = ctx->h_vchains;             // n_chains + 1 words
+  uint32_t* const res = ctx->h_vchains + n_chains + 1;  // 2 x n_chains words
+  offs[0] = 0;
+  for (size_t c = 0; c < n_chains; ++c) offs[c + 1] = offs[c] + lengths[c];
+  HIP_OK(hipMemcpyAsync(ctx->d_voffs, offs, (n_chains + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_OK(hipMemsetAsync(d_first, 0xFF, n_chains * sizeof(uint32_t), ctx->stream));
+  HIP_OK(hipMemsetAsync(d_nbad, 0, n_chains * sizeof(uint32_t), ctx->stream));
+  for (size_t t0 = 0; t0 < total; t0 += kTile) {
+    const size_t tn = std::min(kTile, total - t0);
+    const bool last = t0 + tn == total;
+    const size_t avail = tn + (last ? 0 : 1);
+    HIP_OK(hipMemcpyAsync(ctx->d_vblk, blocks + t0, avail * sizeof(pow_block), hipMemcpyHostToDevice, ctx->stream));
+    if (pow_hooks)
+      if (int rc = pow_hooks->before_launch(ctx)) return rc;
+    HIP_OK(hipEventRecord(ctx->ev0, ctx->stream));
+    HIP_OK(pow_launch_verify_batch((uint32_t)tn, (uint32_t)avail, (uint32_t)t0, diff_bits, ctx->stream, ctx->d_vblk,
+                                   ctx->d_voffs, (uint32_t)n_chains, ctx->d_vstatus, d_first, d_nbad));
+    HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+    if (status) HIP_OK(hipMemcpyAsync(status + t0, ctx->d_vstatus, tn, hipMemcpyDeviceToHost, ctx->stream));
+    if (last)  // the verdicts of all tiles, once
+      HIP_OK(hipMemcpyAsync(res, d_first, 2 * n_chains * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = stream_wait_for(ctx, "chains verify kernel", 100ull * avail)) return rc;  // + 100 ns per block
+    float ms = 0;
+    HIP_OK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    ctx->stats.kernel_ms += ms;
+    ctx->stats.launches += 1;
+    ctx->stats.hashes += tn;
+  }
+  // The fork choice (node.cpp:249: a node moves only to a strictly higher
+  // index, so the first of equal tips stays).
+  bool clean = true;
+  size_t pick = SIZE_MAX;
+  uint32_t pick_index = 0;
+  for (size_t c = 0; c < n_chains; ++c) {
+    const uint32_t bad = res[n_chains + c];
+    if (first_bad) first_bad[c] = bad ? res[c] : lengths[c];
+    if (n_bad) n_bad[c] = bad;
+    if (bad) {
+      clean = false;
+    } else if (lengths[c]) {
+      const uint32_t tip = blocks[offs[c]].index;
+      if (pick == SIZE_MAX || tip > pick_index) {
+        pick = c;
+        pick_index = tip;
+      }
+    }
+  }
+  if (best) *best = pick;
+  return clean ? 1 : 0;
 }
 
 int pow_sweep_device(pow_ctx* ctx, const pow_block* tmpl, uint64_t ctr_start, uint64_t ctr_count,

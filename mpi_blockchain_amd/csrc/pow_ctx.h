@@ -24,6 +24,11 @@ struct PowVerifyRes {
   unsigned int n_bad;      // flagged blocks (atomic add)
 };
 
+// K7 (pow_verify_batch_kernel, pow_verify_batch.hip), one launch per host tile
+// of pow_verify_chains: its verdict is two words per chain, first_bad (atomic
+// min of the position within the chain; ~0 = none) and n_bad (atomic add),
+// reset by the host before the call's first launch.
+
 // What K4, K5 and K6 share (pow_walk_dev.h: the lowest-key search and the seal).
 // The workgroups that count themselves out on one exit word: the word counts
 // them in its low 16 bits and carries their trials (at most 2^40 + one per
@@ -188,6 +193,10 @@ struct pow_ctx {
   size_t verify_cap = 0;             // ... both sized for this many blocks
   PowVerifyRes* d_vres = nullptr;    // K3's result words ...
   PowVerifyRes* h_vres = nullptr;    // ... and their pinned twin: reset value up, result down
+  uint32_t* d_voffs = nullptr;       // pow_verify_chains: the chains' offsets (n_chains + 1 words) ...
+  uint32_t* d_vcres = nullptr;       // ... K7's verdicts: first_bad, then n_bad, a call's n_chains words each ...
+  uint32_t* h_vchains = nullptr;     // ... and the pinned twin of both: the offsets up, the verdicts down
+  size_t vchains_cap = 0;            // ... all sized for this many chains
   PowChainBuf* d_chain = nullptr;    // pow_mine_chain: a batch on the device ...
   PowChainBuf* h_chain = nullptr;    // ... its pinned twin ...
   PowChainSlot* d_cslot = nullptr;   // ... and one slot per workgroup of a launch
@@ -244,6 +253,9 @@ hipError_t pow_launch_hash(uint32_t n, hipStream_t stream, const uint32_t* msgs,
 hipError_t pow_launch_hash_one(hipStream_t stream, const PowMsg& M, PowHashOut* hout, uint32_t seq);
 hipError_t pow_launch_verify(uint32_t n_check, uint32_t n_avail, unsigned diff, hipStream_t stream,
                              const uint32_t* blocks, uint8_t* status, PowVerifyRes* res);
+hipError_t pow_launch_verify_batch(uint32_t n_check, uint32_t n_avail, uint32_t base, unsigned diff,
+                                   hipStream_t stream, const uint32_t* blocks, const uint32_t* offs,
+                                   uint32_t n_chains, uint8_t* status, uint32_t* first_bad, uint32_t* n_bad);
 hipError_t pow_launch_chain(hipStream_t stream, const PowChainLaunch& L, const uint32_t* prev, uint32_t* dst,
                             PowSealCtl* ctl, PowChainSlot* slots);
 hipError_t pow_launch_batch(hipStream_t stream, const PowBatchLaunch& L, uint32_t n_tmpl, const uint32_t* tmpls,

@@ -33,6 +33,15 @@ class VerifyResult:
 
 
 @dataclass
+class VerifyChainsResult:
+    ok: bool              # no block of any chain is flagged (pow_verify_chains returned 1)
+    best: int | None      # the fork choice: the valid chain with the highest tip index (lowest position on a tie); None if none
+    first_bad: list       # per chain: the lowest flagged index within it; its length if none
+    n_bad: list           # per chain: flagged blocks
+    status: list          # per chain: np.uint8 per block, as VerifyResult.status
+
+
+@dataclass
 class MineChainResult:
     blocks: ctypes.Array  # the mined chain, tip first: Block * n_mined
     n_mined: int          # blocks mined
@@ -167,6 +176,41 @@ class GpuMiner:
         rc = check(self.L.pow_verify_chain(self.ctx, arr, n, difficulty, status.ctypes.data_as(ctypes.c_void_p),
                                            ctypes.byref(first), ctypes.byref(bad)), self.L)
         return VerifyResult(rc == 1, first.value, bad.value, status)
+
+    def verify_chains(self, chains, difficulty: int = DEFAULT_DIFFICULTY) -> VerifyChainsResult:
+        """pow_verify_chains over a sequence of chains, each tip first and a
+        list of Blocks or a ctypes ``Block`` array (empty chains allowed):
+        every chain audited on its own in one call, and the fork choice among
+        the valid ones.  The host statements of the result are
+        :func:`mpi_blockchain_amd.block.verify_chains` and
+        :func:`mpi_blockchain_amd.block.best_chain`."""
+        n = len(chains)
+        lens = [len(c) for c in chains]
+        total = sum(lens)
+        arr = (Block * max(total, 1))()
+        at = 0
+        for c, ln in zip(chains, lens):
+            if ln == 0:
+                continue
+            if isinstance(c, ctypes.Array):
+                ctypes.memmove(ctypes.byref(arr, at * ctypes.sizeof(Block)), c, ln * ctypes.sizeof(Block))
+            else:
+                for i, b in enumerate(c):
+                    ctypes.memmove(ctypes.byref(arr, (at + i) * ctypes.sizeof(Block)), ctypes.addressof(b),
+                                   ctypes.sizeof(Block))
+            at += ln
+        lengths = (ctypes.c_uint32 * max(n, 1))(*lens)
+        status = np.zeros(total, dtype=np.uint8)
+        first = (ctypes.c_uint32 * max(n, 1))()
+        bad = (ctypes.c_uint32 * max(n, 1))()
+        best = ctypes.c_size_t()
+        rc = check(self.L.pow_verify_chains(self.ctx, arr, lengths, n, difficulty,
+                                            status.ctypes.data_as(ctypes.c_void_p), first, bad, ctypes.byref(best)),
+                   self.L)
+        ends = np.cumsum([0] + lens)
+        return VerifyChainsResult(rc == 1, None if best.value == ctypes.c_size_t(-1).value else best.value,
+                                  list(first)[:n], list(bad)[:n],
+                                  [status[ends[c]:ends[c + 1]] for c in range(n)])
 
     # ---- mining ----
     def cancel(self) -> None:
@@ -383,5 +427,5 @@ def block_hex(b: Block) -> str:
     return field(b, "block_hash").split(b"\0", 1)[0].decode()
 
 
-__all__ = ["GpuMiner", "DeviceBuffer", "StopBoard", "MineResult", "MineChainResult", "MineBatchResult", "VerifyResult", "refresh_template", "proof_of_work_round", "block_hex",
+__all__ = ["GpuMiner", "DeviceBuffer", "StopBoard", "MineResult", "MineChainResult", "MineBatchResult", "VerifyResult", "VerifyChainsResult", "refresh_template", "proof_of_work_round", "block_hex",
            "nonce_from_counter"]
