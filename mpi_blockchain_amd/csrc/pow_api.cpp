@@ -1,6 +1,9 @@
 // C ABI of the gfx950 miner (include/pow_gpu.h): context, launches, bounded
-// waits, result read-back.  The HIP-free precompute and launch splitting are
-// in pow_host.cpp.
+// waits, result read-back.  The HIP-free precompute, launch splitting and the
+// fused calls' plans are in pow_host.cpp, the holders of the buffers that grow
+// in pow_ctx.h.  What the calls share on the host is here: the timed section
+// (timed_begin, timed_end), the verify calls' tile walk (verify_tiles) and the
+// fused mining calls' frame (FusedCall, mine_linked_host).
 //
 // Replaces the inner loop of proof_of_work (node.cpp:292-308) and
 // block_to_hash (block.cpp:74-77); see include/pow_gpu.h for the mapping of
@@ -98,6 +101,27 @@ int stream_wait_for(pow_ctx* ctx, const char* what, uint64_t extra_ns) {
   return stream_wait(ctx, what, t0, t0 + ctx->watchdog_ns + extra_ns, false);
 }
 
+// The timed section of a call's launches, in two halves.  The opener: the test
+// library's hook and the first event.  The caller then queues its launches,
+// records ev1 and queues its copies down.  The closer: the bounded wait for
+// all of it (the base deadline plus `extra_ns`), then the kernels' time and
+// `launches` into `s`; the trials are the caller's to count.
+int timed_begin(pow_ctx* ctx) {
+  if (pow_hooks)
+    if (int rc = pow_hooks->before_launch(ctx)) return rc;
+  HIP_OK(hipEventRecord(ctx->ev0, ctx->stream));
+  return POW_OK;
+}
+
+int timed_end(pow_ctx* ctx, const char* what, uint64_t extra_ns, uint32_t launches, pow_stats* s) {
+  if (int rc = stream_wait_for(ctx, what, extra_ns)) return rc;
+  float ms = 0;
+  HIP_OK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  s->kernel_ms += ms;
+  s->launches += launches;
+  return POW_OK;
+}
+
 unsigned grid_for(const pow_ctx* ctx, uint32_t n_prefix) {
   // one lane per prefix per chunk; no more workgroups than there are chunks
   const uint64_t want = ((uint64_t)n_prefix + 255) / 256;
@@ -114,9 +138,7 @@ int run_search(pow_ctx* ctx, uint64_t start, uint64_t count, unsigned diff, uint
   if (ctx->sentinel_idle && mode >= 1) L.mode |= POW_LAUNCH_SENTINEL_IDLE;
   if (int rc2 = stage_result(ctx, true, start)) return rc2;
   const unsigned grid = grid_for(ctx, L.n_prefix);
-  if (pow_hooks)
-    if (int rc2 = pow_hooks->before_launch(ctx)) return rc2;
-  HIP_OK(hipEventRecord(ctx->ev0, ctx->stream));
+  if (int rc2 = timed_begin(ctx)) return rc2;
   HIP_OK(pow_launch_search((int)mode, diff > 32 || ctx->force_full, grid, ctx->stream, ctx->d_consts, L, dev_out,
                            ctx->d_res));
   HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
@@ -408,31 +430,7 @@ void pow_destroy(pow_ctx* ctx) {
   (void)hipFree(ctx->d_blob);
   if (ctx->h_blob) (void)hipHostFree(ctx->h_blob);
   (void)hipFree(ctx->d_tail);
-  (void)hipFree(ctx->d_out);
-  (void)hipFree(ctx->d_alt);
-  (void)hipFree(ctx->d_sort_tmp);
-  (void)hipFree(ctx->d_msgs);
-  (void)hipFree(ctx->d_dig);
-  (void)hipFree(ctx->d_vblk);
-  (void)hipFree(ctx->d_vstatus);
-  (void)hipFree(ctx->d_vres);
-  if (ctx->h_vres) (void)hipHostFree(ctx->h_vres);
-  (void)hipFree(ctx->d_voffs);
-  (void)hipFree(ctx->d_vcres);
-  if (ctx->h_vchains) (void)hipHostFree(ctx->h_vchains);
-  (void)hipFree(ctx->d_chain);
-  (void)hipFree(ctx->d_cslot);
-  if (ctx->h_chain) (void)hipHostFree(ctx->h_chain);
-  (void)hipFree(ctx->d_batch);
-  (void)hipFree(ctx->d_brec);
-  (void)hipFree(ctx->d_bslot);
-  if (ctx->h_batch) (void)hipHostFree(ctx->h_batch);
-  if (ctx->h_brec) (void)hipHostFree(ctx->h_brec);
-  (void)hipFree(ctx->d_race);
-  (void)hipFree(ctx->d_rin);
-  (void)hipFree(ctx->d_rslot);
-  if (ctx->h_race) (void)hipHostFree(ctx->h_race);
-  if (ctx->h_rin) (void)hipHostFree(ctx->h_rin);
+  ctx->release_buffers();  // everything made after pow_init
   if (ctx->h_res) (void)hipHostFree(ctx->h_res);
   if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
   if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
@@ -525,32 +523,23 @@ int pow_hash_blocks(pow_ctx* ctx, const pow_block* blocks, size_t n, uint8_t* di
   if (n > (1u << 24)) return fail(POW_EINVAL, "batch too large");
   if (int rc = set_dev(ctx)) return rc;
   if (n == 1) return hash_one(ctx, blocks, digests, hex);  // validation: one block, lowest latency
-  if (n > ctx->hash_cap) {
-    (void)hipFree(ctx->d_msgs);
-    (void)hipFree(ctx->d_dig);
-    ctx->d_msgs = nullptr;
-    ctx->d_dig = nullptr;
-    ctx->hash_cap = 0;
-    HIP_OK(hipMalloc(&ctx->d_msgs, n * 320));
-    HIP_OK(hipMalloc(&ctx->d_dig, n * 32));
-    ctx->hash_cap = n;
-  }
+  RESERVE(ctx->d_msgs, n * 80);
+  RESERVE(ctx->d_dig, n * 8);
   std::vector<uint32_t> words(n * 80);
   for (size_t i = 0; i < n; ++i) {
     uint8_t m[320];
     padded_message(&blocks[i], m);
     for (int k = 0; k < 80; ++k) words[i * 80 + k] = be32(m + 4 * k);
   }
-  HIP_OK(hipMemcpyAsync(ctx->d_msgs, words.data(), n * 320, hipMemcpyHostToDevice, ctx->stream));
-  HIP_OK(hipEventRecord(ctx->ev0, ctx->stream));
-  HIP_OK(pow_launch_hash((uint32_t)n, ctx->stream, ctx->d_msgs, ctx->d_dig));
+  HIP_OK(hipMemcpyAsync(ctx->d_msgs.p, words.data(), n * 320, hipMemcpyHostToDevice, ctx->stream));
+  HIP_OK(hipEventRecord(ctx->ev0, ctx->stream));  // not timed_begin: this launch has never run the test library's hook
+  HIP_OK(pow_launch_hash((uint32_t)n, ctx->stream, ctx->d_msgs.p, ctx->d_dig.p));
   HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
   std::vector<uint32_t> dg(n * 8);
-  HIP_OK(hipMemcpyAsync(dg.data(), ctx->d_dig, n * 32, hipMemcpyDeviceToHost, ctx->stream));
-  if (int rc = stream_wait_for(ctx, "batch hash kernel", 100ull * n)) return rc;  // + 100 ns per block
-  float ms = 0;
-  HIP_OK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-  ctx->stats = pow_stats{ms, 1u, (uint64_t)n};
+  HIP_OK(hipMemcpyAsync(dg.data(), ctx->d_dig.p, n * 32, hipMemcpyDeviceToHost, ctx->stream));
+  pow_stats s{0, 0u, (uint64_t)n};
+  if (int rc = timed_end(ctx, "batch hash kernel", 100ull * n, 1u, &s)) return rc;  // + 100 ns per block
+  ctx->stats = s;
   for (size_t i = 0; i < n; ++i)
     digest_out(&dg[i * 8], digests ? digests + 32 * i : nullptr, hex ? hex + 65 * i : nullptr);
   return POW_OK;
@@ -560,10 +549,59 @@ int pow_hash_block(pow_ctx* ctx, const pow_block* b, uint8_t digest[32], char he
   return pow_hash_blocks(ctx, b, 1, digest, hex);
 }
 
-// K3 over the raw structs: no per-block host work.  Chains longer than a host
-// tile (2^16 blocks) run tile by tile through the same device buffers, each
-// tile carrying the next one's first block as its halo (the parent of its
-// last block), so device memory stays at 36 MB however long the chain is.
+}  // extern "C"
+
+namespace {
+
+// K3 and K7 run over the raw structs, no per-block host work.  Chains longer
+// than a host tile (2^16 blocks) run tile by tile through the same device
+// buffers, each tile carrying the next one's first block as its halo (the
+// parent of its last block), so device memory stays at 36 MB however long the
+// chains are.
+constexpr size_t kVerifyTile = 1u << 16;
+struct VerifyTile {
+  size_t t0, tn;  // blocks [t0, t0 + tn) of the call
+  size_t avail;   // tn + the halo block
+  bool last;      // no halo: the call's blocks end here
+};
+
+// The tile's buffers, shared by both calls, for a tile of `want` blocks.
+int ensure_verify_tile(pow_ctx* ctx, size_t want) {
+  RESERVE(ctx->d_vblk, want + 1);  // + the halo block
+  RESERVE(ctx->d_vstatus, want);
+  return POW_OK;
+}
+
+// The walk over the tiles of `n` blocks.  Per tile: before(t) (what goes up in
+// front of the blocks), the blocks and their halo up, then the timed section
+// around launch(t), which queues the tile's launch, records ev1 and queues the
+// copies down, the status bytes among them; the wait allows 100 ns per block.
+// after(t) reads what came down.  before exists for K3 alone: its result words
+// are reset per tile by a copy that has always gone up in front of the blocks,
+// and the order of the stream's operations is kept.
+template <class Before, class Launch, class After>
+int verify_tiles(pow_ctx* ctx, const pow_block* blocks, size_t n, const char* what, Before before, Launch launch,
+                 After after) {
+  for (size_t t0 = 0; t0 < n; t0 += kVerifyTile) {
+    VerifyTile t{t0, std::min(kVerifyTile, n - t0), 0, false};
+    t.last = t.t0 + t.tn == n;
+    t.avail = t.tn + (t.last ? 0 : 1);
+    if (int rc = before(t)) return rc;
+    HIP_OK(hipMemcpyAsync(ctx->d_vblk.p, blocks + t.t0, t.avail * sizeof(pow_block), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = timed_begin(ctx)) return rc;
+    if (int rc = launch(t)) return rc;
+    if (int rc = timed_end(ctx, what, 100ull * t.avail, 1u, &ctx->stats)) return rc;
+    ctx->stats.hashes += t.tn;
+    after(t);
+  }
+  return POW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// K3, tile by tile: its two result words are reset and read per tile.
 int pow_verify_chain(pow_ctx* ctx, const pow_block* chain, size_t n, unsigned diff_bits, uint8_t* status,
                      size_t* first_bad, size_t* n_bad) {
   if (diff_bits > 256) return fail(POW_EINVAL, "diff_bits %u > 256", diff_bits);
@@ -574,46 +612,34 @@ int pow_verify_chain(pow_ctx* ctx, const pow_block* chain, size_t n, unsigned di
   if (n_bad) *n_bad = 0;
   if (n == 0) return 1;
   if (int rc = set_dev(ctx)) return rc;
-  const size_t kTile = 1u << 16;
-  const size_t want = std::min(n, kTile);
-  if (want > ctx->verify_cap) {
-    (void)hipFree(ctx->d_vblk);
-    (void)hipFree(ctx->d_vstatus);
-    ctx->d_vblk = nullptr;
-    ctx->d_vstatus = nullptr;
-    ctx->verify_cap = 0;
-    HIP_OK(hipMalloc(&ctx->d_vblk, (want + 1) * sizeof(pow_block)));  // + the halo block
-    HIP_OK(hipMalloc(&ctx->d_vstatus, want));
-    ctx->verify_cap = want;
-  }
-  if (!ctx->d_vres) HIP_OK(hipMalloc(&ctx->d_vres, sizeof(PowVerifyRes)));
-  if (!ctx->h_vres) HIP_OK(hipHostMalloc(&ctx->h_vres, sizeof(PowVerifyRes), hipHostMallocDefault));
+  if (int rc = ensure_verify_tile(ctx, std::min(n, kVerifyTile))) return rc;
+  RESERVE(ctx->d_vres, 1);
+  RESERVE(ctx->h_vres, 1);
+  PowVerifyRes* const d_res = ctx->d_vres.p;
+  PowVerifyRes* const h_res = ctx->h_vres.p;
   size_t lowest = n, bad = 0;
-  for (size_t t0 = 0; t0 < n; t0 += kTile) {
-    const size_t tn = std::min(kTile, n - t0);
-    const size_t avail = tn + (t0 + tn < n ? 1 : 0);
-    *ctx->h_vres = PowVerifyRes{~0u, 0u};
-    HIP_OK(hipMemcpyAsync(ctx->d_vres, ctx->h_vres, sizeof(PowVerifyRes), hipMemcpyHostToDevice, ctx->stream));
-    HIP_OK(hipMemcpyAsync(ctx->d_vblk, chain + t0, avail * sizeof(pow_block), hipMemcpyHostToDevice, ctx->stream));
-    if (pow_hooks)
-      if (int rc = pow_hooks->before_launch(ctx)) return rc;
-    HIP_OK(hipEventRecord(ctx->ev0, ctx->stream));
-    HIP_OK(pow_launch_verify((uint32_t)tn, (uint32_t)avail, diff_bits, ctx->stream, ctx->d_vblk, ctx->d_vstatus,
-                             ctx->d_vres));
-    HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_OK(hipMemcpyAsync(ctx->h_vres, ctx->d_vres, sizeof(PowVerifyRes), hipMemcpyDeviceToHost, ctx->stream));
-    if (status) HIP_OK(hipMemcpyAsync(status + t0, ctx->d_vstatus, tn, hipMemcpyDeviceToHost, ctx->stream));
-    if (int rc = stream_wait_for(ctx, "chain verify kernel", 100ull * avail)) return rc;  // + 100 ns per block
-    float ms = 0;
-    HIP_OK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    ctx->stats.kernel_ms += ms;
-    ctx->stats.launches += 1;
-    ctx->stats.hashes += tn;
-    if (ctx->h_vres->n_bad) {
-      lowest = std::min(lowest, t0 + ctx->h_vres->first_bad);
-      bad += ctx->h_vres->n_bad;
-    }
-  }
+  const int rc = verify_tiles(
+      ctx, chain, n, "chain verify kernel",
+      [&](const VerifyTile&) -> int {
+        *h_res = PowVerifyRes{~0u, 0u};
+        HIP_OK(hipMemcpyAsync(d_res, h_res, sizeof(PowVerifyRes), hipMemcpyHostToDevice, ctx->stream));
+        return POW_OK;
+      },
+      [&](const VerifyTile& t) -> int {
+        HIP_OK(pow_launch_verify((uint32_t)t.tn, (uint32_t)t.avail, diff_bits, ctx->stream,
+                                 (const uint32_t*)ctx->d_vblk.p, ctx->d_vstatus.p, d_res));
+        HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+        HIP_OK(hipMemcpyAsync(h_res, d_res, sizeof(PowVerifyRes), hipMemcpyDeviceToHost, ctx->stream));
+        if (status) HIP_OK(hipMemcpyAsync(status + t.t0, ctx->d_vstatus.p, t.tn, hipMemcpyDeviceToHost, ctx->stream));
+        return POW_OK;
+      },
+      [&](const VerifyTile& t) {
+        if (h_res->n_bad) {
+          lowest = std::min(lowest, t.t0 + h_res->first_bad);
+          bad += h_res->n_bad;
+        }
+      });
+  if (rc) return rc;
   if (first_bad) *first_bad = lowest;
   if (n_bad) *n_bad = bad;
   return bad == 0 ? 1 : 0;
@@ -621,7 +647,7 @@ int pow_verify_chain(pow_ctx* ctx, const pow_block* chain, size_t n, unsigned di
 
 // K7 over the concatenated raw structs: the host work is per chain (the
 // offsets up, two verdict words per chain down, the fork choice), never per
-// block.  Tiles, halo and device buffers are pow_verify_chain's.
+// block.  Its verdict words are reset once and come down with the last tile.
 int pow_verify_chains(pow_ctx* ctx, const pow_block* blocks, const uint32_t* lengths, size_t n_chains,
                       unsigned diff_bits, uint8_t* status, uint32_t* first_bad, uint32_t* n_bad, size_t* best) {
   if (diff_bits > 256) return fail(POW_EINVAL, "diff_bits %u > 256", diff_bits);
@@ -642,62 +668,34 @@ int pow_verify_chains(pow_ctx* ctx, const pow_block* blocks, const uint32_t* len
     return 1;
   }
   if (int rc = set_dev(ctx)) return rc;
-  const size_t kTile = 1u << 16;
-  const size_t want = std::min(total, kTile);
-  if (want > ctx->verify_cap) {
-    (void)hipFree(ctx->d_vblk);
-    (void)hipFree(ctx->d_vstatus);
-    ctx->d_vblk = nullptr;
-    ctx->d_vstatus = nullptr;
-    ctx->verify_cap = 0;
-    HIP_OK(hipMalloc(&ctx->d_vblk, (want + 1) * sizeof(pow_block)));  // + the halo block
-    HIP_OK(hipMalloc(&ctx->d_vstatus, want));
-    ctx->verify_cap = want;
-  }
-  if (n_chains > ctx->vchains_cap) {
-    (void)hipFree(ctx->d_voffs);
-    (void)hipFree(ctx->d_vcres);
-    if (ctx->h_vchains) (void)hipHostFree(ctx->h_vchains);
-    ctx->d_voffs = nullptr;
-    ctx->d_vcres = nullptr;
-    ctx->h_vchains = nullptr;
-    ctx->vchains_cap = 0;
-    HIP_OK(hipMalloc(&ctx->d_voffs, (n_chains + 1) * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&ctx->d_vcres, 2 * n_chains * sizeof(uint32_t)));
-    HIP_OK(hipHostMalloc(&ctx->h_vchains, (3 * n_chains + 1) * sizeof(uint32_t), hipHostMallocDefault));
-    ctx->vchains_cap = n_chains;
-  }
+  if (int rc = ensure_verify_tile(ctx, std::min(total, kVerifyTile))) return rc;
+  RESERVE(ctx->d_voffs, n_chains + 1);
+  RESERVE(ctx->d_vcres, 2 * n_chains);
+  RESERVE(ctx->h_vchains, 3 * n_chains + 1);
   // first_bad, then n_bad, n_chains words each: one copy brings both down.
-  uint32_t* const d_first = ctx->d_vcres;
-  uint32_t* const d_nbad = ctx->d_vcres + n_chains;
-  uint32_t* const offs = ctx->h_vchains;             // n_chains + 1 words
-  uint32_t* const res = ctx->h_vchains + n_chains + 1;  // 2 x n_chains words
+  uint32_t* const d_first = ctx->d_vcres.p;
+  uint32_t* const d_nbad = ctx->d_vcres.p + n_chains;
+  uint32_t* const offs = ctx->h_vchains.p;                // n_chains + 1 words
+  uint32_t* const res = ctx->h_vchains.p + n_chains + 1;  // 2 x n_chains words
   offs[0] = 0;
   for (size_t c = 0; c < n_chains; ++c) offs[c + 1] = offs[c] + lengths[c];
-  HIP_OK(hipMemcpyAsync(ctx->d_voffs, offs, (n_chains + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_OK(hipMemcpyAsync(ctx->d_voffs.p, offs, (n_chains + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
   HIP_OK(hipMemsetAsync(d_first, 0xFF, n_chains * sizeof(uint32_t), ctx->stream));
   HIP_OK(hipMemsetAsync(d_nbad, 0, n_chains * sizeof(uint32_t), ctx->stream));
-  for (size_t t0 = 0; t0 < total; t0 += kTile) {
-    const size_t tn = std::min(kTile, total - t0);
-    const bool last = t0 + tn == total;
-    const size_t avail = tn + (last ? 0 : 1);
-    HIP_OK(hipMemcpyAsync(ctx->d_vblk, blocks + t0, avail * sizeof(pow_block), hipMemcpyHostToDevice, ctx->stream));
-    if (pow_hooks)
-      if (int rc = pow_hooks->before_launch(ctx)) return rc;
-    HIP_OK(hipEventRecord(ctx->ev0, ctx->stream));
-    HIP_OK(pow_launch_verify_batch((uint32_t)tn, (uint32_t)avail, (uint32_t)t0, diff_bits, ctx->stream, ctx->d_vblk,
-                                   ctx->d_voffs, (uint32_t)n_chains, ctx->d_vstatus, d_first, d_nbad));
-    HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
-    if (status) HIP_OK(hipMemcpyAsync(status + t0, ctx->d_vstatus, tn, hipMemcpyDeviceToHost, ctx->stream));
-    if (last)  // the verdicts of all tiles, once
-      HIP_OK(hipMemcpyAsync(res, d_first, 2 * n_chains * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (int rc = stream_wait_for(ctx, "chains verify kernel", 100ull * avail)) return rc;  // + 100 ns per block
-    float ms = 0;
-    HIP_OK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    ctx->stats.kernel_ms += ms;
-    ctx->stats.launches += 1;
-    ctx->stats.hashes += tn;
-  }
+  const int rc = verify_tiles(
+      ctx, blocks, total, "chains verify kernel", [](const VerifyTile&) -> int { return POW_OK; },
+      [&](const VerifyTile& t) -> int {
+        HIP_OK(pow_launch_verify_batch((uint32_t)t.tn, (uint32_t)t.avail, (uint32_t)t.t0, diff_bits, ctx->stream,
+                                       (const uint32_t*)ctx->d_vblk.p, ctx->d_voffs.p, (uint32_t)n_chains,
+                                       ctx->d_vstatus.p, d_first, d_nbad));
+        HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+        if (status) HIP_OK(hipMemcpyAsync(status + t.t0, ctx->d_vstatus.p, t.tn, hipMemcpyDeviceToHost, ctx->stream));
+        if (t.last)  // the verdicts of all tiles, once
+          HIP_OK(hipMemcpyAsync(res, d_first, 2 * n_chains * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        return POW_OK;
+      },
+      [](const VerifyTile&) {});
+  if (rc) return rc;
   // The fork choice (node.cpp:249: a node moves only to a strictly higher
   // index, so the first of equal tips stays).
   bool clean = true;
@@ -758,33 +756,26 @@ int pow_sweep(pow_ctx* ctx, const pow_block* tmpl, uint64_t ctr_start, uint64_t 
   if (!ctx || !n_found) return fail(POW_EINVAL, "null");
   if (cap && !out_ctrs) return fail(POW_EINVAL, "cap without buffer");
   if (int rc = set_dev(ctx)) return rc;
-  if (cap > ctx->out_cap) {
-    (void)hipFree(ctx->d_out);
-    (void)hipFree(ctx->d_alt);
-    (void)hipFree(ctx->d_sort_tmp);
-    ctx->d_out = ctx->d_alt = nullptr;
-    ctx->d_sort_tmp = nullptr;
-    ctx->out_cap = ctx->sort_tmp_bytes = 0;
-    HIP_OK(hipMalloc(&ctx->d_out, cap * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&ctx->d_alt, cap * sizeof(uint32_t)));
-    size_t tb = 0;
-    HIP_OK(pow_sort_u32(nullptr, &tb, ctx->d_out, ctx->d_alt, (uint32_t)cap, nullptr, ctx->stream));
-    HIP_OK(hipMalloc(&ctx->d_sort_tmp, tb ? tb : 1));
-    ctx->sort_tmp_bytes = tb;
-    ctx->out_cap = cap;
+  // The twin is reserved last: its capacity vouches for the list and the sort's scratch too.
+  if (cap > ctx->d_alt.cap) {
+    RESERVE(ctx->d_out, cap);
+    size_t tb = 0;  // the size query reads no key
+    HIP_OK(pow_sort_u32(nullptr, &tb, ctx->d_out.p, ctx->d_out.p, (uint32_t)cap, nullptr, ctx->stream));
+    RESERVE(ctx->d_sort_tmp, tb ? tb : 1);
+    RESERVE(ctx->d_alt, cap);
   }
   size_t n = 0;
   uint64_t mn = 0;
-  int rc = pow_sweep_device(ctx, tmpl, ctr_start, ctr_count, diff_bits, cap ? ctx->d_out : nullptr,
+  int rc = pow_sweep_device(ctx, tmpl, ctr_start, ctr_count, diff_bits, cap ? ctx->d_out.p : nullptr,
                             cap, &n, &mn);
   if (rc) return rc;
   *n_found = n;
   const size_t got = std::min(n, cap);
   if (got) {
     // ascending order: device radix sort (the kernel appends in completion order)
-    uint32_t* sorted = ctx->d_out;
-    size_t tb = ctx->sort_tmp_bytes;
-    HIP_OK(pow_sort_u32(ctx->d_sort_tmp, &tb, ctx->d_out, ctx->d_alt, (uint32_t)got, &sorted, ctx->stream));
+    uint32_t* sorted = ctx->d_out.p;
+    size_t tb = ctx->d_sort_tmp.cap;
+    HIP_OK(pow_sort_u32(ctx->d_sort_tmp.p, &tb, ctx->d_out.p, ctx->d_alt.p, (uint32_t)got, &sorted, ctx->stream));
     HIP_OK(hipMemcpyAsync(out_ctrs, sorted, got * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (int rc = stream_wait_for(ctx, "sweep sort and copy", 4ull * got)) return rc;  // + 1 ns per byte
   }
@@ -950,18 +941,33 @@ static_assert(offsetof(PowChainBuf, ctl) == sizeof(pow_block) &&
 
 // The buffers of the fused path, made at the first call that needs them.
 int ensure_chain(pow_ctx* ctx) {
-  if (!ctx->d_chain) HIP_OK(hipMalloc(&ctx->d_chain, sizeof(PowChainBuf)));
-  if (!ctx->h_chain) HIP_OK(hipHostMalloc(&ctx->h_chain, sizeof(PowChainBuf), hipHostMallocDefault));
-  if (!ctx->d_cslot) {
-    // One workgroup (four waves, one per SIMD) per CU at most: a trial is one
-    // dependent chain that keeps its SIMD's VALU busy alone, so further waves
-    // only stretch every trial.
-    const unsigned cap = (unsigned)std::max(1, ctx->cu_count);
-    HIP_OK(hipMalloc(&ctx->d_cslot, (size_t)cap * sizeof(PowChainSlot)));
-    ctx->chain_grid_max = cap;
-  }
+  RESERVE(ctx->d_chain, 1);
+  RESERVE(ctx->h_chain, 1);
+  // One workgroup (four waves, one per SIMD) per CU at most: a trial is one
+  // dependent chain that keeps its SIMD's VALU busy alone, so further waves
+  // only stretch every trial.
+  RESERVE(ctx->d_cslot, (size_t)std::max(1, ctx->cu_count));
   return POW_OK;
 }
+
+// The frame of pow_mine_chain, pow_mine_batch and pow_mine_race: it opens the
+// call (the stats and the two optional outputs zeroed), keeps the running
+// stats and the count of finished items (blocks, templates, heights), and
+// every return of the call that reports them goes through finish.
+struct FusedCall {
+  pow_ctx* ctx;
+  size_t* n_done;         // may be null
+  uint64_t* hashes_done;  // may be null
+  pow_stats total{};
+  size_t done = 0;
+  FusedCall(pow_ctx* c, size_t* n, uint64_t* h) : ctx(c), n_done(n), hashes_done(h) { finish(0); }  // all zero
+  int finish(int rc) {
+    ctx->stats = total;
+    if (n_done) *n_done = done;
+    if (hashes_done) *hashes_done = total.hashes;
+    return rc;
+  }
+};
 
 // The template refresh of node.cpp:292-299 on the host (the host loop's).
 void refresh(pow_block* t, const pow_block* last, uint32_t owner, unsigned diff, uint64_t created_at) {
@@ -971,6 +977,48 @@ void refresh(pow_block* t, const pow_block* last, uint32_t owner, unsigned diff,
   t->difficulty = diff;
   t->created_at = created_at;
   memcpy(t->previous_block_hash, last->block_hash, POW_HASH_SIZE);  // all 256 bytes (trap T5)
+}
+
+// The host loop of pow_mine_chain (R = 1) and pow_mine_race: n linked blocks
+// through refresh + pow_mine, each height's R rivals one by one under the best
+// counter so far.  A height nobody solves, or a cancel, ends it.
+int mine_linked_host(FusedCall& f, const pow_block* parent, size_t n, unsigned diff_bits, const uint32_t* owners,
+                     size_t R, const uint64_t* created_at, uint64_t now, uint64_t ctr_start, uint64_t ctr_count,
+                     const volatile uint32_t* cancel_word, uint32_t epoch, pow_block* out, uint32_t* winners,
+                     uint64_t* found_ctr) {
+  pow_ctx* const ctx = f.ctx;
+  pow_block last = *parent;
+  while (f.done < n && !cancel_moved(cancel_word, epoch)) {
+    pow_block best;
+    uint64_t best_ctr = UINT64_MAX;
+    uint32_t best_r = 0;
+    bool cancelled = false;
+    for (size_t r = 0; r < R; ++r) {
+      // A later position loses a tie: it searches only below the best counter so far.
+      const uint64_t window = best_ctr == UINT64_MAX ? ctr_count : best_ctr - ctr_start;
+      if (window == 0) break;  // ctr_start itself solved: nothing lies below it
+      pow_block tmpl, blk;
+      uint64_t ctr = UINT64_MAX;
+      refresh(&tmpl, &last, owners[r], diff_bits, created_at ? created_at[f.done * R + r] : now);
+      const int rc = mine_impl(ctx, &tmpl, ctr_start, window, diff_bits, cancel_word, epoch, &blk, &ctr, nullptr, false);
+      add_stats(&f.total, ctx->stats);
+      if (rc < 0) return f.finish(rc);
+      if (rc == 1) {
+        best = blk;
+        best_ctr = ctr;
+        best_r = (uint32_t)r;
+      } else if (cancel_moved(cancel_word, epoch)) {  // this rival's window was not searched to its end
+        cancelled = true;
+        break;
+      }
+    }
+    if (cancelled || best_ctr == UINT64_MAX) break;
+    out[n - 1 - f.done] = last = best;
+    if (winners) winners[n - 1 - f.done] = best_r;
+    if (found_ctr) found_ctr[n - 1 - f.done] = best_ctr;
+    ++f.done;
+  }
+  return f.finish(f.done == n ? 1 : 0);
 }
 
 }  // namespace
@@ -984,93 +1032,55 @@ int pow_mine_chain(pow_ctx* ctx, const pow_block* parent, size_t n, unsigned dif
   if (int rc = check_fused_args(diff_bits, ctr_start, ctr_count, n, "chain", "blocks")) return rc;
   if (!ctx || ((!parent || !out) && n)) return fail(POW_EINVAL, "null");
   if (ctx->board) return fail(POW_EINVAL, "pow_mine_chain does not run on a context bound to a stop board");
-  ctx->stats = pow_stats{};
-  if (n_mined) *n_mined = 0;
-  if (hashes_done) *hashes_done = 0;
+  FusedCall f(ctx, n_mined, hashes_done);
   if (n == 0) return 1;
   if (int rc = set_dev(ctx)) return rc;
   const uint64_t now = created_at ? 0 : (uint64_t)time(nullptr);
-  pow_stats total{};
-  size_t done = 0;
-  auto finish = [&](int rc) {
-    ctx->stats = total;
-    if (n_mined) *n_mined = done;
-    if (hashes_done) *hashes_done = total.hashes;
-    return rc;
-  };
-  if (diff_bits > 32 || (int)diff_bits > ctx->chain_fused_max) {
-    pow_block last = *parent;
-    while (done < n && !cancel_moved(cancel_word, epoch)) {
-      pow_block tmpl, blk;
-      refresh(&tmpl, &last, owner, diff_bits, created_at ? created_at[done] : now);
-      const int rc = mine_impl(ctx, &tmpl, ctr_start, ctr_count, diff_bits, cancel_word, epoch, &blk, nullptr, nullptr,
-                               false);
-      add_stats(&total, ctx->stats);
-      if (rc < 0) return finish(rc);
-      if (rc == 0) break;
-      out[n - 1 - done] = last = blk;
-      ++done;
-    }
-    return finish(done == n ? 1 : 0);
-  }
-  if (cancel_moved(cancel_word, epoch)) return finish(0);
+  if (diff_bits > 32 || (int)diff_bits > ctx->chain_fused_max)
+    return mine_linked_host(f, parent, n, diff_bits, &owner, 1, created_at, now, ctr_start, ctr_count, cancel_word, epoch,
+                            out, nullptr, nullptr);
+  if (cancel_moved(cancel_word, epoch)) return f.finish(0);
   if (int rc = ensure_chain(ctx)) return rc;
+  const PowChainPlan plan =
+      pow_chain_plan(diff_bits, ctr_count, (uint32_t)ctx->d_cslot.cap, ctx->chain_lanes_log2, ctx->chain_batch);
   PowChainLaunch L;
   memset(&L, 0, sizeof L);
   fill_head(&L.w, ctr_start, ctr_count, diff_bits);
   L.owner = owner;
   L.diff = diff_bits;
-  // The grid follows the difficulty: lanes for four times the expected 2^d
-  // trials (a block then costs one trial's latency but for 1 in e^4; at d = 9
-  // and 13 two times measured 1.4 and 0.6 us per block slower, eight times 0.3
-  // and 2.2 us: more workgroups to start and to count out), no more than the
-  // window has counters or the chip takes at one wave per SIMD; the lanes of a
-  // full grid walk on through the window.
-  {
-    const uint64_t lanes = std::min<uint64_t>(1ull << (diff_bits + ctx->chain_lanes_log2), ctr_count);
-    L.nwg = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((lanes + 255) / 256, ctx->chain_grid_max));
-  }
-  // A batch is about 2^26 expected trials (a handful of ms: the cancel latency).
-  const size_t batch =
-      ctx->chain_batch ? std::min<size_t>(ctx->chain_batch, POW_CHAIN_MAX_BATCH)
-                       : std::max<size_t>(1, std::min<size_t>(POW_CHAIN_MAX_BATCH, (size_t)1 << (26 - std::min(diff_bits, 26u))));
-  PowChainBuf* const H = ctx->h_chain;
-  PowChainBuf* const D = ctx->d_chain;
+  L.nwg = plan.nwg;
+  PowChainBuf* const H = ctx->h_chain.p;
+  PowChainBuf* const D = ctx->d_chain.p;
   H->parent = *parent;
-  while (done < n) {
-    if (cancel_moved(cancel_word, epoch)) return finish(0);
-    const size_t nb = std::min(batch, n - done);
+  while (f.done < n) {
+    if (cancel_moved(cancel_word, epoch)) return f.finish(0);
+    const size_t nb = std::min<size_t>(plan.batch, n - f.done);
     memset(&H->ctl, 0, sizeof H->ctl);
     H->ctl.min_key = ~0ull;
     HIP_OK(hipMemcpyAsync(D, H, offsetof(PowChainBuf, blk), hipMemcpyHostToDevice, ctx->stream));
-    if (pow_hooks)
-      if (int rc = pow_hooks->before_launch(ctx)) return rc;
-    HIP_OK(hipEventRecord(ctx->ev0, ctx->stream));
+    if (int rc = timed_begin(ctx)) return rc;
     for (size_t j = 0; j < nb; ++j) {
-      L.created_at = created_at ? created_at[done + j] : now;
+      L.created_at = created_at ? created_at[f.done + j] : now;
       const pow_block* const prev = j == 0 ? &D->parent : &D->blk[nb - j];
       HIP_OK(pow_launch_chain(ctx->stream, L, (const uint32_t*)prev, (uint32_t*)&D->blk[nb - 1 - j], &D->ctl,
-                              ctx->d_cslot));
+                              ctx->d_cslot.p));
     }
     HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
     HIP_OK(hipMemcpyAsync(&H->ctl, &D->ctl, sizeof(PowSealCtl) + nb * sizeof(pow_block), hipMemcpyDeviceToHost,
                           ctx->stream));
-    if (int rc = stream_wait_for(ctx, "chain mining batch", 2ull * nb * ctr_count)) return rc;  // 2 ns per counter
-    float ms = 0;
-    HIP_OK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    total.kernel_ms += ms;
-    total.launches += (uint32_t)nb;
-    total.hashes += H->ctl.hashes;
+    // 2 ns per counter
+    if (int rc = timed_end(ctx, "chain mining batch", 2ull * nb * ctr_count, (uint32_t)nb, &f.total)) return rc;
+    f.total.hashes += H->ctl.hashes;
     const size_t m = H->ctl.n_done;
     if (m > nb || (m < nb && !H->ctl.stop)) return fail(POW_EHIP, "chain mining batch: %zu of %zu blocks and no stop word", m, nb);
     // Block done + j is blk[nb - 1 - j] and goes to out[n - 1 - done - j]:
     // the m sealed ones are the batch's upper m slots, contiguous in both.
-    if (m) memcpy(out + (n - done - m), &H->blk[nb - m], m * sizeof(pow_block));
-    done += m;
-    if (m < nb) return finish(0);  // a window without a solution
-    H->parent = H->blk[0];         // the tip: the next batch's parent
+    if (m) memcpy(out + (n - f.done - m), &H->blk[nb - m], m * sizeof(pow_block));
+    f.done += m;
+    if (m < nb) return f.finish(0);  // a window without a solution
+    H->parent = H->blk[0];           // the tip: the next batch's parent
   }
-  return finish(1);
+  return f.finish(1);
 }
 
 namespace {
@@ -1081,12 +1091,11 @@ namespace {
 // templates a call has, and 10.1 MB of pinned host memory.
 int ensure_batch(pow_ctx* ctx) {
   const size_t tile_bytes = (size_t)POW_BATCH_MAX_TILE * (sizeof(PowBatchCtl) + sizeof(pow_block));
-  const size_t rec_bytes = (size_t)POW_BATCH_MAX_TILE * sizeof(PowBatchRec);
-  if (!ctx->d_batch) HIP_OK(hipMalloc(&ctx->d_batch, tile_bytes));
-  if (!ctx->h_batch) HIP_OK(hipHostMalloc(&ctx->h_batch, tile_bytes, hipHostMallocDefault));
-  if (!ctx->d_brec) HIP_OK(hipMalloc(&ctx->d_brec, rec_bytes));
-  if (!ctx->h_brec) HIP_OK(hipHostMalloc(&ctx->h_brec, rec_bytes, hipHostMallocDefault));
-  if (!ctx->d_bslot) HIP_OK(hipMalloc(&ctx->d_bslot, (size_t)POW_BATCH_MAX_WG * sizeof(PowChainSlot)));
+  RESERVE(ctx->d_batch, tile_bytes);
+  RESERVE(ctx->h_batch, tile_bytes);
+  RESERVE(ctx->d_brec, POW_BATCH_MAX_TILE);
+  RESERVE(ctx->h_brec, POW_BATCH_MAX_TILE);
+  RESERVE(ctx->d_bslot, POW_BATCH_MAX_WG);
   return POW_OK;
 }
 
@@ -1100,90 +1109,52 @@ int pow_mine_batch(pow_ctx* ctx, const pow_block* tmpls, size_t n, unsigned diff
   if (int rc = check_fused_args(diff_bits, ctr_start, ctr_count, n, "batch", "templates")) return rc;
   if (!ctx || ((!tmpls || !out) && n)) return fail(POW_EINVAL, "null");
   if (ctx->board) return fail(POW_EINVAL, "pow_mine_batch does not run on a context bound to a stop board");
-  ctx->stats = pow_stats{};
-  if (n_solved) *n_solved = 0;
-  if (hashes_done) *hashes_done = 0;
+  FusedCall f(ctx, n_solved, hashes_done);  // done = the templates solved
   if (found_ctr) std::fill(found_ctr, found_ctr + n, UINT64_MAX);
   if (n == 0) return 1;
   if (int rc = set_dev(ctx)) return rc;
-  pow_stats total{};
-  size_t solved = 0;
-  auto finish = [&](int rc) {
-    ctx->stats = total;
-    if (n_solved) *n_solved = solved;
-    if (hashes_done) *hashes_done = total.hashes;
-    return rc;
-  };
   if (n == 1 || diff_bits > 32 || (int)diff_bits > ctx->batch_fused_max) {
     for (size_t i = 0; i < n && !cancel_moved(cancel_word, epoch); ++i) {
       uint64_t ctr = UINT64_MAX;
       const int rc = mine_impl(ctx, &tmpls[i], ctr_start, ctr_count, diff_bits, cancel_word, epoch, &out[i], &ctr, nullptr,
                                false);
-      add_stats(&total, ctx->stats);
-      if (rc < 0) return finish(rc);
+      add_stats(&f.total, ctx->stats);
+      if (rc < 0) return f.finish(rc);
       if (rc == 1) {
         if (found_ctr) found_ctr[i] = ctr;
-        ++solved;
+        ++f.done;
       }
     }
-    return finish(solved == n ? 1 : 0);
+    return f.finish(f.done == n ? 1 : 0);
   }
-  if (cancel_moved(cancel_word, epoch)) return finish(0);
+  if (cancel_moved(cancel_word, epoch)) return f.finish(0);
   if (int rc = ensure_batch(ctx)) return rc;
+  const PowBatchPlan plan = pow_batch_plan(diff_bits, n, ctr_count, (uint32_t)std::max(1, ctx->cu_count),
+                                           ctx->batch_lanes_log2, ctx->batch_tile);
   PowBatchLaunch L;
   memset(&L, 0, sizeof L);
   fill_head(&L.w, ctr_start, ctr_count, diff_bits);
-  // Templates per launch: about 2^26 expected trials (a handful of ms: the
-  // cancel latency), a grid of at most 2^16 workgroups, and windows of at most
-  // 2^38 counters in all, which keeps the watchdog's 2 ns per counter a bound
-  // worth having (550 s, K4's own worst case).
-  size_t tile = ctx->batch_tile ? ctx->batch_tile : (size_t)((1ull << 26) / std::min<uint64_t>(1ull << std::min(diff_bits, 26u), ctr_count));
-  tile = std::min<size_t>(tile, (size_t)((1ull << 38) / ctr_count));
-  tile = std::max<size_t>(1, std::min<size_t>(tile, POW_BATCH_MAX_TILE));
-  {
-    // Lanes for 2^lanes_log2 times the expected 2^d trials of a template: no
-    // more than the window has counters or the chip takes at one wave per SIMD.
-    // Four times, as K4, while the launch leaves CUs idle (a template then costs
-    // one trial's latency but for 1 in e^4); every lane computes at least one
-    // trial, so once the launch's workgroups exceed one per CU the surplus
-    // lanes are only surplus work: twice, then once the expected trials
-    // (d = 13, 64 templates: 8.8 us per template at four times, 4.1 at once).
-    const uint64_t cus = (uint64_t)std::max(1, ctx->cu_count);
-    const auto nwg_for = [&](unsigned lanes_log2) {
-      const uint64_t lanes = std::min<uint64_t>(1ull << (diff_bits + lanes_log2), ctr_count);
-      return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((lanes + 255) / 256, cus));
-    };
-    unsigned lanes_log2 = ctx->batch_lanes_log2 < 0 ? 2u : (unsigned)ctx->batch_lanes_log2;
-    if (ctx->batch_lanes_log2 < 0)
-      while (lanes_log2 > 0 && std::min(tile, n) * nwg_for(lanes_log2) > cus) --lanes_log2;
-    L.nwg_t = nwg_for(lanes_log2);
-  }
-  tile = std::max<size_t>(1, std::min<size_t>(tile, POW_BATCH_MAX_WG / L.nwg_t));
-  for (size_t t0 = 0; t0 < n; t0 += tile) {
-    if (cancel_moved(cancel_word, epoch)) return finish(0);
-    const size_t tn = std::min(tile, n - t0);
+  L.nwg_t = plan.nwg_t;
+  uint8_t* const h_tile = ctx->h_batch.p;
+  uint8_t* const d_tile = ctx->d_batch.p;
+  for (size_t t0 = 0; t0 < n; t0 += plan.tile) {
+    if (cancel_moved(cancel_word, epoch)) return f.finish(0);
+    const size_t tn = std::min<size_t>(plan.tile, n - t0);
     // The tile as it goes up: tn control words, then the tn raw structs.
     const size_t ctl_bytes = tn * sizeof(PowBatchCtl);
-    PowBatchCtl* const hctl = (PowBatchCtl*)ctx->h_batch;
+    PowBatchCtl* const hctl = (PowBatchCtl*)h_tile;
     for (size_t i = 0; i < tn; ++i) hctl[i] = PowBatchCtl{~0ull, 0ull};
-    memcpy(ctx->h_batch + ctl_bytes, tmpls + t0, tn * sizeof(pow_block));
-    HIP_OK(hipMemcpyAsync(ctx->d_batch, ctx->h_batch, ctl_bytes + tn * sizeof(pow_block), hipMemcpyHostToDevice,
-                          ctx->stream));
-    if (pow_hooks)
-      if (int rc = pow_hooks->before_launch(ctx)) return rc;
-    HIP_OK(hipEventRecord(ctx->ev0, ctx->stream));
-    HIP_OK(pow_launch_batch(ctx->stream, L, (uint32_t)tn, (const uint32_t*)(ctx->d_batch + ctl_bytes),
-                            (PowBatchCtl*)ctx->d_batch, ctx->d_bslot, ctx->d_brec));
+    memcpy(h_tile + ctl_bytes, tmpls + t0, tn * sizeof(pow_block));
+    HIP_OK(hipMemcpyAsync(d_tile, h_tile, ctl_bytes + tn * sizeof(pow_block), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = timed_begin(ctx)) return rc;
+    HIP_OK(pow_launch_batch(ctx->stream, L, (uint32_t)tn, (const uint32_t*)(d_tile + ctl_bytes), (PowBatchCtl*)d_tile,
+                            ctx->d_bslot.p, ctx->d_brec.p));
     HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_OK(hipMemcpyAsync(ctx->h_brec, ctx->d_brec, tn * sizeof(PowBatchRec), hipMemcpyDeviceToHost, ctx->stream));
-    if (int rc = stream_wait_for(ctx, "batch mining tile", 2ull * tn * ctr_count)) return rc;  // 2 ns per counter
-    float ms = 0;
-    HIP_OK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    total.kernel_ms += ms;
-    total.launches += 1;
+    HIP_OK(hipMemcpyAsync(ctx->h_brec.p, ctx->d_brec.p, tn * sizeof(PowBatchRec), hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = timed_end(ctx, "batch mining tile", 2ull * tn * ctr_count, 1u, &f.total)) return rc;  // 2 ns per counter
     for (size_t i = 0; i < tn; ++i) {
-      const PowBatchRec& r = ctx->h_brec[i];
-      total.hashes += r.trials;
+      const PowBatchRec& r = ctx->h_brec.p[i];
+      f.total.hashes += r.trials;
       if (r.rel == ~0ull) continue;
       if (r.rel >= ctr_count) return fail(POW_EHIP, "batch mining tile: template %zu reports counter %llu outside its window", t0 + i, (unsigned long long)r.rel);
       pow_block* const o = &out[t0 + i];
@@ -1193,10 +1164,10 @@ int pow_mine_batch(pow_ctx* ctx, const pow_block* tmpls, size_t n, unsigned diff
       digest_out(r.digest, nullptr, hx);
       memcpy(o->block_hash, hx, 65);  // strcpy semantics (node.cpp:318)
       if (found_ctr) found_ctr[t0 + i] = ctr_start + r.rel;
-      ++solved;
+      ++f.done;
     }
   }
-  return finish(solved == n ? 1 : 0);
+  return f.finish(f.done == n ? 1 : 0);
 }
 
 namespace {
@@ -1209,16 +1180,12 @@ static_assert(offsetof(PowRaceBuf, ctl) == sizeof(pow_block) &&
 // The buffers of pow_mine_race's fused path, made at the first call that needs
 // them: about 180 KB of device memory (170 KB of it pinned too), one slot per workgroup.
 int ensure_race(pow_ctx* ctx) {
-  if (!ctx->d_race) HIP_OK(hipMalloc(&ctx->d_race, sizeof(PowRaceBuf)));
-  if (!ctx->h_race) HIP_OK(hipHostMalloc(&ctx->h_race, sizeof(PowRaceBuf), hipHostMallocDefault));
-  if (!ctx->d_rin) HIP_OK(hipMalloc(&ctx->d_rin, sizeof(PowRaceIn)));
-  if (!ctx->h_rin) HIP_OK(hipHostMalloc(&ctx->h_rin, sizeof(PowRaceIn), hipHostMallocDefault));
-  if (!ctx->d_rslot) {
-    // The plan's largest grid: one workgroup per rival, or per CU (pow_race_plan).
-    const unsigned cap = (unsigned)std::max(POW_RACE_MAX_RIVALS, ctx->cu_count);
-    HIP_OK(hipMalloc(&ctx->d_rslot, (size_t)cap * sizeof(PowChainSlot)));
-    ctx->race_grid_max = cap;
-  }
+  RESERVE(ctx->d_race, 1);
+  RESERVE(ctx->h_race, 1);
+  RESERVE(ctx->d_rin, 1);
+  RESERVE(ctx->h_rin, 1);
+  // The plan's largest grid: one workgroup per rival, or per CU (pow_race_plan).
+  RESERVE(ctx->d_rslot, (size_t)std::max(POW_RACE_MAX_RIVALS, ctx->cu_count));
   return POW_OK;
 }
 
@@ -1259,55 +1226,14 @@ int pow_mine_race(pow_ctx* ctx, const pow_block* parent, size_t n, unsigned diff
     }
     return rc;
   }
-  ctx->stats = pow_stats{};
-  if (n_mined) *n_mined = 0;
-  if (hashes_done) *hashes_done = 0;
+  FusedCall f(ctx, n_mined, hashes_done);
   if (n == 0) return 1;
   if (int rc = set_dev(ctx)) return rc;
   const uint64_t now = created_at ? 0 : (uint64_t)time(nullptr);
-  pow_stats total{};
-  size_t done = 0;
-  auto finish = [&](int rc) {
-    ctx->stats = total;
-    if (n_mined) *n_mined = done;
-    if (hashes_done) *hashes_done = total.hashes;
-    return rc;
-  };
-  if (diff_bits > 32 || (int)diff_bits > ctx->race_fused_max) {
-    pow_block last = *parent;
-    while (done < n && !cancel_moved(cancel_word, epoch)) {
-      pow_block best;
-      uint64_t best_ctr = UINT64_MAX;
-      uint32_t best_r = 0;
-      bool cancelled = false;
-      for (size_t r = 0; r < R; ++r) {
-        // A later position loses a tie: it searches only below the best counter so far.
-        const uint64_t window = best_ctr == UINT64_MAX ? ctr_count : best_ctr - ctr_start;
-        if (window == 0) break;  // ctr_start itself solved: nothing lies below it
-        pow_block tmpl, blk;
-        uint64_t ctr = UINT64_MAX;
-        refresh(&tmpl, &last, owners[r], diff_bits, created_at ? created_at[done * R + r] : now);
-        const int rc = mine_impl(ctx, &tmpl, ctr_start, window, diff_bits, cancel_word, epoch, &blk, &ctr, nullptr, false);
-        add_stats(&total, ctx->stats);
-        if (rc < 0) return finish(rc);
-        if (rc == 1) {
-          best = blk;
-          best_ctr = ctr;
-          best_r = (uint32_t)r;
-        } else if (cancel_moved(cancel_word, epoch)) {  // this rival's window was not searched to its end
-          cancelled = true;
-          break;
-        }
-      }
-      if (cancelled || best_ctr == UINT64_MAX) break;
-      out[n - 1 - done] = last = best;
-      if (winners) winners[n - 1 - done] = best_r;
-      if (found_ctr) found_ctr[n - 1 - done] = best_ctr;
-      ++done;
-    }
-    return finish(done == n ? 1 : 0);
-  }
-  if (cancel_moved(cancel_word, epoch)) return finish(0);
+  if (diff_bits > 32 || (int)diff_bits > ctx->race_fused_max)
+    return mine_linked_host(f, parent, n, diff_bits, owners, R, created_at, now, ctr_start, ctr_count, cancel_word, epoch, out,
+                            winners, found_ctr);
+  if (cancel_moved(cancel_word, epoch)) return f.finish(0);
   if (int rc = ensure_race(ctx)) return rc;
   PowRacePlan plan;
   pow_race_plan(diff_bits, (uint32_t)R, ctr_count, (uint32_t)std::max(1, ctx->cu_count), ctx->race_lanes_log2,
@@ -1318,59 +1244,53 @@ int pow_mine_race(pow_ctx* ctx, const pow_block* parent, size_t n, unsigned diff
   L.diff = diff_bits;
   L.n_rivals = (uint32_t)R;
   L.nwg_r = plan.nwg_r;
-  if ((uint64_t)L.nwg_r * R > ctx->race_grid_max)
-    return fail(POW_EHIP, "race plan: %u workgroups for %u slots", (unsigned)(L.nwg_r * R), ctx->race_grid_max);
-  PowRaceBuf* const H = ctx->h_race;
-  PowRaceBuf* const D = ctx->d_race;
-  PowRaceIn* const HI = ctx->h_rin;
+  if ((uint64_t)L.nwg_r * R > ctx->d_rslot.cap)
+    return fail(POW_EHIP, "race plan: %u workgroups for %u slots", (unsigned)(L.nwg_r * R), (unsigned)ctx->d_rslot.cap);
+  PowRaceBuf* const H = ctx->h_race.p;
+  PowRaceBuf* const D = ctx->d_race.p;
+  PowRaceIn* const HI = ctx->h_rin.p;
   H->parent = *parent;
   memcpy(HI->owner, owners, R * sizeof(uint32_t));
-  while (done < n) {
-    if (cancel_moved(cancel_word, epoch)) return finish(0);
-    const size_t nb = std::min<size_t>(plan.batch, n - done);
+  while (f.done < n) {
+    if (cancel_moved(cancel_word, epoch)) return f.finish(0);
+    const size_t nb = std::min<size_t>(plan.batch, n - f.done);
     memset(&H->ctl, 0, sizeof H->ctl);
     H->ctl.min_key = ~0ull;
-    for (size_t i = 0; i < nb * R; ++i) HI->created_at[i] = created_at ? created_at[done * R + i] : now;
+    for (size_t i = 0; i < nb * R; ++i) HI->created_at[i] = created_at ? created_at[f.done * R + i] : now;
     HIP_OK(hipMemcpyAsync(D, H, offsetof(PowRaceBuf, rec), hipMemcpyHostToDevice, ctx->stream));
-    HIP_OK(hipMemcpyAsync(ctx->d_rin, HI, offsetof(PowRaceIn, created_at) + nb * R * sizeof(uint64_t),
+    HIP_OK(hipMemcpyAsync(ctx->d_rin.p, HI, offsetof(PowRaceIn, created_at) + nb * R * sizeof(uint64_t),
                           hipMemcpyHostToDevice, ctx->stream));
-    if (pow_hooks)
-      if (int rc = pow_hooks->before_launch(ctx)) return rc;
-    HIP_OK(hipEventRecord(ctx->ev0, ctx->stream));
+    if (int rc = timed_begin(ctx)) return rc;
     for (size_t j = 0; j < nb; ++j) {
       L.height = (uint32_t)j;
       const pow_block* const prev = j == 0 ? &D->parent : &D->blk[nb - j];
-      HIP_OK(pow_launch_race(ctx->stream, L, (const uint32_t*)prev, (uint32_t*)&D->blk[nb - 1 - j], ctx->d_rin, &D->ctl,
-                             ctx->d_rslot, D->rec));
+      HIP_OK(pow_launch_race(ctx->stream, L, (const uint32_t*)prev, (uint32_t*)&D->blk[nb - 1 - j], ctx->d_rin.p, &D->ctl,
+                             ctx->d_rslot.p, D->rec));
     }
     HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
     HIP_OK(hipMemcpyAsync(&H->ctl, &D->ctl, offsetof(PowRaceBuf, blk) - offsetof(PowRaceBuf, ctl) + nb * sizeof(pow_block),
                           hipMemcpyDeviceToHost, ctx->stream));
     // 2 ns per (counter, rival) pair of the batch
-    if (int rc = stream_wait_for(ctx, "race mining batch", 2ull * nb * R * ctr_count)) return rc;
-    float ms = 0;
-    HIP_OK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    total.kernel_ms += ms;
-    total.launches += (uint32_t)nb;
-    total.hashes += H->ctl.hashes;
+    if (int rc = timed_end(ctx, "race mining batch", 2ull * nb * R * ctr_count, (uint32_t)nb, &f.total)) return rc;
+    f.total.hashes += H->ctl.hashes;
     const size_t m = H->ctl.n_done;
     if (m > nb || (m < nb && !H->ctl.stop)) return fail(POW_EHIP, "race mining batch: %zu of %zu heights and no stop word", m, nb);
     for (size_t j = 0; j < m; ++j) {
       const PowRaceRec& rec = H->rec[j];
       if (rec.winner >= R || rec.rel >= ctr_count)
-        return fail(POW_EHIP, "race mining batch: height %zu reports rival %u at counter %llu", done + j, rec.winner,
+        return fail(POW_EHIP, "race mining batch: height %zu reports rival %u at counter %llu", f.done + j, rec.winner,
                     (unsigned long long)rec.rel);
-      if (winners) winners[n - 1 - done - j] = rec.winner;
-      if (found_ctr) found_ctr[n - 1 - done - j] = ctr_start + rec.rel;
+      if (winners) winners[n - 1 - f.done - j] = rec.winner;
+      if (found_ctr) found_ctr[n - 1 - f.done - j] = ctr_start + rec.rel;
     }
     // Height done + j is blk[nb - 1 - j] and goes to out[n - 1 - done - j]:
     // the m sealed ones are the batch's upper m slots, contiguous in both.
-    if (m) memcpy(out + (n - done - m), &H->blk[nb - m], m * sizeof(pow_block));
-    done += m;
-    if (m < nb) return finish(0);  // a height nobody solved
-    H->parent = H->blk[0];         // the tip: the next batch's parent
+    if (m) memcpy(out + (n - f.done - m), &H->blk[nb - m], m * sizeof(pow_block));
+    f.done += m;
+    if (m < nb) return f.finish(0);  // a height nobody solved
+    H->parent = H->blk[0];           // the tip: the next batch's parent
   }
-  return finish(1);
+  return f.finish(1);
 }
 
 int pow_cancel(pow_ctx* ctx, uint32_t epoch) {

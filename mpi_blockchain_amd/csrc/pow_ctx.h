@@ -1,5 +1,6 @@
-// The context of the C ABI and what pow_api.cpp shares with the test
-// library's hooks (pow_hooks.cpp).  Private to csrc/; not part of the C ABI.
+// The context of the C ABI, the holders of its grow-on-demand buffers and what
+// pow_api.cpp shares with the test library's hooks (pow_hooks.cpp).  Private to
+// csrc/; not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,6 +18,43 @@
   } while (0)
 
 struct pow_aql;  // the direct dispatcher (pow_aql.h): test library only
+
+// The context's buffers that are made at the first call that needs them, or
+// grow with a call's size: a pointer and its capacity in elements, in device
+// memory (DevBuf) or pinned host memory (HostBuf).  reserve(n) keeps what it
+// has when n <= cap; otherwise it frees first and allocates after, so a grown
+// buffer never stands beside its predecessor.  No destructor frees them:
+// pow_destroy leaves a wedged context's memory allocated under a kernel that
+// may still write it, and that stays its explicit decision
+// (pow_ctx::release_buffers, which has to name every holder of pow_ctx: one
+// that is added and not listed there leaks).  A failed allocation is reported
+// with the buffer's name (`what`; RESERVE passes the expression).
+template <class T, bool kPinned>
+struct CtxBuf {
+  T* p = nullptr;
+  size_t cap = 0;
+  void release() {
+    if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    cap = 0;
+  }
+  int reserve(size_t n, const char* what) {
+    if (n <= cap) return POW_OK;
+    release();
+    const hipError_t e = kPinned ? hipHostMalloc(&p, n * sizeof(T), hipHostMallocDefault) : hipMalloc(&p, n * sizeof(T));
+    if (e != hipSuccess)
+      return fail(POW_EHIP, "%s of %s (%zu bytes) failed: %s", kPinned ? "hipHostMalloc" : "hipMalloc", what,
+                  n * sizeof(T), hipGetErrorString(e));
+    cap = n;
+    return POW_OK;
+  }
+};
+#define RESERVE(buf, n)                                   \
+  do {                                                    \
+    if (int rc_ = (buf).reserve((n), #buf)) return rc_;   \
+  } while (0)
+template <class T> using DevBuf = CtxBuf<T, false>;
+template <class T> using HostBuf = CtxBuf<T, true>;
 
 // Result words of K3 (pow_verify_kernel): reset by the host before a launch.
 struct PowVerifyRes {
@@ -59,8 +97,8 @@ struct PowSealCtl {
   unsigned int n_done;         // blocks sealed by the batch
 };
 
-// K4 (pow_chain_kernel, pow_chain.hip), one launch per block of pow_mine_chain.
-#define POW_CHAIN_MAX_BATCH 64   // launches queued without a host wait
+// K4 (pow_chain_kernel, pow_chain.hip), one launch per block of pow_mine_chain,
+// at most POW_CHAIN_MAX_BATCH (pow_host.h) queued without a host wait.
 // pow_mine_chain: above it the host loop over pow_mine.  The largest measured d
 // at which the fused call beat the host loop (profiles/mine_chain/README.md).
 #define POW_CHAIN_FUSED_MAX_D 23
@@ -81,9 +119,8 @@ struct PowChainLaunch {
   uint64_t created_at;     // the template's created_at
 };
 
-// K5 (pow_batch_kernel, pow_batch.hip), one launch per tile of pow_mine_batch's templates.
-#define POW_BATCH_MAX_TILE (1u << 14)  // templates per launch
-#define POW_BATCH_MAX_WG (1u << 16)    // workgroups per launch
+// K5 (pow_batch_kernel, pow_batch.hip), one launch per tile of pow_mine_batch's
+// templates: POW_BATCH_MAX_TILE templates and POW_BATCH_MAX_WG workgroups at most (pow_host.h).
 static_assert(POW_BATCH_MAX_WG <= POW_WALK_MAX_WG, "a template's workgroups fit the exit word's count");
 // pow_mine_batch: above it the host loop over pow_mine.  The largest measured d
 // at which the fused call beat the C loop at n = 64 by more than the two
@@ -180,38 +217,39 @@ struct pow_ctx {
   PowResult* h_res = nullptr;  // pinned read-back of d_res
   uint32_t* d_tail = nullptr;  // sweep: per-wave remainders (< 32 each), appended after the launch
   uint32_t tail_cap = 0;
-  uint32_t* d_out = nullptr;   // pow_sweep's device list and its radix-sort twin
-  uint32_t* d_alt = nullptr;
-  void* d_sort_tmp = nullptr;
-  size_t sort_tmp_bytes = 0;
-  size_t out_cap = 0;
-  uint32_t* d_msgs = nullptr;
-  uint32_t* d_dig = nullptr;
-  size_t hash_cap = 0;
-  uint32_t* d_vblk = nullptr;        // pow_verify_chain: one host tile of raw structs + its halo block,
-  uint8_t* d_vstatus = nullptr;      // the tile's status bytes ...
-  size_t verify_cap = 0;             // ... both sized for this many blocks
-  PowVerifyRes* d_vres = nullptr;    // K3's result words ...
-  PowVerifyRes* h_vres = nullptr;    // ... and their pinned twin: reset value up, result down
-  uint32_t* d_voffs = nullptr;       // pow_verify_chains: the chains' offsets (n_chains + 1 words) ...
-  uint32_t* d_vcres = nullptr;       // ... K7's verdicts: first_bad, then n_bad, a call's n_chains words each ...
-  uint32_t* h_vchains = nullptr;     // ... and the pinned twin of both: the offsets up, the verdicts down
-  size_t vchains_cap = 0;            // ... all sized for this many chains
-  PowChainBuf* d_chain = nullptr;    // pow_mine_chain: a batch on the device ...
-  PowChainBuf* h_chain = nullptr;    // ... its pinned twin ...
-  PowChainSlot* d_cslot = nullptr;   // ... and one slot per workgroup of a launch
-  unsigned chain_grid_max = 0;       // slots allocated = the largest grid of a K4 launch
-  uint8_t* d_batch = nullptr;        // pow_mine_batch: a tile's control words, then its raw structs ...
-  uint8_t* h_batch = nullptr;        // ... and the pinned twin they go up from in one copy
-  PowBatchRec* d_brec = nullptr;     // the tile's result records ...
-  PowBatchRec* h_brec = nullptr;     // ... and their pinned twin
-  PowChainSlot* d_bslot = nullptr;   // one slot per workgroup of a K5 launch (POW_BATCH_MAX_WG)
-  PowRaceBuf* d_race = nullptr;      // pow_mine_race: a batch on the device ...
-  PowRaceBuf* h_race = nullptr;      // ... its pinned twin ...
-  PowRaceIn* d_rin = nullptr;        // ... the rivals' owners and created_at ...
-  PowRaceIn* h_rin = nullptr;        // ... and the pinned twin they go up from
-  PowChainSlot* d_rslot = nullptr;   // one slot per workgroup of a K6 launch ...
-  unsigned race_grid_max = 0;        // ... = max(POW_RACE_MAX_RIVALS, cu_count)
+  // Made or grown by the call that needs them (release_buffers frees them):
+  DevBuf<uint32_t> d_out, d_alt;     // pow_sweep's device list and its radix-sort twin ...
+  DevBuf<uint8_t> d_sort_tmp;        // ... and the sort's scratch, in bytes
+  DevBuf<uint32_t> d_msgs, d_dig;    // pow_hash_blocks: 80 message words in, 8 digest words out per block
+  DevBuf<pow_block> d_vblk;          // pow_verify_chain[s]: one host tile of raw structs + its halo block,
+  DevBuf<uint8_t> d_vstatus;         // the tile's status bytes
+  DevBuf<PowVerifyRes> d_vres;       // K3's result words ...
+  HostBuf<PowVerifyRes> h_vres;      // ... and their pinned twin: reset value up, result down
+  DevBuf<uint32_t> d_voffs;          // pow_verify_chains: the chains' offsets (n_chains + 1 words) ...
+  DevBuf<uint32_t> d_vcres;          // ... K7's verdicts: first_bad, then n_bad, a call's n_chains words each ...
+  HostBuf<uint32_t> h_vchains;       // ... and the pinned twin of both: the offsets up, the verdicts down
+  DevBuf<PowChainBuf> d_chain;       // pow_mine_chain: a batch on the device ...
+  HostBuf<PowChainBuf> h_chain;      // ... its pinned twin ...
+  DevBuf<PowChainSlot> d_cslot;      // ... and one slot per workgroup of the largest K4 launch: one per CU
+  DevBuf<uint8_t> d_batch;           // pow_mine_batch: a tile's control words, then its raw structs ...
+  HostBuf<uint8_t> h_batch;          // ... and the pinned twin they go up from in one copy
+  DevBuf<PowBatchRec> d_brec;        // the tile's result records ...
+  HostBuf<PowBatchRec> h_brec;       // ... and their pinned twin
+  DevBuf<PowChainSlot> d_bslot;      // one slot per workgroup of a K5 launch (POW_BATCH_MAX_WG)
+  DevBuf<PowRaceBuf> d_race;         // pow_mine_race: a batch on the device ...
+  HostBuf<PowRaceBuf> h_race;        // ... its pinned twin ...
+  DevBuf<PowRaceIn> d_rin;           // ... the rivals' owners and created_at ...
+  HostBuf<PowRaceIn> h_rin;          // ... and the pinned twin they go up from
+  DevBuf<PowChainSlot> d_rslot;      // one slot per workgroup of a K6 launch: max(POW_RACE_MAX_RIVALS, cu_count)
+  void release_buffers() {  // every holder above
+    d_out.release(), d_alt.release(), d_sort_tmp.release();
+    d_msgs.release(), d_dig.release();
+    d_vblk.release(), d_vstatus.release(), d_vres.release(), h_vres.release();
+    d_voffs.release(), d_vcres.release(), h_vchains.release();
+    d_chain.release(), d_cslot.release(), h_chain.release();
+    d_batch.release(), d_brec.release(), d_bslot.release(), h_batch.release(), h_brec.release();
+    d_race.release(), d_rin.release(), d_rslot.release(), h_race.release(), h_rin.release();
+  }
   unsigned grid_full = 0;  // workgroups that fill the chip (8 per CU)
   // Set only by the test library's hooks (pow_hooks.cpp, at pow_init):
   bool force_full = false;        // use the d > 32 kernel for every d

@@ -1,11 +1,12 @@
 // Host code of the C ABI that needs no GPU (pow_host.h): the error string, the
-// clock, the per-template precompute, the launch splitting and the host-side
-// helpers of include/pow_gpu.h.  No HIP header: tests/host_unit.cpp links this
-// file alone and runs it on the CPU.
+// clock, the per-template precompute, the launch splitting, the plans of the
+// fused mining calls and the host-side helpers of include/pow_gpu.h.  No HIP
+// header: tests/host_unit.cpp links this file alone and runs it on the CPU.
 #include "pow_host.h"
 
 #include <time.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstddef>
 #include <cstdio>
@@ -241,6 +242,59 @@ void pow_race_plan(unsigned diff, uint32_t n_rivals, uint64_t ctr_count, uint32_
   if (batch > cap) batch = cap;
   if (batch < 1) batch = 1;
   p->batch = (uint32_t)batch;
+}
+
+namespace {
+// Workgroups for 2^lanes_log2 times the expected 2^d trials: no more lanes than
+// the window has counters, no more workgroups than `most`, never below one.
+uint64_t nwg_for(unsigned d, unsigned lanes_log2, uint64_t ctr_count, uint64_t most) {
+  const uint64_t lanes = std::min<uint64_t>(1ull << (d + lanes_log2), ctr_count);
+  return std::max<uint64_t>(1, std::min<uint64_t>((lanes + 255) / 256, most));
+}
+}  // namespace
+
+PowChainPlan pow_chain_plan(unsigned diff, uint64_t ctr_count, uint32_t grid_max, unsigned lanes_log2,
+                            unsigned batch_override) {
+  const unsigned d = std::min(diff, 32u);
+  // The grid follows the difficulty: lanes for four times the expected 2^d
+  // trials (a block then costs one trial's latency but for 1 in e^4; at d = 9
+  // and 13 two times measured 1.4 and 0.6 us per block slower, eight times 0.3
+  // and 2.2 us: more workgroups to start and to count out), no more than the
+  // window has counters or the chip takes at one wave per SIMD; the lanes of a
+  // full grid walk on through the window.
+  PowChainPlan p;
+  p.nwg = (uint32_t)nwg_for(d, std::min(lanes_log2, 8u), ctr_count, grid_max);
+  // A batch is about 2^26 expected trials (a handful of ms: the cancel latency).
+  const uint64_t batch = batch_override ? batch_override : 1ull << (26 - std::min(d, 26u));
+  p.batch = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(batch, POW_CHAIN_MAX_BATCH));
+  return p;
+}
+
+PowBatchPlan pow_batch_plan(unsigned diff, uint64_t n, uint64_t ctr_count, uint32_t cu_count, int lanes_log2,
+                            unsigned tile_override) {
+  const unsigned d = std::min(diff, 32u);
+  const uint64_t window = std::max<uint64_t>(1, ctr_count), cus = std::max(1u, cu_count);
+  // Templates per launch: about 2^26 expected trials (a handful of ms: the
+  // cancel latency), a grid of at most 2^16 workgroups, and windows of at most
+  // 2^38 counters in all, which keeps the watchdog's 2 ns per counter a bound
+  // worth having (550 s, K4's own worst case).
+  uint64_t tile = tile_override ? tile_override : (1ull << 26) / std::min<uint64_t>(1ull << std::min(d, 26u), window);
+  tile = std::min<uint64_t>(tile, (1ull << 38) / window);
+  tile = std::max<uint64_t>(1, std::min<uint64_t>(tile, POW_BATCH_MAX_TILE));
+  // Lanes for 2^lanes_log2 times the expected 2^d trials of a template: no
+  // more than the window has counters or the chip takes at one wave per SIMD.
+  // Four times, as K4, while the launch leaves CUs idle (a template then costs
+  // one trial's latency but for 1 in e^4); every lane computes at least one
+  // trial, so once the launch's workgroups exceed one per CU the surplus
+  // lanes are only surplus work: twice, then once the expected trials
+  // (d = 13, 64 templates: 8.8 us per template at four times, 4.1 at once).
+  unsigned ll = lanes_log2 < 0 ? 2u : std::min((unsigned)lanes_log2, 8u);
+  if (lanes_log2 < 0)
+    while (ll > 0 && std::min(tile, n) * nwg_for(d, ll, window, cus) > cus) --ll;
+  PowBatchPlan p;
+  p.nwg_t = (uint32_t)nwg_for(d, ll, window, cus);
+  p.tile = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(tile, POW_BATCH_MAX_WG / p.nwg_t));
+  return p;
 }
 
 extern "C" {

@@ -1,7 +1,8 @@
 // HIP-free host code of the miner (pow_host.cpp): the error string, the
-// clock, the per-template precompute and the launch splitting.  Pure integer
-// code: it compiles with a plain C++ compiler and no ROCm include path, so
-// tests/host_unit.cpp runs it on the CPU under sanitizers.  Library-internal
+// clock, the per-template precompute, the launch splitting and the plans of
+// the fused mining calls (K4, K5, K6).  Pure integer code: it compiles with a
+// plain C++ compiler and no ROCm include path, so tests/host_unit.cpp and
+// tests/{race,fused}_plan_unit.cpp run it on the CPU under sanitizers.  Library-internal
 // (pow_api.cpp, pow_group.cpp, pow_aql.cpp, pow_hooks.cpp); not part of the C
 // ABI, hence hidden.  pow_build_consts and pow_set_error (pow_template.h) and
 // the host-side helpers of include/pow_gpu.h are defined there too.
@@ -49,5 +50,38 @@ struct PowRacePlan {
 };
 void pow_race_plan(unsigned diff, uint32_t n_rivals, uint64_t ctr_count, uint32_t cu_count, unsigned lanes_log2,
                    unsigned batch_override, PowRacePlan* p);
+
+// The limits of the two plans below (their kernels are described in pow_ctx.h).
+#define POW_CHAIN_MAX_BATCH 64         // K4: launches queued without a host wait
+#define POW_BATCH_MAX_TILE (1u << 14)  // K5: templates per launch
+#define POW_BATCH_MAX_WG (1u << 16)    // K5: workgroups per launch
+
+// The plan of pow_mine_chain's fused path (K4, one launch per block): the
+// launch's workgroups and the blocks queued per batch.  Pure, as the race's:
+// the difficulty (<= 32), the window (1..2^32), the slots the context holds
+// (one per CU) and the test library's two overrides (lanes_log2: 2 is the
+// shipped value; batch_override: 0 = none).  It holds that 1 <= nwg <= max(1,
+// grid_max), (nwg - 1) x 256 < ctr_count (no workgroup starts past the window)
+// and 1 <= batch <= POW_CHAIN_MAX_BATCH.
+struct PowChainPlan {
+  uint32_t nwg;    // workgroups per launch
+  uint32_t batch;  // blocks per batch
+};
+PowChainPlan pow_chain_plan(unsigned diff, uint64_t ctr_count, uint32_t grid_max, unsigned lanes_log2,
+                            unsigned batch_override);
+
+// The plan of pow_mine_batch's fused path (K5, one launch per tile of the n
+// templates): the workgroups a template gets and the templates per launch.
+// Pure; lanes_log2 = -1 is the shipped plan (2 down to 0, while the launch
+// would exceed one workgroup per CU), tile_override 0 = none.  It holds that 1
+// <= nwg_t <= max(1, cu_count), 1 <= tile <= POW_BATCH_MAX_TILE, tile x nwg_t
+// <= POW_BATCH_MAX_WG, and tile x ctr_count <= 2^38 whenever tile > 1: an
+// override is capped by the window and the workgroups like the planned tile.
+struct PowBatchPlan {
+  uint32_t nwg_t;  // workgroups per template
+  uint32_t tile;   // templates per launch
+};
+PowBatchPlan pow_batch_plan(unsigned diff, uint64_t n, uint64_t ctr_count, uint32_t cu_count, int lanes_log2,
+                            unsigned tile_override);
 
 #pragma GCC visibility pop

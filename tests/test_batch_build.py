@@ -9,7 +9,7 @@ import pytest
 
 from mpi_blockchain_amd import _lib
 
-from test_build import CSRC, ROOT, null_stream_calls
+from test_build import CSRC, ROOT, api_function, null_stream_calls, timed_section_helpers
 
 KERNEL = "_Z16pow_batch_kernel"
 SWITCHES = (b"POW_BATCH_FUSED_MAX", b"POW_BATCH_TILE", b"POW_BATCH_LANES_LOG2")
@@ -57,12 +57,6 @@ def test_batch_kernel_is_in_both_libraries():
         assert os.path.join(CSRC, "pow_batch.hip") in build.sources(test=test)
 
 
-def batch_body() -> str:
-    api = open(os.path.join(CSRC, "pow_api.cpp")).read()
-    body = api[api.index("int pow_mine_batch("):]
-    return body[:body.index("\n}\n")]
-
-
 def test_no_null_stream_in_batch_sources():
     found = {}
     for f in ("pow_batch.hip", "pow_api.cpp", "pow_ctx.h"):
@@ -70,13 +64,18 @@ def test_no_null_stream_in_batch_sources():
         if hits:
             found[f] = hits
     assert not found, found
-    body = batch_body()
-    assert not null_stream_calls(body)
+    # the tile's bounded wait is in the timed section's closer
+    body, h = api_function("pow_mine_batch"), timed_section_helpers()
+    union = body + h["timed_begin"] + h["timed_end"]
+    assert not null_stream_calls(union)
     # one plain stream launch behind one bounded wait per tile; no graph
-    assert body.count("pow_launch_batch(ctx->stream") == 1 and body.count("stream_wait_for(") == 1
-    assert "hipGraph" not in body and "hipGraph" not in open(os.path.join(CSRC, "pow_batch.hip")).read()
+    assert body.count("pow_launch_batch(ctx->stream") == 1 and body.count("timed_end(") == 1
+    assert union.count("stream_wait_for(") == 1
+    assert "hipGraph" not in union and "hipGraph" not in open(os.path.join(CSRC, "pow_batch.hip")).read()
     # n == 1 and the host loop are pow_mine's own implementation
     assert "mine_impl(ctx, &tmpls[i]" in body
+    # the plan is the HIP-free one
+    assert "pow_batch_plan(" in body and "pow_batch_plan(" in open(os.path.join(CSRC, "pow_host.cpp")).read()
 
 
 def test_batch_kernel_never_waits_for_another_workgroup():

@@ -489,6 +489,26 @@ def null_stream_calls(text: str) -> list[tuple[int, str]]:
     return bad
 
 
+def api_function(name: str) -> str:
+    """The text of pow_api.cpp's function `name`, from its return type to its closing brace."""
+    api = open(os.path.join(CSRC, "pow_api.cpp")).read()
+    body = api[api.index(f"int {name}("):]
+    return body[:body.index("\n}\n")]
+
+
+def timed_section_helpers() -> dict:
+    """pow_api.cpp's helpers that stand between a call and its bounded wait:
+    each holds exactly one call of the next, down to the one stream_wait_for(
+    in timed_end, and none makes a null-stream call."""
+    h = {n: api_function(n) for n in ("timed_begin", "timed_end", "verify_tiles")}
+    for text in h.values():
+        assert not null_stream_calls(text)
+    assert h["timed_end"].count("stream_wait_for(") == 1 and "stream_wait_for(" not in h["timed_begin"]
+    walk = h["verify_tiles"]
+    assert walk.count("timed_begin(") == 1 and walk.count("timed_end(") == 1 and "stream_wait_for(" not in walk
+    return h
+
+
 def test_no_null_stream_in_library_sources():
     found = {}
     for p in SHIPPED_SOURCES:

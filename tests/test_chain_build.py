@@ -9,7 +9,7 @@ import pytest
 
 from mpi_blockchain_amd import _lib
 
-from test_build import CSRC, ROOT, null_stream_calls
+from test_build import CSRC, ROOT, api_function, null_stream_calls, timed_section_helpers
 
 KERNEL = "_Z16pow_chain_kernel"
 SWITCHES = (b"POW_CHAIN_BATCH", b"POW_CHAIN_FUSED_MAX", b"POW_CHAIN_LANES_LOG2")
@@ -65,12 +65,16 @@ def test_no_null_stream_in_chain_sources():
             found[f] = hits
     assert not found, found
     api = open(os.path.join(CSRC, "pow_api.cpp")).read()
-    body = api[api.index("int pow_mine_chain("):]
-    body = body[:body.index("\n}\n")]
-    assert not null_stream_calls(body)
+    # the batch's bounded wait is in the timed section's closer, the host loop in the one shared with pow_mine_race
+    body, h = api_function("pow_mine_chain"), timed_section_helpers()
+    union = body + h["timed_begin"] + h["timed_end"] + api_function("mine_linked_host")
+    assert not null_stream_calls(union)
     # plain stream launches behind one bounded wait per batch; no graph
-    assert "pow_launch_chain(ctx->stream" in body and body.count("stream_wait_for(") == 1
+    assert "pow_launch_chain(ctx->stream" in body and body.count("timed_end(") == 1
+    assert union.count("stream_wait_for(") == 1
     assert "hipGraph" not in api and "hipGraph" not in open(os.path.join(CSRC, "pow_chain.hip")).read()
+    # the plan is the HIP-free one
+    assert "pow_chain_plan(" in body and "pow_chain_plan(" in open(os.path.join(CSRC, "pow_host.cpp")).read()
 
 
 def test_chain_kernel_never_waits_for_another_workgroup():

@@ -1,9 +1,12 @@
 """pow_mine_chain on the host (CPU only): its statement
 mpi_blockchain_amd.block.mine_chain against a chain mined through the
 reference's own block_to_hash and solves_problem
-(tests/golden/mined_chain.json), and the argument errors of the C entry
-point, which need no GPU."""
+(tests/golden/mined_chain.json), the argument errors of the C entry point,
+which need no GPU, and the pure plans of its and pow_mine_batch's fused paths
+(csrc/pow_host.cpp) under sanitizers in a process of their own."""
 import ctypes
+import os
+import subprocess
 
 import pytest
 
@@ -11,6 +14,9 @@ from mpi_blockchain_amd import _lib
 from mpi_blockchain_amd.block import field, make_block, mine_chain, nonce_from_counter, set_field, verify_chain
 
 import chain_util as cu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "mpi_blockchain_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
@@ -108,3 +114,18 @@ def test_empty_chain_still_needs_a_context():
     L = _lib.load()
     assert L.pow_mine_chain(None, None, 0, 4, 0, None, 0, 1, None, 0, None, None, None) == _lib.POW_EINVAL
     assert "pow_mine_chain" in _lib.EXPORTS
+
+
+def test_plans_under_sanitizers(tmp_path):
+    """tests/fused_plan_unit.cpp links pow_host.cpp alone and runs as a process
+    of its own: nothing is loaded into Python."""
+    exe = str(tmp_path / "fused_plan_unit")
+    # no ROCm include path: pow_host.cpp and its headers are HIP-free
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=undefined", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
+                    os.path.join(ROOT, "tests", "fused_plan_unit.cpp"), os.path.join(CSRC, "pow_host.cpp"), "-o", exe],
+                   check=True, cwd=str(tmp_path))
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    print(r.stdout, r.stderr)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    assert " plans, 0 failed" in r.stdout, r.stdout

@@ -9,7 +9,7 @@ import pytest
 
 from mpi_blockchain_amd import _lib
 
-from test_build import CSRC, ROOT, null_stream_calls
+from test_build import CSRC, ROOT, api_function, null_stream_calls, timed_section_helpers
 
 KERNEL = "_Z15pow_race_kernel"
 SWITCHES = (b"POW_RACE_FUSED_MAX", b"POW_RACE_BATCH", b"POW_RACE_LANES_LOG2")
@@ -57,12 +57,6 @@ def test_race_kernel_is_in_both_libraries():
         assert os.path.join(CSRC, "pow_race.hip") in build.sources(test=test)
 
 
-def race_body() -> str:
-    api = open(os.path.join(CSRC, "pow_api.cpp")).read()
-    body = api[api.index("int pow_mine_race("):]
-    return body[:body.index("\n}\n")]
-
-
 def test_no_null_stream_in_race_sources():
     found = {}
     for f in ("pow_race.hip", "pow_api.cpp", "pow_ctx.h"):
@@ -70,15 +64,18 @@ def test_no_null_stream_in_race_sources():
         if hits:
             found[f] = hits
     assert not found, found
-    body = race_body()
-    assert not null_stream_calls(body)
+    # the batch's bounded wait is in the timed section's closer, the host loop in the one shared with pow_mine_chain
+    body, h, host = api_function("pow_mine_race"), timed_section_helpers(), api_function("mine_linked_host")
+    union = body + h["timed_begin"] + h["timed_end"] + host
+    assert not null_stream_calls(union)
     # plain stream launches behind one bounded wait and one copy back per batch; no graph
-    assert body.count("pow_launch_race(ctx->stream") == 1 and body.count("stream_wait_for(") == 1
-    assert body.count("hipMemcpyDeviceToHost") == 1
-    assert "hipGraph" not in body and "hipGraph" not in open(os.path.join(CSRC, "pow_race.hip")).read()
+    assert body.count("pow_launch_race(ctx->stream") == 1 and body.count("timed_end(") == 1
+    assert union.count("stream_wait_for(") == 1
+    assert union.count("hipMemcpyDeviceToHost") == 1
+    assert "hipGraph" not in union and "hipGraph" not in open(os.path.join(CSRC, "pow_race.hip")).read()
     # one rival is pow_mine_chain, and the host loop is pow_mine's own implementation under the best counter so far
     assert "return rc;" in body and "pow_mine_chain(ctx, parent, n, diff_bits" in body
-    assert "mine_impl(ctx, &tmpl, ctr_start, window" in body
+    assert body.count("mine_linked_host(") == 1 and "mine_impl(ctx, &tmpl, ctr_start, window" in host
     # the plan is the HIP-free one
     assert "pow_race_plan(" in body and "pow_race_plan(" in open(os.path.join(CSRC, "pow_host.cpp")).read()
 

@@ -12,7 +12,7 @@ import tempfile
 
 import pytest
 
-from test_build import CSRC, ROOT, null_stream_calls
+from test_build import CSRC, ROOT, api_function, null_stream_calls, timed_section_helpers
 
 KERNEL = "_Z17pow_verify_kernel"
 
@@ -73,8 +73,10 @@ def test_no_null_stream_in_verify_sources():
         if hits:
             found[f] = hits
     assert not found, found
-    api = open(os.path.join(CSRC, "pow_api.cpp")).read()
-    body = api[api.index("int pow_verify_chain("):]
-    body = body[:body.index("\n}\n")]
-    assert "stream_wait_for(" in body and "hipMemcpyAsync(" in body
-    assert "padded_message" not in body  # no per-block host work
+    # the tiles' copy up and the bounded wait are in the walk the call shares with pow_verify_chains
+    body, h = api_function("pow_verify_chain"), timed_section_helpers()
+    assert body.count("verify_tiles(") == 1 and "hipMemcpyAsync(" in body and "hipMemcpyAsync(" in h["verify_tiles"]
+    union = body + h["verify_tiles"] + h["timed_begin"] + h["timed_end"]
+    assert union.count("stream_wait_for(") == 1 and not null_stream_calls(union)
+    assert "pow_launch_verify(" in body
+    assert "padded_message" not in union  # no per-block host work

@@ -14,13 +14,15 @@ difficulty):
                blocks (oracle/_ref/libref_O2.so: ref_sweep, i.e. block_to_hash
                plus the nonce write and solves_problem per block), one CPU thread
 
-Median of 21 calls after 3 warm-up calls.  Writes the table to
-profiles/verify_chains/README.md (or --out) and prints it.
+Median of 21 calls (or --calls) after 3 warm-up calls.  Writes the table to
+profiles/verify_chains/README.md (or --out) and prints it; --json FILE keeps
+every call's time of the two GPU columns, for comparing two builds.
 
-    python tools/verify_chains_bench.py [--out FILE] [--shapes 2x5,64x200,...]
+    python tools/verify_chains_bench.py [--calls 21] [--out FILE] [--json FILE] [--shapes 2x5,64x200,...]
 """
 import argparse
 import ctypes
+import json
 import os
 import statistics
 import sys
@@ -38,7 +40,7 @@ SHAPES = ((2, 5), (16, 5), (64, 5), (1024, 5), (64, 200), (1 << 14, 5))
 REPS, WARM = 21, 3
 
 
-def median_ms(fn):
+def median_ms(fn, samples=None):
     for _ in range(WARM):
         fn()
     ts = []
@@ -46,14 +48,20 @@ def median_ms(fn):
         t0 = time.perf_counter()
         fn()
         ts.append((time.perf_counter() - t0) * 1e3)
+    if samples is not None:
+        samples.extend(ts)
     return statistics.median(ts), min(ts), max(ts)
 
 
 def main():
+    global REPS
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "verify_chains", "README.md"))
     ap.add_argument("--shapes", default=",".join(f"{n}x{k}" for n, k in SHAPES))
+    ap.add_argument("--calls", type=int, default=REPS)
+    ap.add_argument("--json")
     args = ap.parse_args()
+    REPS = args.calls
     shapes = [tuple(int(v) for v in s.split("x")) for s in args.shapes.split(",")]
     R = RefLib("O2")
     most = max(n * k for n, k in shapes)
@@ -61,7 +69,7 @@ def main():
     full = build_chain(most, 0, seed=9)  # every slice of a valid chain is a valid chain: the batches are slices
     print(f"built {most} blocks in {time.perf_counter() - t0:.1f} s", flush=True)
     size = ctypes.sizeof(Block)
-    rows = []
+    rows, samples = [], []
     with GpuMiner(0) as m:
         m.warmup()
         info = m.device_info()
@@ -89,10 +97,12 @@ def main():
                     ok += verify_chain(ctx, tip, k, 0, None, pf, pb)
                 assert ok == n
 
-            g = median_ms(chains_call)
+            sample = {"chains": n, "length": k, "chains_call_ms": [], "chain_loop_ms": []}
+            samples.append(sample)
+            g = median_ms(chains_call, sample["chains_call_ms"])
             kern = statistics.median(kernel[-REPS:])
             assert list(first) == [k] * n and not any(bad)
-            lp = median_ms(chain_loop)
+            lp = median_ms(chain_loop, sample["chain_loop_ms"])
             tmpl = OBlock()
             ctypes.memmove(ctypes.addressof(tmpl), ctypes.addressof(full[0]), ctypes.sizeof(OBlock))
             c = median_ms(lambda: R.sweep(tmpl, 0, total, cap=1))
@@ -125,6 +135,9 @@ def main():
     with open(args.out, "w") as f:
         f.write(text)
     print(text)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(samples, f, indent=1)
 
 
 if __name__ == "__main__":
