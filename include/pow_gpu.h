@@ -124,6 +124,19 @@ int pow_block_to_bytes(const pow_block* b, uint8_t out[POW_MSG_BYTES]);
 /* solves_problem (block.cpp:91-96) with a run-time difficulty: the first
  * `diff_bits` binary digits of the 64-char hex digest are all '0'. */
 int pow_solves_problem(const char* hex, unsigned diff_bits);
+/* The reference's OWN nonces: what its gen_random_nonce (block.cpp:61-72, 9 x
+ * rand() % 62 over a-z, A-Z, 0-9, then NUL) returns at calls trial_start ..
+ * trial_start + n - 1 (the first call of a process is trial 0) after
+ * srand(seed); the reference seeds with time(NULL) + mpi_rank (node.cpp:386).
+ * This is glibc's TYPE_3 generator, the one the reference was built and
+ * measured with: r[i] = r[i-31] + r[i-3] over 2^32, seeded by the 16807
+ * Lehmer step (seed 0 counts as 1), draw k = r[k + 344] >> 1.  The library
+ * restates it and jumps to trial_start by a polynomial power; it never calls
+ * rand() or srand(), keeps no process-global state and is thread-safe.
+ * nonces: n x POW_NONCE_SIZE bytes.  POW_EINVAL: trial_start + n >
+ * POW_RAND_TRIAL_LIMIT, or null nonces with n > 0.  No GPU work. */
+#define POW_RAND_TRIAL_LIMIT (1ULL << 56)
+int pow_rand_nonces(uint32_t seed, uint64_t trial_start, size_t n, char* nonces);
 
 /* ---- GPU entry points -------------------------------------------------- */
 /* block_to_hash (block.cpp:74-77) for a batch of blocks on the GPU.
@@ -440,6 +453,60 @@ int pow_mine_race(pow_ctx* ctx, const pow_block* parent, size_t n, unsigned diff
                   pow_block* out /* n, tip first */,
                   uint32_t* winners /* n, may be NULL */, uint64_t* found_ctr /* n, may be NULL */,
                   size_t* n_mined, uint64_t* hashes_done);
+
+/* pow_mine with the reference's own nonces in place of the counter nonces:
+ * "with seed S, which block does the reference mine, and after how many
+ * trials?"  The call looks at trials [trial_start, trial_start + trial_count)
+ * of the stream of srand(seed) (pow_rand_nonces above) on *tmpl.
+ * Returns 1 with the LOWEST solving trial in *found_trial (may be NULL): *out =
+ * *tmpl copied whole, nonce = that trial's nonce, block_hash[0..64] = the 64 hex
+ * characters + NUL of the digest the GPU computed; bytes 65..255 of block_hash
+ * stay the template's (node.cpp:318).  The reference tests its trials in order
+ * and stops at the first that solves, so found_trial + 1 is where its stream
+ * stands afterwards, also when a rival's block made it change template
+ * mid-stream (the stream runs on across templates, node.cpp:285-302): a caller
+ * replays a reference rank by calling again from found_trial + 1 on the next
+ * template (examples/mine_rand.c).
+ * Returns 0, with out not touched, if the window holds no solution or the
+ * cancel word (optional; read at entry and between launches) differs from
+ * `epoch`.
+ * POW_EINVAL, checked in this order before the context is touched and with
+ * nothing written: diff_bits > 32 (the kernel tests H0 <= threshold as
+ * pow_mine_chain's does, and a 2^32 window at d > 32 more likely than not holds
+ * nothing); trial_count == 0 or > 2^32; trial_start + trial_count >
+ * POW_RAND_TRIAL_LIMIT; a null ctx, tmpl or out; a context bound to a stop
+ * board.
+ * The window runs in launches of at most 2^26 trials (the cancel latency, a
+ * handful of milliseconds), in ascending order; the first launch with a hit
+ * ends the call.  Per launch: one copy up (the control words, the generator's
+ * state at the launch's first trial and the template), one copy back of 64
+ * bytes and one bounded wait (10 s + 2 ns per trial).  In a launch lane g of G
+ * walks runs of T consecutive trials of the stream, its 31-word generator state
+ * in LDS; it starts from the launch's state moved by two polynomials of tables
+ * that depend on T alone (made on the host at the first call with that T, 63
+ * KB), and jumps from run to run by a third.  The grid is pow_mine_chain's
+ * (lanes for four times the expected 2^d trials, at most one workgroup per CU);
+ * T = 1 while that grid covers them, else the power of two at which one pass
+ * does (at most 1,024).  All lanes share the lowest solving trial so far and
+ * stop above it: every trial below the answer is tested.  The host seals the
+ * block from the GPU's record and checks the nine characters the GPU hashed
+ * against pow_rand_nonces: a difference fails the call with POW_EHIP.
+ * *hashes_done (may be NULL) = trials issued.  pow_get_stats: launches,
+ * kernel_ms (events around each launch) and hashes.  pow_warmup does not
+ * launch this call's kernel: the first call of a process also loads its code
+ * object and makes the buffers.
+ * Cost (MI355X, profiles/mine_rand/README.md; medians of 9 passes over the same
+ * templates, against pow_mine with counter nonces in the same process): SLOWER
+ * than pow_mine at every d measured: 83.6 us per call at d = 9 (pow_mine:
+ * 35.3), 87.2 at d = 13 (36.5), 150.5 at d = 17 (51.8), 409 at d = 19 (144),
+ * 1,411 at d = 21 (452) and 5,508 at d = 23 (2,987).  A 2^30 window without a
+ * solution at d = 32 runs at 6.27 G trials/s (pow_mine: 9.09).  The call is for
+ * reproducing or auditing a reference run, not for throughput. */
+int pow_mine_rand(pow_ctx* ctx, const pow_block* tmpl, uint32_t seed,
+                  uint64_t trial_start, uint64_t trial_count, unsigned diff_bits,
+                  const volatile uint32_t* cancel_word, uint32_t epoch,
+                  pow_block* out, uint64_t* found_trial /* may be NULL */,
+                  uint64_t* hashes_done /* may be NULL */);
 
 /* In-flight cancellation (the reference re-checks its chain only after a
  * trial, node.cpp:315).  Publishes `epoch`, the caller's current value of the

@@ -19,6 +19,7 @@ HASH_SIZE = 256
 NONCE_SIZE = 10
 MSG_BYTES = 270
 COUNTER_LIMIT = 62**9
+RAND_TRIAL_LIMIT = 1 << 56
 
 POW_OK, POW_EINVAL, POW_ENOSPC, POW_EHIP, POW_ENODEV, POW_ECOMM = 0, -1, -2, -3, -4, -5
 _ERRNAMES = {POW_EINVAL: "POW_EINVAL", POW_ENOSPC: "POW_ENOSPC", POW_EHIP: "POW_EHIP",
@@ -118,6 +119,9 @@ def load(test_hooks: bool = False) -> ctypes.CDLL:
         "pow_nonce_from_counter": ([ctypes.c_uint64, ctypes.c_char_p], ctypes.c_int),
         "pow_block_to_bytes": ([P, ctypes.c_char_p], ctypes.c_int),
         "pow_solves_problem": ([ctypes.c_char_p, ctypes.c_uint], ctypes.c_int),
+        "pow_rand_nonces": ([ctypes.c_uint32, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_char_p], ctypes.c_int),
+        "pow_mine_rand": ([ctypes.c_void_p, P, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint,
+                           ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, P, c_u64p, c_u64p], ctypes.c_int),
         "pow_hash_blocks": ([ctypes.c_void_p, P, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p],
                             ctypes.c_int),
         "pow_hash_block": ([ctypes.c_void_p, P, ctypes.c_char_p, ctypes.c_char_p], ctypes.c_int),
@@ -186,7 +190,7 @@ def load(test_hooks: bool = False) -> ctypes.CDLL:
 EXPORTS = ("pow_device_count", "pow_init", "pow_warmup", "pow_destroy", "pow_last_error", "pow_get_stats", "pow_launch_path",
            "pow_device_info", "pow_device_pci_bus_id",
            "pow_nonce_from_counter", "pow_block_to_bytes", "pow_solves_problem", "pow_hash_blocks",
-           "pow_hash_block", "pow_verify_chain", "pow_verify_chains", "pow_mine_chain", "pow_mine_batch", "pow_mine_race", "pow_mine", "pow_mine_any", "pow_cancel", "pow_sweep", "pow_sweep_device", "pow_dev_alloc", "pow_dev_free",
+           "pow_hash_block", "pow_verify_chain", "pow_verify_chains", "pow_mine_chain", "pow_mine_batch", "pow_mine_race", "pow_mine_rand", "pow_rand_nonces", "pow_mine", "pow_mine_any", "pow_cancel", "pow_sweep", "pow_sweep_device", "pow_dev_alloc", "pow_dev_free",
            "pow_dev_read", "pow_valu_peak", "pow_valu_rate", "pow_valu_rate_ctx", "pow_group_partition", "pow_group_unique_id", "pow_group_init",
            "pow_group_init_within",
            "pow_group_init_custom", "pow_group_destroy", "pow_group_info", "pow_group_rccl_path", "pow_group_last_search",

@@ -1293,6 +1293,111 @@ int pow_mine_race(pow_ctx* ctx, const pow_block* parent, size_t n, unsigned diff
   return f.finish(1);
 }
 
+namespace {
+
+// The buffers of pow_mine_rand, made at the first call: 70 KB of device memory.
+int ensure_rand(pow_ctx* ctx) {
+  RESERVE(ctx->d_rand, 1);
+  RESERVE(ctx->h_rand, 1);
+  RESERVE(ctx->d_rrec, 1);
+  RESERVE(ctx->h_rrec, 1);
+  RESERVE(ctx->d_rnslot, POW_RAND_MAX_WG);
+  RESERVE(ctx->d_rnchar, 3 * POW_RAND_MAX_WG);
+  RESERVE(ctx->d_rtab, POW_RAND_TAB_WORDS);
+  RESERVE(ctx->h_rtab, POW_RAND_TAB_WORDS);
+  return POW_OK;
+}
+
+}  // namespace
+
+// K8, one launch per 2^26 trials of the window, in ascending order; the first
+// launch with a hit ends the call.
+int pow_mine_rand(pow_ctx* ctx, const pow_block* tmpl, uint32_t seed, uint64_t trial_start, uint64_t trial_count,
+                  unsigned diff_bits, const volatile uint32_t* cancel_word, uint32_t epoch, pow_block* out,
+                  uint64_t* found_trial, uint64_t* hashes_done) {
+  if (diff_bits > 32) return fail(POW_EINVAL, "diff_bits %u > 32", diff_bits);
+  if (trial_count == 0 || trial_count > (1ull << 32))
+    return fail(POW_EINVAL, "trial_count %llu not in 1..2^32", (unsigned long long)trial_count);
+  if (trial_start > POW_RAND_TRIAL_LIMIT || trial_count > POW_RAND_TRIAL_LIMIT - trial_start)
+    return fail(POW_EINVAL, "trial range past POW_RAND_TRIAL_LIMIT (2^56)");
+  if (!ctx || !tmpl || !out) return fail(POW_EINVAL, "null");
+  if (ctx->board) return fail(POW_EINVAL, "pow_mine_rand does not run on a context bound to a stop board");
+  FusedCall f(ctx, nullptr, hashes_done);
+  if (cancel_moved(cancel_word, epoch)) return f.finish(0);
+  if (int rc = set_dev(ctx)) return rc;
+  if (int rc = ensure_rand(ctx)) return rc;
+  const PowRandPlan plan = pow_rand_plan(diff_bits, trial_count, (uint32_t)std::max(1, ctx->cu_count),
+                                         ctx->rand_lanes_log2, ctx->rand_run, ctx->rand_launch_log2);
+  PowRandIn* const H = ctx->h_rand.p;
+  PowRandIn* const D = ctx->d_rand.p;
+  memset(H, 0, sizeof *H);
+  memcpy(&H->tmpl, tmpl, sizeof *tmpl);  // whole: padding included
+  PowLaunchLat thr;
+  make_launch_lat(0, 1, diff_bits, &thr);
+  H->thr = thr.thr;
+  PowRandLaunch L;
+  memset(&L, 0, sizeof L);
+  L.run = plan.run;
+  L.nwg = plan.nwg;
+  uint32_t to_next[POW_RAND_WORDS];  // from a launch's first trial to the next launch's
+  pow_rand_power(9ull * L.run * ((uint64_t)L.nwg * 256u - 1u), H->step);
+  pow_rand_power(9ull * plan.launch, to_next);
+  {
+    uint32_t jump[POW_RAND_WORDS];
+    pow_rand_seed(seed, H->state);
+    pow_rand_power(9ull * trial_start, jump);
+    pow_rand_apply(jump, H->state, H->state);
+  }
+  for (uint64_t off = 0; off < trial_count; off += plan.launch) {
+    if (cancel_moved(cancel_word, epoch)) return f.finish(0);
+    const uint64_t n = std::min<uint64_t>(plan.launch, trial_count - off);
+    L.count = (uint32_t)n;
+    if (ctx->rand_tab_run != plan.run) {
+      // The tables of this T go up once, in front of the first launch that
+      // needs them and under its bounded wait: they count as there, and their
+      // pinned twin as free, once that wait has returned.
+      pow_rand_tables(plan.run, ctx->h_rtab.p);
+      ctx->rand_tab_run = 0;
+      HIP_OK(hipMemcpyAsync(ctx->d_rtab.p, ctx->h_rtab.p, POW_RAND_TAB_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice,
+                            ctx->stream));
+    }
+    H->ctl = PowBatchCtl{~0ull, 0ull};
+    HIP_OK(hipMemcpyAsync(D, H, sizeof *H, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = timed_begin(ctx)) return rc;
+    HIP_OK(pow_launch_rand(ctx->stream, L, D, ctx->d_rtab.p, &D->ctl, ctx->d_rnslot.p, ctx->d_rnchar.p, ctx->d_rrec.p));
+    HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_OK(hipMemcpyAsync(ctx->h_rrec.p, ctx->d_rrec.p, sizeof(PowRandRec), hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = timed_end(ctx, "rand mining launch", 2ull * n, 1u, &f.total)) return rc;  // 2 ns per trial
+    ctx->rand_tab_run = plan.run;
+    const PowRandRec& r = *ctx->h_rrec.p;
+    f.total.hashes += r.trials;
+    if (r.rel == ~0ull) {
+      pow_rand_apply(to_next, H->state, H->state);
+      continue;
+    }
+    if (r.rel >= n) return fail(POW_EHIP, "rand mining launch: reports trial %llu outside its %llu", (unsigned long long)r.rel, (unsigned long long)n);
+    // The nine characters the device hashed against the host's own generator:
+    // a device generator that drifted must not pass as a valid block.
+    const uint64_t trial = trial_start + off + r.rel;
+    char want[POW_NONCE_SIZE], got[POW_NONCE_SIZE];
+    if (int rc = pow_rand_nonces(seed, trial, 1, want)) return rc;
+    for (int i = 0; i < 8; ++i) got[i] = (char)(r.nonce_w[i / 4] >> (24 - 8 * (i % 4)));
+    got[8] = (char)r.nonce_w[2];
+    got[9] = 0;
+    if (memcmp(want, got, POW_NONCE_SIZE) != 0)
+      return fail(POW_EHIP, "rand mining launch: the device hashed nonce \"%.9s\" at trial %llu of seed %u, the host's generator gives \"%.9s\"",
+                  got, (unsigned long long)trial, seed, want);
+    if (out != tmpl) memcpy(out, tmpl, sizeof *out);  // whole: padding included
+    memcpy(out->nonce, want, POW_NONCE_SIZE);
+    char hx[65];
+    digest_out(r.digest, nullptr, hx);
+    memcpy(out->block_hash, hx, 65);  // strcpy semantics (node.cpp:318)
+    if (found_trial) *found_trial = trial;
+    return f.finish(1);
+  }
+  return f.finish(0);
+}
+
 int pow_cancel(pow_ctx* ctx, uint32_t epoch) {
   if (!ctx) return fail(POW_EINVAL, "null");
   // A plain store into mapped host memory: no HIP call, no stream; the

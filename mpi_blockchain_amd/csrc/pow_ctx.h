@@ -182,6 +182,34 @@ struct PowRaceLaunch {
   uint32_t height;         // of the batch: the row of PowRaceIn::created_at, and the record to write
 };
 
+// K8 (pow_rand_kernel, pow_rand.hip), one launch per 2^26 trials at most of
+// pow_mine_rand: the search of K4-K6 over the nonces of the reference's rand()
+// stream.  What goes up per launch, in one copy:
+struct PowRandIn {
+  PowBatchCtl ctl;                  // min_rel = the lowest solving trial relative to the launch; reset by the host
+  uint32_t state[POW_RAND_WORDS];   // the generator's state at the launch's first trial
+  uint32_t thr;                     // a digest solves iff H0 <= thr
+  uint32_t step[POW_RAND_WORDS];    // x^(9 T (G - 1)): from the end of a lane's run to its next
+  uint32_t pad;
+  pow_block tmpl;                   // the raw struct, hashed as it stands (as K5)
+};
+static_assert(offsetof(PowRandIn, tmpl) % 4 == 0 && sizeof(PowRandIn) % 8 == 0, "dwords");
+// ... and what comes down: written by the last workgroup to leave.
+struct PowRandRec {
+  unsigned long long rel;     // lowest solving trial relative to the launch; ~0 = the launch holds none
+  unsigned int digest[8];     // its digest
+  unsigned long long trials;
+  unsigned int nonce_w[3];    // message words 1 and 2 and the top byte of word 3 as the winning lane hashed them
+  unsigned int pad;
+};
+// The arguments of a launch.
+struct PowRandLaunch {
+  uint32_t count;  // trials of the launch, <= 2^26
+  uint32_t run;    // T: consecutive trials of a lane per pass, <= POW_RAND_MAX_RUN
+  uint32_t nwg;    // workgroups (= gridDim.x), <= POW_RAND_MAX_WG
+  uint32_t pad;
+};
+
 struct pow_ctx {
   int device = 0;
   int cu_count = 0;
@@ -241,7 +269,18 @@ struct pow_ctx {
   DevBuf<PowRaceIn> d_rin;           // ... the rivals' owners and created_at ...
   HostBuf<PowRaceIn> h_rin;          // ... and the pinned twin they go up from
   DevBuf<PowChainSlot> d_rslot;      // one slot per workgroup of a K6 launch: max(POW_RACE_MAX_RIVALS, cu_count)
+  DevBuf<PowRandIn> d_rand;          // pow_mine_rand: a launch's input on the device ...
+  HostBuf<PowRandIn> h_rand;         // ... and its pinned twin
+  DevBuf<PowRandRec> d_rrec;         // the launch's record ...
+  HostBuf<PowRandRec> h_rrec;        // ... and its pinned twin
+  DevBuf<PowChainSlot> d_rnslot;     // one slot per workgroup of a K8 launch (POW_RAND_MAX_WG) ...
+  DevBuf<uint32_t> d_rnchar;         // ... and the three nonce words of its hit
+  DevBuf<uint32_t> d_rtab;           // the two tables of the run T below (pow_rand_tables) ...
+  HostBuf<uint32_t> h_rtab;          // ... and the pinned twin they go up from
+  uint32_t rand_tab_run = 0;         // the T the tables on the device were made for (0 = none yet)
   void release_buffers() {  // every holder above
+    d_rand.release(), h_rand.release(), d_rrec.release(), h_rrec.release();
+    d_rnslot.release(), d_rnchar.release(), d_rtab.release(), h_rtab.release();
     d_out.release(), d_alt.release(), d_sort_tmp.release();
     d_msgs.release(), d_dig.release();
     d_vblk.release(), d_vstatus.release(), d_vres.release(), h_vres.release();
@@ -267,6 +306,9 @@ struct pow_ctx {
   unsigned race_batch = 0;        // pow_mine_race: heights per batch (0 = the plan)
   unsigned race_lanes_log2 = 2;   // K6's grid: lanes over all rivals = 2^this x the expected 2^d trials
   int race_fused_max = POW_RACE_FUSED_MAX_D;  // pow_mine_race: highest d on the fused path (-1 = host loop only)
+  unsigned rand_run = 0;          // pow_mine_rand: K8's run T (0 = the plan)
+  int rand_lanes_log2 = -1;       // K8's grid: 2^this lanes (-1 = the plan: K4's grid)
+  unsigned rand_launch_log2 = 26; // trials per K8 launch = 2^this
   // K1' and K2' launches as AQL packets (pow_aql.cpp) instead of
   // hipLaunchKernel: test library only, opt-in there; null = the HIP launch
   // path, the only one the shipped library has.
@@ -300,6 +342,8 @@ hipError_t pow_launch_batch(hipStream_t stream, const PowBatchLaunch& L, uint32_
                             PowBatchCtl* ctl, PowChainSlot* slots, PowBatchRec* rec);
 hipError_t pow_launch_race(hipStream_t stream, const PowRaceLaunch& L, const uint32_t* prev, uint32_t* dst,
                            const PowRaceIn* in, PowSealCtl* ctl, PowChainSlot* slots, PowRaceRec* rec);
+hipError_t pow_launch_rand(hipStream_t stream, const PowRandLaunch& L, const PowRandIn* in, const uint32_t* tab,
+                           PowBatchCtl* ctl, PowChainSlot* slots, uint32_t* slot_nonce, PowRandRec* rec);
 hipError_t pow_sort_u32(void* temp, size_t* temp_bytes, uint32_t* keys, uint32_t* alt, uint32_t n,
                         uint32_t** sorted, hipStream_t stream);
 hipError_t pow_launch_search_lat(bool full, bool any, bool asm_groups, unsigned grid, hipStream_t stream,

@@ -44,6 +44,12 @@ void configure(pow_ctx* ctx) {
   if (const char* rf = getenv("POW_RACE_FUSED_MAX")) ctx->race_fused_max = (int)std::max(-1l, std::min(32l, strtol(rf, nullptr, 0)));
   if (const char* rb = getenv("POW_RACE_BATCH")) ctx->race_batch = (unsigned)std::min((unsigned long)POW_RACE_MAX_BATCH, strtoul(rb, nullptr, 0));
   if (const char* rl = getenv("POW_RACE_LANES_LOG2")) ctx->race_lanes_log2 = (unsigned)std::min(8ul, strtoul(rl, nullptr, 0));
+  // pow_mine_rand: K8's run T (rounded down to a power of two, at most 1,024), its grid (2^n lanes, at
+  // least one workgroup and at most one per CU) and the trials per launch (2^n, at most 2^26); the
+  // result must not depend on any of them
+  if (const char* rr = getenv("POW_RAND_RUN")) ctx->rand_run = (unsigned)std::min((unsigned long)POW_RAND_MAX_RUN, strtoul(rr, nullptr, 0));
+  if (const char* rg = getenv("POW_RAND_LANES_LOG2")) ctx->rand_lanes_log2 = (int)std::min(16ul, strtoul(rg, nullptr, 0));
+  if (const char* rn = getenv("POW_RAND_LAUNCH_LOG2")) ctx->rand_launch_log2 = (unsigned)std::min(26ul, strtoul(rn, nullptr, 0));
   if (const char* g = getenv("POW_GRID_PER_CU")) {  // launch-geometry experiments
     const int per = atoi(g);
     if (per > 0 && per <= 64) ctx->grid_full = (unsigned)ctx->cu_count * (unsigned)per;

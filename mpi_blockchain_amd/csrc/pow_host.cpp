@@ -297,9 +297,124 @@ PowBatchPlan pow_batch_plan(unsigned diff, uint64_t n, uint64_t ctr_count, uint3
   return p;
 }
 
+// ---------------- glibc's TYPE_3 rand(), restated (block.cpp:61-72's source of nonces) ----------------
+
+void pow_rand_seed(uint32_t seed, uint32_t x[POW_RAND_WORDS]) {
+  uint32_t r[344];
+  r[0] = seed ? seed : 1u;
+  for (int i = 1; i < 31; ++i) {
+    const int32_t w = (int32_t)r[i - 1];
+    const int32_t hi = w / 127773, lo = w - hi * 127773;  // C division: toward zero
+    int64_t v = 16807ll * lo - 2836ll * hi;
+    if (v < 0) v += 2147483647;
+    r[i] = (uint32_t)v;
+  }
+  for (int i = 31; i < 34; ++i) r[i] = r[i - 31];
+  for (int i = 34; i < 344; ++i) r[i] = r[i - 31] + r[i - 3];
+  memcpy(x, r + 313, POW_RAND_WORDS * sizeof(uint32_t));
+}
+
+uint32_t pow_rand_draw(uint32_t x[POW_RAND_WORDS]) {
+  const uint32_t v = x[0] + x[28];
+  memmove(x, x + 1, (POW_RAND_WORDS - 1) * sizeof(uint32_t));
+  x[POW_RAND_WORDS - 1] = v;
+  return v >> 1;
+}
+
+void pow_rand_mul(const uint32_t a[POW_RAND_WORDS], const uint32_t b[POW_RAND_WORDS], uint32_t out[POW_RAND_WORDS]) {
+  uint32_t t[2 * POW_RAND_WORDS - 1] = {0};
+  for (int i = 0; i < POW_RAND_WORDS; ++i)
+    for (int j = 0; j < POW_RAND_WORDS; ++j) t[i + j] += a[i] * b[j];
+  for (int k = 2 * POW_RAND_WORDS - 2; k >= POW_RAND_WORDS; --k) {  // x^k = x^(k-3) + x^(k-31)
+    t[k - 3] += t[k];
+    t[k - 31] += t[k];
+  }
+  memcpy(out, t, POW_RAND_WORDS * sizeof(uint32_t));
+}
+
+void pow_rand_power(uint64_t n, uint32_t c[POW_RAND_WORDS]) {
+  uint32_t sq[POW_RAND_WORDS] = {0, 1u};  // x
+  memset(c, 0, POW_RAND_WORDS * sizeof(uint32_t));
+  c[0] = 1u;
+  for (; n; n >>= 1) {
+    if (n & 1u) pow_rand_mul(c, sq, c);
+    pow_rand_mul(sq, sq, sq);
+  }
+}
+
+void pow_rand_apply(const uint32_t c[POW_RAND_WORDS], const uint32_t x[POW_RAND_WORDS], uint32_t y[POW_RAND_WORDS]) {
+  uint32_t e[2 * POW_RAND_WORDS - 1], out[POW_RAND_WORDS];
+  memcpy(e, x, POW_RAND_WORDS * sizeof(uint32_t));
+  for (int k = POW_RAND_WORDS; k < 2 * POW_RAND_WORDS - 1; ++k) e[k] = e[k - 31] + e[k - 3];
+  for (int j = 0; j < POW_RAND_WORDS; ++j) {
+    uint32_t s = 0;
+    for (int i = 0; i < POW_RAND_WORDS; ++i) s += c[i] * e[i + j];
+    out[j] = s;
+  }
+  memcpy(y, out, sizeof out);
+}
+
+void pow_rand_nonce(uint32_t x[POW_RAND_WORDS], char nonce[POW_NONCE_SIZE]) {
+  for (int i = 0; i < POW_NONCE_SIZE - 1; ++i) nonce[i] = digit_char(pow_rand_draw(x) % 62u);
+  nonce[POW_NONCE_SIZE - 1] = 0;  // block.cpp:71
+}
+
+PowRandPlan pow_rand_plan(unsigned diff, uint64_t trial_count, uint32_t cu_count, int lanes_log2, unsigned run_override,
+                          unsigned launch_log2) {
+  const unsigned d = std::min(diff, 32u);
+  PowRandPlan p;
+  p.launch = 1ull << std::min(launch_log2, 26u);  // 2^26: the cancel latency, a handful of ms
+  const uint64_t n = std::max<uint64_t>(1, std::min(trial_count, p.launch));
+  const uint64_t most = std::min<uint64_t>(std::max(1u, cu_count), POW_RAND_MAX_WG);
+  // The grid is K4's: lanes for four times the expected 2^d trials, at most one workgroup per CU.
+  p.nwg = (uint32_t)(lanes_log2 < 0 ? nwg_for(d, 2, n, most)
+                                    : nwg_for(0, (unsigned)std::min(lanes_log2, 16), n, most));
+  // One trial per lane while that grid covers four times the expected trials
+  // (or the launch): a block then costs one trial's latency, as K4's.  Above
+  // that a lane walks T consecutive trials per pass, so that one pass covers them.
+  const uint64_t want = std::min<uint64_t>(4ull << d, n);
+  uint32_t run = 1;
+  if (run_override)
+    while (2 * run <= std::min(run_override, POW_RAND_MAX_RUN)) run *= 2;
+  else
+    while (run < POW_RAND_MAX_RUN && (uint64_t)p.nwg * 256u * run < want) run *= 2;
+  p.run = run;
+  return p;
+}
+
+void pow_rand_tables(uint32_t run, uint32_t* tab) {
+  uint32_t step[POW_RAND_WORDS], cur[POW_RAND_WORDS];
+  uint32_t* const A = tab;
+  uint32_t* const B = tab + POW_RAND_WORDS * 256u;
+  pow_rand_power(9ull * run, step);
+  pow_rand_power(0, cur);
+  for (uint32_t l = 0; l < 256u; ++l) {
+    for (int i = 0; i < POW_RAND_WORDS; ++i) A[i * 256u + l] = cur[i];
+    pow_rand_mul(cur, step, cur);
+  }
+  memcpy(step, cur, sizeof step);  // x^(9 T 256)
+  pow_rand_power(0, cur);
+  for (uint32_t w = 0; w < POW_RAND_MAX_WG; ++w) {
+    memcpy(B + w * POW_RAND_WORDS, cur, sizeof cur);
+    pow_rand_mul(cur, step, cur);
+  }
+}
+
 extern "C" {
 
 const char* pow_last_error(void) { return g_err.c_str(); }
+
+int pow_rand_nonces(uint32_t seed, uint64_t trial_start, size_t n, char* nonces) {
+  if (trial_start > POW_RAND_TRIAL_LIMIT || n > POW_RAND_TRIAL_LIMIT - trial_start)
+    return fail(POW_EINVAL, "trials past POW_RAND_TRIAL_LIMIT (2^56)");
+  if (!nonces && n) return fail(POW_EINVAL, "null nonces");
+  uint32_t x[POW_RAND_WORDS], jump[POW_RAND_WORDS];
+  pow_rand_seed(seed, x);
+  pow_rand_power(9ull * trial_start, jump);  // < 2^60
+  pow_rand_apply(jump, x, x);
+  for (size_t t = 0; t < n; ++t) pow_rand_nonce(x, nonces + t * POW_NONCE_SIZE);
+  return POW_OK;
+}
 
 int pow_nonce_from_counter(uint64_t ctr, char nonce[POW_NONCE_SIZE]) {
   if (!nonce) return fail(POW_EINVAL, "null nonce");

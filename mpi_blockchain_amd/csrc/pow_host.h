@@ -1,6 +1,7 @@
 // HIP-free host code of the miner (pow_host.cpp): the error string, the
 // clock, the per-template precompute, the launch splitting and the plans of
-// the fused mining calls (K4, K5, K6).  Pure integer code: it compiles with a
+// the fused mining calls (K4, K5, K6), and the reference's rand() stream with
+// the plan of K8.  Pure integer code: it compiles with a
 // plain C++ compiler and no ROCm include path, so tests/host_unit.cpp and
 // tests/{race,fused}_plan_unit.cpp run it on the CPU under sanitizers.  Library-internal
 // (pow_api.cpp, pow_group.cpp, pow_aql.cpp, pow_hooks.cpp); not part of the C
@@ -83,5 +84,52 @@ struct PowBatchPlan {
 };
 PowBatchPlan pow_batch_plan(unsigned diff, uint64_t n, uint64_t ctr_count, uint32_t cu_count, int lanes_log2,
                             unsigned tile_override);
+
+// ---- the reference's nonce stream (pow_rand_nonces, pow_mine_rand, K8) ----
+// glibc's TYPE_3 rand(): r[i] = r[i-31] + r[i-3] over Z/2^32, draw k = r[k +
+// 344] >> 1.  The state at draw q is x[0..30] = r[q + 313 .. q + 343]: draw q is
+// (x[0] + x[28]) >> 1, which becomes the new x[30].  Moving a state n draws is
+// a multiplication by x^n mod (x^31 - x^28 - 1), a polynomial of 31 words.
+// None of this calls rand() or srand(): no process-global state.
+#define POW_RAND_WORDS 31
+// The state at draw 0 of srand(seed) (seed 0 counts as 1).
+void pow_rand_seed(uint32_t seed, uint32_t x[POW_RAND_WORDS]);
+// The next draw of the state, which moves on by one.
+uint32_t pow_rand_draw(uint32_t x[POW_RAND_WORDS]);
+// out = a * b mod (x^31 - x^28 - 1); out may be a or b.
+void pow_rand_mul(const uint32_t a[POW_RAND_WORDS], const uint32_t b[POW_RAND_WORDS], uint32_t out[POW_RAND_WORDS]);
+// c = x^n, by square and multiply.
+void pow_rand_power(uint64_t n, uint32_t c[POW_RAND_WORDS]);
+// y = the state x moved by the polynomial c: y[j] = sum c[i] * x[i + j] over x
+// extended to 61 words by the recurrence.  y may be x.
+void pow_rand_apply(const uint32_t c[POW_RAND_WORDS], const uint32_t x[POW_RAND_WORDS], uint32_t y[POW_RAND_WORDS]);
+// The nine characters + NUL of the trial the state stands at (9 draws).
+void pow_rand_nonce(uint32_t x[POW_RAND_WORDS], char nonce[POW_NONCE_SIZE]);
+
+// The plan of pow_mine_rand (K8, launches of at most 2^26 trials): the trials
+// per launch, the launch's workgroups and the run T of consecutive trials a
+// lane walks before it jumps to its next run.  Pure: the difficulty (<= 32),
+// the window (1..2^32), the chip's CUs and the test library's three overrides
+// (lanes_log2: the grid's lanes as a power of two, -1 = the plan: K4's grid;
+// run_override: 0 = the plan; launch_log2: 26 is the shipped value).  It holds
+// that 1 <= launch <= 2^26, 1 <= nwg <= min(max(1, cu_count), POW_RAND_MAX_WG),
+// (nwg - 1) x 256 < min(launch, trial_count), run is a power of two (an
+// override: rounded down to one) and 1 <= run <= POW_RAND_MAX_RUN, so a pass
+// of the grid is at most 2^26 trials.
+#define POW_RAND_MAX_WG 256u
+#define POW_RAND_MAX_RUN 1024u
+struct PowRandPlan {
+  uint64_t launch;  // trials per launch
+  uint32_t nwg;     // workgroups per launch
+  uint32_t run;     // T
+};
+PowRandPlan pow_rand_plan(unsigned diff, uint64_t trial_count, uint32_t cu_count, int lanes_log2, unsigned run_override,
+                          unsigned launch_log2);
+// The two tables of a run T that K8's lanes start from: A[i * 256 + l] = word i
+// of x^(9 T l), l < 256 (word-major: a wave reads a word of its 64 lanes'
+// polynomials in one line), then B[w * 31 + i] = word i of x^(9 T 256 w), w <
+// POW_RAND_MAX_WG.  tab holds POW_RAND_TAB_WORDS words.
+#define POW_RAND_TAB_WORDS (POW_RAND_WORDS * 256u + POW_RAND_MAX_WG * POW_RAND_WORDS)
+void pow_rand_tables(uint32_t run, uint32_t* tab);
 
 #pragma GCC visibility pop

@@ -4,9 +4,10 @@
 // Each kernel is one translation unit that includes this header; a kernel
 // keeps how blockIdx.x maps to (template or rival, part), where word 0 of the
 // message comes from, which control words it uses, and what its last
-// workgroup writes.
+// workgroup writes.  K8 (pow_rand.hip) walks the reference's rand() nonces with
+// a loop of its own and shares the rest: expand, trial_of, leave and winner.
 //
-// The message.  A template is a 552-byte struct Block in LDS as 138 dwords;
+// The message. A template is a 552-byte struct Block in LDS as 138 dwords;
 // its padded message is 80 words in 5 chunks.  Message bytes 4..269 are the
 // struct's nonce and previous_block_hash, 266 bytes that start 2 bytes past a
 // dword of the struct, so they are byte-swapped dwords of it.  The hash field
@@ -144,11 +145,12 @@ __device__ __forceinline__ void expand(uint32_t (&msg0)[16], uint32_t (&kw)[4][6
   }
 }
 
-// The digest of the message with the nonce of ctr_start + rel.
-__device__ __forceinline__ void trial(const uint32_t (&base_digit)[9], uint32_t rel, const uint32_t (&msg0)[16],
-                                      const uint32_t (&kw)[4][64], uint32_t h[8]) {
+// The digest of the message with the nine nonce characters that chars(c) gives.
+template <class Chars>
+__device__ __forceinline__ void trial_of(Chars chars, const uint32_t (&msg0)[16], const uint32_t (&kw)[4][64],
+                                         uint32_t h[8]) {
   uint32_t c[9];
-  nonce_chars(base_digit, rel, c);
+  chars(c);
   uint32_t w[16];
 #pragma unroll
   for (int k = 0; k < 8; ++k) h[k] = IV[k];
@@ -166,6 +168,12 @@ __device__ __forceinline__ void trial(const uint32_t (&base_digit)[9], uint32_t 
     h[0] += s.a; h[1] += s.b; h[2] += s.c; h[3] += s.d;
     h[4] += s.e; h[5] += s.f; h[6] += s.g; h[7] += s.h;
   }
+}
+
+// The digest of the message with the nonce of ctr_start + rel.
+__device__ __forceinline__ void trial(const uint32_t (&base_digit)[9], uint32_t rel, const uint32_t (&msg0)[16],
+                                      const uint32_t (&kw)[4][64], uint32_t h[8]) {
+  trial_of([&](uint32_t (&c)[9]) { nonce_chars(base_digit, rel, c); }, msg0, kw, h);
 }
 
 // This workgroup's share, part `part` of `nparts`, of the search over the

@@ -12,7 +12,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import HASH_SIZE, Block, PowStats, check, load
+from ._lib import HASH_SIZE, NONCE_SIZE, Block, PowStats, check, load
 from .block import DEFAULT_DIFFICULTY, field, nonce_from_counter
 
 
@@ -69,6 +69,24 @@ class MineRaceResult:
     complete: bool        # all n were mined (pow_mine_race returned 1)
     hashes: int           # trials issued
     kernel_ms: float      # GPU time of the call
+
+
+@dataclass
+class MineRandResult:
+    block: Block          # the solved block (the reference's nonce of `trial` + block_hash filled)
+    trial: int            # the lowest solving trial of the window: the reference's stream then stands at trial + 1
+    hashes: int           # trials issued
+    kernel_ms: float      # GPU time of the call
+
+
+def rand_nonces(seed: int, start: int = 0, n: int = 1) -> list[bytes]:
+    """pow_rand_nonces: what the reference's gen_random_nonce (block.cpp:61-72)
+    returns at calls start .. start + n - 1 after srand(seed), each 9
+    characters + NUL.  Host only; no GPU work and no call of rand()."""
+    buf = ctypes.create_string_buffer(max(n, 1) * NONCE_SIZE)
+    L = load()
+    check(L.pow_rand_nonces(seed & 0xFFFFFFFF, start, n, buf), L)
+    return [buf.raw[i * NONCE_SIZE:(i + 1) * NONCE_SIZE] for i in range(n)]
 
 
 def refresh_template(last: Block, rank: int, difficulty: int = DEFAULT_DIFFICULTY,
@@ -247,6 +265,22 @@ class GpuMiner:
             return None
         return MineResult(out, ctr.value, hashes.value, self.stats()["kernel_ms"])
 
+    def mine_rand(self, tmpl: Block, seed: int, start: int = 0, count: int = 1 << 32,
+                  difficulty: int = DEFAULT_DIFFICULTY, epoch: int | None = None) -> MineRandResult | None:
+        """pow_mine_rand: :meth:`mine` with the reference's own nonces, trials
+        [start, start + count) of the stream of ``srand(seed)``: the LOWEST
+        solving trial, which is where the reference itself stops.  None if the
+        window holds none or :meth:`cancel` was called meanwhile."""
+        out = Block()
+        trial, hashes = ctypes.c_uint64(), ctypes.c_uint64()
+        ep = self._cancel.value if epoch is None else epoch
+        rc = check(self.L.pow_mine_rand(self.ctx, ctypes.byref(tmpl), seed & 0xFFFFFFFF, start, count, difficulty,
+                                        ctypes.byref(self._cancel), ep, ctypes.byref(out), ctypes.byref(trial),
+                                        ctypes.byref(hashes)), self.L)
+        if rc == 0:
+            return None
+        return MineRandResult(out, trial.value, hashes.value, self.stats()["kernel_ms"])
+
     def mine_chain(self, parent: Block, n: int, difficulty: int = DEFAULT_DIFFICULTY, owner: int = 0,
                    created_at=None, ctr_start: int = 0, ctr_count: int = 1 << 32,
                    epoch: int | None = None) -> MineChainResult:
@@ -423,9 +457,28 @@ def proof_of_work_round(miner: GpuMiner, last: Block, rank: int, start: int, cou
     return miner.mine(refresh_template(last, rank, difficulty), start, count, difficulty)
 
 
+def replay_proof_of_work(miner: GpuMiner, last: Block, rank: int, seed: int, n_blocks: int,
+                         difficulty: int = DEFAULT_DIFFICULTY, created_at=None) -> tuple[list, int]:
+    """What a solo reference rank seeded ``srand(seed)`` does (node.cpp:285-318):
+    refresh the template on the tip, test the stream's trials in order from
+    where it stands, seal the first that solves, go on at the trial after it.
+    created_at: one value per block (None: the clock, as the reference).
+    Returns the blocks, oldest first, and the total trials the rank drew; fewer
+    than `n_blocks` blocks if a 2^32 window held no solution."""
+    blocks, at = [], 0
+    for k in range(n_blocks):
+        tmpl = refresh_template(last, rank, difficulty, None if created_at is None else created_at[k])
+        r = miner.mine_rand(tmpl, seed, at, 1 << 32, difficulty)
+        if r is None:
+            break
+        blocks.append(r.block)
+        last, at = r.block, r.trial + 1
+    return blocks, at
+
+
 def block_hex(b: Block) -> str:
     return field(b, "block_hash").split(b"\0", 1)[0].decode()
 
 
-__all__ = ["GpuMiner", "DeviceBuffer", "StopBoard", "MineResult", "MineChainResult", "MineBatchResult", "VerifyResult", "VerifyChainsResult", "refresh_template", "proof_of_work_round", "block_hex",
+__all__ = ["GpuMiner", "DeviceBuffer", "StopBoard", "MineResult", "MineRandResult", "rand_nonces", "replay_proof_of_work", "MineChainResult", "MineBatchResult", "VerifyResult", "VerifyChainsResult", "refresh_template", "proof_of_work_round", "block_hex",
            "nonce_from_counter"]
