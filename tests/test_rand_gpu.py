@@ -4,7 +4,6 @@ solving trial against a brute force over tests/rand_util.py and hashlib, which
 never runs the code under test.  Every comparison of a block is over all 552
 bytes.  The shapes are the smallest at which K8 can still go wrong: d <= 15
 keeps the brute force at tens of thousands of hashlib calls."""
-import contextlib
 import ctypes
 import functools
 import json
@@ -18,32 +17,13 @@ from mpi_blockchain_amd import _lib
 from mpi_blockchain_amd.miner import GpuMiner, StopBoard, rand_nonces, refresh_template, replay_proof_of_work
 
 from helpers import block_from_template
+from rand_gpu_util import SEED, block_of, brute, call, check_against_brute, miner_with, raw
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "mpi_blockchain_amd")
-SWITCHES = ("POW_RAND_RUN", "POW_RAND_LANES_LOG2", "POW_RAND_LAUNCH_LOG2")
 LIMIT = 1 << 56
-SEED = 1700000003  # time + rank
-
-
-@contextlib.contextmanager
-def miner_with(**switches):
-    """A context of the test library whose pow_init saw the given switches."""
-    saved = {k: os.environ.pop(k, None) for k in SWITCHES}
-    os.environ.update({k: str(v) for k, v in switches.items()})
-    try:
-        m = GpuMiner(0, test_hooks=True)
-    finally:
-        for k, v in saved.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-    try:
-        yield m
-    finally:
-        m.close()
 
 
 @pytest.fixture(scope="module")
@@ -57,47 +37,6 @@ def shipped():
 def replay():
     with open(os.path.join(ROOT, "tests", "golden", "rand_replay.json")) as f:
         return json.load(f)
-
-
-def raw(b) -> bytes:
-    return ctypes.string_at(ctypes.addressof(b), ctypes.sizeof(b))
-
-
-def block_of(data: bytes) -> _lib.Block:
-    b = _lib.Block()
-    ctypes.memmove(ctypes.addressof(b), data, len(data))
-    return b
-
-
-@functools.lru_cache(maxsize=None)
-def brute(tmpl_bytes: bytes, seed: int, start: int, count: int, d: int, want: int = 1):
-    """rand_util's answer, computed once per case and shared."""
-    return tuple(rand_util.mine(tmpl_bytes, seed, start, count, d, want))
-
-
-def call(m, tmpl, seed, start, count, d, cancel=None, epoch=0):
-    """pow_mine_rand through the C ABI with poisoned outputs: rc, out's bytes, found, hashes."""
-    out = (ctypes.c_char * 552)(*([0xA5] * 552))
-    found, hashes = ctypes.c_uint64(12345), ctypes.c_uint64(12345)
-    rc = m.L.pow_mine_rand(m.ctx, ctypes.byref(tmpl), seed, start, count, d, cancel, epoch,
-                           ctypes.cast(out, ctypes.POINTER(_lib.Block)), ctypes.byref(found), ctypes.byref(hashes))
-    return rc, bytes(out), found.value, hashes.value
-
-
-def check_against_brute(m, tmpl, seed, start, count, d):
-    tb = raw(tmpl)
-    hits = brute(tb, seed, start, count, d)
-    rc, out, found, hashes = call(m, tmpl, seed, start, count, d)
-    if not hits:
-        assert (rc, out, found) == (0, b"\xA5" * 552, 12345), (seed, start, count, d)
-        assert hashes >= count
-        return None
-    trial, nonce, hexd = hits[0]
-    assert rc == 1, (m.L.pow_last_error(), seed, start, count, d)
-    assert found == trial, (found, trial, seed, start, count, d)
-    assert out == rand_util.seal(tb, nonce, hexd)
-    assert hashes >= trial - start + 1  # every trial up to the answer was tested
-    return trial
 
 
 # ---- 1: the headline ----

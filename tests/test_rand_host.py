@@ -2,11 +2,13 @@
 checks of pow_mine_rand (CPU only).  The stream is pinned three ways: to libc's
 own srand/rand through ctypes, to the pure-Python restatement tests/rand_util.py
 and to what the reference's gen_random_nonce gave (tests/golden/rand_replay.json,
-and the live reference build where it exists)."""
+and the live reference build where it exists).  K8's plan, its tables and its
+lane walk run in tests/rand_plan_unit.cpp, a process of its own under sanitizers."""
 import ctypes
 import ctypes.util
 import json
 import os
+import subprocess
 
 import pytest
 
@@ -117,6 +119,51 @@ def test_restated_brute_force_reproduces_the_recorded_replays(replay):
             last, at = rand_util.seal(bytes(t), nonce, hexd), trial + 1
             assert last.hex() == b["block_hex"]
         assert at == r["total_trials"]
+
+
+def test_plan_tables_and_lane_walk_under_sanitizers(tmp_path):
+    """tests/rand_plan_unit.cpp links pow_host.cpp alone and runs as a process
+    of its own under ASan + UBSan: nothing is loaded into Python."""
+    csrc = os.path.join(ROOT, "mpi_blockchain_amd", "csrc")
+    exe = str(tmp_path / "rand_plan_unit")
+    # no ROCm include path: pow_host.cpp and its headers are HIP-free
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=undefined", "-I", os.path.join(ROOT, "include"), "-I", csrc,
+                    os.path.join(ROOT, "tests", "rand_plan_unit.cpp"), os.path.join(csrc, "pow_host.cpp"), "-o", exe],
+                   check=True, cwd=str(tmp_path))
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    print(r.stdout, r.stderr)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    assert " checks, 0 failed" in r.stdout, r.stdout
+    assert int(r.stdout.split(" checks, 0 failed")[0].split()[-1]) > 1_000_000  # the sweep ran
+
+
+def test_seam_fixture_is_hashlib_s(golden):
+    """tests/golden/rand_seam.json (gen_rand_seam.py: the GPU only searched) row
+    by row: the nonce of the trial, its digest, its leading zero bits, one
+    witness on either side of the 32-bit seam, and nothing else near 2^-29 in
+    the 2,048-trial window the GPU tests run around it."""
+    import hashlib
+
+    with open(os.path.join(ROOT, "tests", "golden", "rand_seam.json")) as f:
+        v = json.load(f)
+    assert (v["before"], v["window"]) == (1000, 2048)
+    rows = v["witnesses"]
+    assert [r["leading_zeros"] == 31 for r in rows] == [True, False] and rows[1]["leading_zeros"] >= 32
+    templates = {t["name"]: t for t in golden["templates"]}
+    for r in rows:
+        t = templates[r["template"]]
+        assert (r["template"], r["seed"]) == ("S0", 1700000003) and v["before"] <= r["trial"] < LIMIT
+        tb = bytes(make_block(t["index"], t["node_owner_number"], t["difficulty"], t["created_at"],
+                              bytes.fromhex(t["previous_block_hash_hex"])))
+        nonce, = rand_util.nonces(r["seed"], r["trial"], 1)
+        assert nonce == r["nonce"].encode() + b"\0" and lib_nonces(r["seed"], r["trial"], 1) == nonce
+        digest = hashlib.sha256(rand_util.message(tb, nonce)).digest()
+        assert digest.hex() == r["digest"]
+        assert 256 - int.from_bytes(digest, "big").bit_length() == r["leading_zeros"]
+        assert int.from_bytes(digest[:4], "big") == (1 if r["leading_zeros"] == 31 else 0)  # H0 == thr
+        near = rand_util.mine(tb, r["seed"], r["trial"] - v["before"], v["window"], 29, want=v["window"])
+        assert near == [(r["trial"], nonce, r["digest"])]
 
 
 def test_all_62_characters_occur():

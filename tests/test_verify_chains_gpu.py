@@ -1,7 +1,11 @@
 """pow_verify_chains on the GPU against its host statements
 (mpi_blockchain_amd.block.verify_chains and best_chain).  The chains are built
 on the CPU with hashlib at d = 4, plus one of 65,538 blocks at d = 0, so no
-input depends on the code under test; every expected value is the mirror's."""
+input depends on the code under test; every expected value is the mirror's.
+K3's link and hex edge matrices (tests/verify_edges.py) go through the
+segmentation too, and the long chain once more as 98,307 chains, half of them
+empty, across both host tiles."""
+import bisect
 import ctypes
 
 import numpy as np
@@ -12,6 +16,7 @@ from mpi_blockchain_amd.block import V_HASH, V_INDEX, V_LINK, V_WORK, make_block
 from mpi_blockchain_amd.miner import GpuMiner
 
 import verify_chains_util as cu
+import verify_edges as ve
 import verify_util as vu
 
 pytestmark = pytest.mark.gpu
@@ -243,3 +248,90 @@ def test_produced_chains(miner):
     r = check(miner, chains, 9)
     assert r.ok and r.best == 1
     assert check(miner, chains[2:] + chains[:1], 9).best == 0
+
+
+# ---- K3's edge matrices (tests/verify_edges.py) through the segmentation ----
+@pytest.mark.parametrize("lead", [0, 1], ids=["pairs", "behind_one_block"])
+def test_link_matrix_as_chains_of_two(miner, lead):
+    """Case k's child and parent as a chain of their own.  In the flat chain
+    every parent is followed by a stranger, the next case's child, and K3
+    rightly flags it; here it is its chain's last block.  Without a leading
+    block the parents sit on odd lanes, lane 63 with the stranger in the halo;
+    behind one the children do, every 32nd on lane 63 with its parent there."""
+    cases = ve.link_cases()
+    flat = ve.link_chain(cases)
+    n = len(cases)
+    chains = ([vu.build_chain(1, 0, seed=91, first_index=77)] if lead else []) + cu.split(flat, [2] * n)
+    assert sum(len(c) for c in chains) > 20 * 64
+    assert (2 * 31 + 1) % 64 == 63  # case 31's parent without the leading block, its child behind it
+    r = check(miner, chains, 0)
+    for k, (pc, pp, kind, a, b) in enumerate(cases):
+        child, parent = (int(s) for s in r.status[lead + k])
+        assert not parent & (V_LINK | V_INDEX), (k, parent)  # a chain's last block has no parent
+        assert bool(child & V_LINK) == ve.link_differs(a, b), (pc, pp, kind)
+        assert not child & V_INDEX
+    # not vacuous: as ONE chain the parents are flagged, each against the next case's child
+    one = miner.verify_chain(flat, 0)
+    assert all(one.status[2 * k + 1] & V_INDEX for k in range(n - 1))
+    assert sum(bool(one.status[2 * k + 1] & V_LINK) for k in range(n - 1)) >= n - 8
+
+
+def test_hex_matrix_in_pieces(miner):
+    """Every text position of block_hash replaced by a NUL in a block of its
+    own, and the 400 blocks cut right in front of each of them: V_HASH on the
+    corrupted block and nothing else anywhere, since the block in front of it,
+    whose link to it is now broken, is the last of its chain."""
+    clean_chain = ve.hex_chain()
+    bad, used = ve.corrupt_hex(clean_chain, "nul")
+    assert len(used) == 64 and sum(V_LINK == s & V_LINK for s in vu.mirror(bad, 0)) == 63  # as one chain: broken links
+    lengths = cu.cut_in_front_of(ve.HEX_BLOCKS, used)
+    assert sum(lengths) == ve.HEX_BLOCKS and len(lengths) == 64 and 2 in lengths and max(lengths) > 64
+    r = check(miner, cu.split(clean_chain, lengths), 0)
+    assert r.ok and r.first_bad == lengths
+    r = check(miner, cu.split(bad, lengths), 0)
+    flagged = [(c, i, int(s)) for c, st in enumerate(r.status) for i, s in enumerate(st) if s]
+    assert flagged == [(c, 0, V_HASH) for c in range(0 if 0 in used else 1, 64)]
+    # ... and with every piece cut once more in its middle, which cuts no corrupted block from its child
+    halves = [h for n in lengths for h in (n - n // 2, n // 2)]
+    r = check(miner, cu.split(bad, halves), 0)
+    assert sum(r.n_bad) == 64 and all(set(st.tolist()) <= {0, V_HASH} for st in r.status)
+
+
+# ---- many chains ----
+def test_many_chains_across_the_host_tile(miner, big_chain):
+    """65,538 blocks as 98,307 chains of 1, 0, 2, 0, 1, 0, ... blocks: a binary
+    search 17 steps deep over offsets of which every other one repeats, in both
+    launches (the second with base = 65,536)."""
+    lengths = cu.repeating_lengths(BIG, (1, 0, 2, 0, 1, 0))
+    chains = cu.split(big_chain, lengths)
+    n = len(chains)
+    assert n > 98000 and lengths.count(0) > 49000 and sum(lengths) == BIG
+    starts = np.cumsum([0] + lengths).tolist()
+    # the chain of a global position: the last one that starts at or in front of it (the empty ones in front of it too)
+    where = {g: bisect.bisect_right(starts, g) - 1 for g in (0, T - 3, T - 1, T, BIG - 1)}
+    assert all(starts[c] <= g < starts[c] + lengths[c] for g, c in where.items())
+    assert where[0] == 0 and where[T - 1] != where[T] and not any(lengths[where[BIG - 1] + 1:])
+    zeros = [[0] * k for k in lengths]  # slices of a valid chain
+    check(miner, chains, 0, (zeros, list(lengths), [0] * n, 0, True))
+    assert miner.stats()["launches"] == 2 and miner.stats()["hashes"] == BIG
+    pair = where[T - 3]
+    assert lengths[pair] == 2 and starts[pair] == T - 3  # the last chain of two in front of the seam
+    for corrupt, c, i, stated in ((vu.flip_nonce, where[0], 0, [V_HASH]), (vu.flip_hash_digit, where[BIG - 1], 0, [V_HASH]),
+                                  (vu.flip_nonce, where[T - 1], 0, [V_HASH]), (vu.flip_hash_digit, where[T], 0, [V_HASH]),
+                                  (vu.flip_hash_digit, pair, 1, [V_LINK, V_HASH])):
+        keep = vu.copy_chain(chains[c])
+        corrupt(chains[c], i)
+        try:
+            st = vu.mirror(chains[c], 0)
+            assert st == stated
+            status = zeros[:c] + [st] + zeros[c + 1:]
+            first = list(lengths)
+            first[c] = next(k for k, s in enumerate(st) if s)
+            n_bad = [0] * n
+            n_bad[c] = sum(1 for s in st if s)
+            best = cu.best_chain(chains, status)
+            assert best == (0 if c else 2)  # the highest tip that is left
+            check(miner, chains, 0, (status, first, n_bad, best, False))
+            assert miner.stats()["launches"] == 2 and miner.stats()["hashes"] == BIG
+        finally:
+            ctypes.memmove(chains[c], keep, ctypes.sizeof(keep))

@@ -25,6 +25,26 @@ def split(chain, lengths):
     return out
 
 
+def repeating_lengths(total: int, pattern) -> list:
+    """`pattern` over and over until the lengths add up to `total` (the last one cut short)."""
+    out, left = [], total
+    while left:
+        for n in pattern:
+            out.append(min(n, left))
+            left -= out[-1]
+            if not left:
+                break
+    return out
+
+
+def cut_in_front_of(total: int, positions) -> list:
+    """Lengths that cut `total` blocks right in front of every one of
+    `positions`: each of them is the first block of a piece (nobody's parent),
+    and the block before it the last of one (nobody's child)."""
+    cuts = sorted(set(positions) - {0}) + [total]
+    return [b - a for a, b in zip([0] + cuts, cuts)]
+
+
 def concat(chains):
     total = sum(len(c) for c in chains)
     arr = (Block * max(total, 1))()
