@@ -80,7 +80,8 @@ typedef struct pow_stats {
                             pow_mine[_any] at d <= 21) times itself with the GPU's realtime
                             counter, from workgroup 0's start to the last workgroup's exit */
   uint32_t launches;     /* kernels launched by the call */
-  uint64_t hashes;       /* trials issued to the GPU (incl. edge lanes masked out) */
+  uint64_t hashes;       /* trials issued to the GPU (incl. edge lanes masked out); pow_find_seed:
+                            (seed, trial) pairs issued, no SHA-256 runs */
 } pow_stats;
 
 /* ---- context --------------------------------------------------------- */
@@ -507,6 +508,71 @@ int pow_mine_rand(pow_ctx* ctx, const pow_block* tmpl, uint32_t seed,
                   const volatile uint32_t* cancel_word, uint32_t epoch,
                   pow_block* out, uint64_t* found_trial /* may be NULL */,
                   uint64_t* hashes_done /* may be NULL */);
+
+/* The inverse of pow_rand_nonces: which srand() seed, at which trial, drew these
+ * nonces?  The reference seeds with time(NULL) + mpi_rank and records the seed
+ * nowhere, so an audit of a captured chain (pow_mine_rand above) starts here:
+ * a block's created_at bounds the seeds, its nonce is the target.
+ * The call returns EVERY (seed position p, trial t, target k) with p < n_seeds,
+ * seed = seed_first + p in uint32_t arithmetic (a window may wrap through 2^32),
+ * t in [trial_start, trial_start + trial_count), and the nine characters of
+ * pow_rand_nonces(seed, t, 1) equal to the first nine bytes of nonces[k]
+ * (nonces: n_targets x POW_NONCE_SIZE bytes; byte 9 of each is not read).  The
+ * search is exhaustive: no early exit.  out is sorted ascending by (p, t, k);
+ * *n_found = the number of matches, also when it exceeds cap, in which case
+ * POW_ENOSPC is returned and out holds the first cap matches in that order (the
+ * host keeps every match of the call before it sorts; out may be NULL when cap
+ * == 0).  Seeds 0 and 1 have the same stream (srand(0) is srand(1)): a window
+ * that holds both reports both, a real tie and not an error.
+ * Returns 1 if at least one match was found; 0, with *n_found = 0 and out not
+ * touched, if none was or if the cancel word (optional; read at entry and
+ * between launches) differs from `epoch`.
+ * POW_EINVAL, checked in this order before the context is touched and with
+ * nothing written: n_targets == 0 or > POW_SEED_MAX_TARGETS; n_seeds == 0 or >
+ * POW_SEED_MAX_SEEDS; trial_count == 0 or > 2^32; trial_start + trial_count >
+ * POW_RAND_TRIAL_LIMIT; a null ctx, nonces or n_found, or a null out with cap >
+ * 0; a target with one of its nine characters outside a-z, A-Z, 0-9 (it cannot
+ * match: refused rather than answered with nothing); a context bound to a stop
+ * board.
+ * The request runs in launches of at most 2^30 (seed, trial) pairs and at most
+ * 2^26 trials per seed, tiles of seeds outermost.  In a launch every seed has up
+ * to 256 workgroups; each seeds its generator on the device (no per-seed host
+ * work or copy), moves it to the launch's first trial by one polynomial from the
+ * host, and its lanes walk runs of T = 31 x 2^j consecutive trials with the
+ * 31-word state in registers: no SHA-256 runs.  Two 62 x 62-bit tables, on a
+ * target's first two characters and on its next two, stand in front of the
+ * compare.  Per launch: one copy up (1.8 KB), one copy back (12 KB: a
+ * counter and up to 1,024 matches; a
+ * launch that counts more fails the call with POW_EHIP rather than return a
+ * subset; 64 targets that all occur in it are 128 at the most) and one bounded
+ * wait (10 s + 2 ns per pair).  The host checks every match against
+ * pow_rand_nonces: a difference fails the call with POW_EHIP.
+ * *pairs_done (may be NULL) = (seed, trial) pairs issued.  pow_get_stats:
+ * launches, kernel_ms (events around each launch) and hashes, which for this
+ * call counts (seed, trial) pairs: no hash is computed.  pow_warmup does not
+ * launch this call's kernel: the first call of a process also loads its code
+ * object and makes the buffers.
+ * Cost (MI355X, profiles/find_seed/README.md; medians of 9 calls, kernel time,
+ * one target / 64 targets): one seed x 2^20 trials 18 / 31 us (59 / 83 us per
+ * call), x 2^32 trials 12.0 / 28.4 ms (360 / 151 G pairs/s: one seed has at most
+ * table B's 256 workgroups, one per CU); 64 seeds x 2^32 trials 221 / 385 ms;
+ * 4,096 seeds x 2^20 trials 3.2 / 5.7 ms, x 2^32 trials 14.1 / 24.7 s (1,244 /
+ * 713 G pairs/s sustained, about 200 and 110 times pow_mine_rand's 6.27 G
+ * trials/s).  A launch of 2^30 pairs takes 0.9 / 1.5 ms, against the 10.7 ms of
+ * pow_mine_rand's full launch in the same process: the cancel latency.  The
+ * reference's own srand + gen_random_nonce loop does 10.9 / 9.4 M pairs/s on one
+ * core of the same box: 18 days for what the last row does in 14 s. */
+#define POW_SEED_MAX_SEEDS (1u << 20)
+#define POW_SEED_MAX_TARGETS 64
+typedef struct pow_seed_match {
+  uint32_t seed;   /* the srand() argument */
+  uint32_t target; /* index into nonces[] */
+  uint64_t trial;  /* absolute trial: pow_rand_nonces(seed, trial, 1) gives nonces[target] */
+} pow_seed_match;
+int pow_find_seed(pow_ctx* ctx, const char* nonces /* n_targets x POW_NONCE_SIZE */, size_t n_targets,
+                  uint32_t seed_first, uint32_t n_seeds, uint64_t trial_start, uint64_t trial_count,
+                  const volatile uint32_t* cancel_word, uint32_t epoch, pow_seed_match* out, size_t cap,
+                  size_t* n_found, uint64_t* pairs_done /* may be NULL */);
 
 /* In-flight cancellation (the reference re-checks its chain only after a
  * trial, node.cpp:315).  Publishes `epoch`, the caller's current value of the

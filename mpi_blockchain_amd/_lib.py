@@ -20,6 +20,7 @@ NONCE_SIZE = 10
 MSG_BYTES = 270
 COUNTER_LIMIT = 62**9
 RAND_TRIAL_LIMIT = 1 << 56
+SEED_MAX_SEEDS, SEED_MAX_TARGETS = 1 << 20, 64
 
 POW_OK, POW_EINVAL, POW_ENOSPC, POW_EHIP, POW_ENODEV, POW_ECOMM = 0, -1, -2, -3, -4, -5
 _ERRNAMES = {POW_EINVAL: "POW_EINVAL", POW_ENOSPC: "POW_ENOSPC", POW_EHIP: "POW_EHIP",
@@ -58,6 +59,12 @@ REDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctype
 class PowStats(ctypes.Structure):
     _fields_ = [("kernel_ms", ctypes.c_double), ("launches", ctypes.c_uint32),
                 ("hashes", ctypes.c_uint64)]
+
+
+class SeedMatchRec(ctypes.Structure):
+    """pow_seed_match (include/pow_gpu.h): one match of pow_find_seed."""
+
+    _fields_ = [("seed", ctypes.c_uint32), ("target", ctypes.c_uint32), ("trial", ctypes.c_uint64)]
 
 
 class ValuResult(ctypes.Structure):
@@ -122,6 +129,9 @@ def load(test_hooks: bool = False) -> ctypes.CDLL:
         "pow_rand_nonces": ([ctypes.c_uint32, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_char_p], ctypes.c_int),
         "pow_mine_rand": ([ctypes.c_void_p, P, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint,
                            ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, P, c_u64p, c_u64p], ctypes.c_int),
+        "pow_find_seed": ([ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
+                           ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32,
+                           ctypes.POINTER(SeedMatchRec), ctypes.c_size_t, c_sizep, c_u64p], ctypes.c_int),
         "pow_hash_blocks": ([ctypes.c_void_p, P, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_char_p],
                             ctypes.c_int),
         "pow_hash_block": ([ctypes.c_void_p, P, ctypes.c_char_p, ctypes.c_char_p], ctypes.c_int),
@@ -190,7 +200,7 @@ def load(test_hooks: bool = False) -> ctypes.CDLL:
 EXPORTS = ("pow_device_count", "pow_init", "pow_warmup", "pow_destroy", "pow_last_error", "pow_get_stats", "pow_launch_path",
            "pow_device_info", "pow_device_pci_bus_id",
            "pow_nonce_from_counter", "pow_block_to_bytes", "pow_solves_problem", "pow_hash_blocks",
-           "pow_hash_block", "pow_verify_chain", "pow_verify_chains", "pow_mine_chain", "pow_mine_batch", "pow_mine_race", "pow_mine_rand", "pow_rand_nonces", "pow_mine", "pow_mine_any", "pow_cancel", "pow_sweep", "pow_sweep_device", "pow_dev_alloc", "pow_dev_free",
+           "pow_hash_block", "pow_verify_chain", "pow_verify_chains", "pow_mine_chain", "pow_mine_batch", "pow_mine_race", "pow_mine_rand", "pow_rand_nonces", "pow_find_seed", "pow_mine", "pow_mine_any", "pow_cancel", "pow_sweep", "pow_sweep_device", "pow_dev_alloc", "pow_dev_free",
            "pow_dev_read", "pow_valu_peak", "pow_valu_rate", "pow_valu_rate_ctx", "pow_group_partition", "pow_group_unique_id", "pow_group_init",
            "pow_group_init_within",
            "pow_group_init_custom", "pow_group_destroy", "pow_group_info", "pow_group_rccl_path", "pow_group_last_search",

@@ -1398,6 +1398,125 @@ int pow_mine_rand(pow_ctx* ctx, const pow_block* tmpl, uint32_t seed, uint64_t t
   return f.finish(0);
 }
 
+namespace {
+
+// The buffers of pow_find_seed, made at the first call: 76 KB of device memory,
+// K8's tables included.
+int ensure_seed(pow_ctx* ctx) {
+  RESERVE(ctx->d_seed, 1);
+  RESERVE(ctx->h_seed, 1);
+  RESERVE(ctx->d_sout, 1);
+  RESERVE(ctx->h_sout, 1);
+  RESERVE(ctx->d_rtab, POW_RAND_TAB_WORDS);
+  RESERVE(ctx->h_rtab, POW_RAND_TAB_WORDS);
+  return POW_OK;
+}
+
+struct SeedHit {
+  uint32_t pos, target;
+  uint64_t trial;
+};
+
+}  // namespace
+
+// K9, one launch per (tile of seeds, slice of trials) of the request, tiles
+// outermost; every match of the call is kept and sorted at the end.
+int pow_find_seed(pow_ctx* ctx, const char* nonces, size_t n_targets, uint32_t seed_first, uint32_t n_seeds,
+                  uint64_t trial_start, uint64_t trial_count, const volatile uint32_t* cancel_word, uint32_t epoch,
+                  pow_seed_match* out, size_t cap, size_t* n_found, uint64_t* pairs_done) {
+  if (n_targets == 0 || n_targets > POW_SEED_MAX_TARGETS)
+    return fail(POW_EINVAL, "n_targets %zu not in 1..%d", n_targets, POW_SEED_MAX_TARGETS);
+  if (n_seeds == 0 || n_seeds > POW_SEED_MAX_SEEDS) return fail(POW_EINVAL, "n_seeds %u not in 1..2^20", n_seeds);
+  if (trial_count == 0 || trial_count > (1ull << 32))
+    return fail(POW_EINVAL, "trial_count %llu not in 1..2^32", (unsigned long long)trial_count);
+  if (trial_start > POW_RAND_TRIAL_LIMIT || trial_count > POW_RAND_TRIAL_LIMIT - trial_start)
+    return fail(POW_EINVAL, "trial range past POW_RAND_TRIAL_LIMIT (2^56)");
+  if (!ctx || !nonces || !n_found || (!out && cap)) return fail(POW_EINVAL, "null");
+  uint32_t tgt[POW_SEED_MAX_TARGETS][2];
+  for (size_t k = 0; k < n_targets; ++k)
+    if (!pow_seed_pack(nonces + k * POW_NONCE_SIZE, tgt[k]))
+      return fail(POW_EINVAL, "target %zu holds a character outside the alphabet a-z, A-Z, 0-9: it cannot match", k);
+  if (ctx->board) return fail(POW_EINVAL, "pow_find_seed does not run on a context bound to a stop board");
+  FusedCall f(ctx, nullptr, pairs_done);
+  *n_found = 0;
+  if (cancel_moved(cancel_word, epoch)) return f.finish(0);
+  if (int rc = set_dev(ctx)) return rc;
+  if (int rc = ensure_seed(ctx)) return rc;
+  const PowSeedPlan plan = pow_seed_plan(n_seeds, trial_count, (uint32_t)std::max(1, ctx->cu_count), ctx->seed_run,
+                                         ctx->seed_wg, ctx->seed_launch_log2);
+  PowSeedIn* const H = ctx->h_seed.p;
+  memset(H, 0, sizeof *H);
+  H->n_targets = (uint32_t)n_targets;
+  for (size_t k = 0; k < n_targets; ++k) {
+    H->tgt[k][0] = tgt[k][0];
+    H->tgt[k][1] = tgt[k][1];
+    H->pair[tgt[k][0] >> 24] |= 1ull << ((tgt[k][0] >> 18) & 63u);
+    H->pair2[(tgt[k][0] >> 12) & 63u] |= 1ull << ((tgt[k][0] >> 6) & 63u);
+  }
+  PowSeedLaunch L;
+  memset(&L, 0, sizeof L);
+  L.seed_first = seed_first;
+  L.run = plan.run;
+  L.nwg = plan.nwg;
+  uint32_t first[POW_RAND_WORDS], to_next[POW_RAND_WORDS];  // to the call's first trial; from a slice's to the next's
+  pow_rand_power(9ull * L.run * ((uint64_t)L.nwg * 256u - 1u), H->step);
+  pow_rand_power(9ull * trial_start, first);
+  pow_rand_power(9ull * plan.slice, to_next);
+  std::vector<SeedHit> hits;
+  for (uint32_t base = 0; base < n_seeds; base += plan.tile) {
+    L.pos_base = base;
+    L.n_seeds = std::min(plan.tile, n_seeds - base);
+    memcpy(H->jump, first, sizeof first);
+    for (uint64_t off = 0; off < trial_count; off += plan.slice) {
+      if (cancel_moved(cancel_word, epoch)) return f.finish(0);
+      const uint64_t n = std::min<uint64_t>(plan.slice, trial_count - off);
+      L.count = (uint32_t)n;
+      if (ctx->rand_tab_run != plan.run) {  // the tables of this T, as pow_mine_rand's
+        pow_rand_tables(plan.run, ctx->h_rtab.p);
+        ctx->rand_tab_run = 0;
+        HIP_OK(hipMemcpyAsync(ctx->d_rtab.p, ctx->h_rtab.p, POW_RAND_TAB_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice,
+                              ctx->stream));
+      }
+      HIP_OK(hipMemcpyAsync(ctx->d_seed.p, H, sizeof *H, hipMemcpyHostToDevice, ctx->stream));
+      HIP_OK(hipMemsetAsync(ctx->d_sout.p, 0, offsetof(PowSeedOut, rec), ctx->stream));
+      if (int rc = timed_begin(ctx)) return rc;
+      HIP_OK(pow_launch_seed(ctx->stream, L, ctx->d_seed.p, ctx->d_rtab.p, ctx->d_sout.p));
+      HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+      HIP_OK(hipMemcpyAsync(ctx->h_sout.p, ctx->d_sout.p, sizeof(PowSeedOut), hipMemcpyDeviceToHost, ctx->stream));
+      const uint64_t pairs = (uint64_t)L.n_seeds * n;
+      if (int rc = timed_end(ctx, "seed search launch", 2ull * pairs, 1u, &f.total)) return rc;  // 2 ns per pair
+      ctx->rand_tab_run = plan.run;
+      f.total.hashes += pairs;
+      const PowSeedOut& r = *ctx->h_sout.p;
+      if (r.n > POW_SEED_DEV_CAP)
+        return fail(POW_EHIP, "seed search launch: %u matches, the device list holds %u", r.n, POW_SEED_DEV_CAP);
+      for (uint32_t i = 0; i < r.n; ++i) {
+        const PowSeedRec& m = r.rec[i];
+        if (m.pos < base || m.pos - base >= L.n_seeds || m.target >= n_targets || m.rel >= n)
+          return fail(POW_EHIP, "seed search launch: reports position %u, target %u at trial %u outside its tile", m.pos,
+                      m.target, m.rel);
+        // The device's generator against the host's: one that drifted must not name a seed.
+        const uint64_t trial = trial_start + off + m.rel;
+        char want[POW_NONCE_SIZE];
+        if (int rc = pow_rand_nonces(seed_first + m.pos, trial, 1, want)) return rc;
+        if (memcmp(want, nonces + m.target * POW_NONCE_SIZE, POW_NONCE_SIZE - 1) != 0)
+          return fail(POW_EHIP, "seed search launch: the device matched target %u at trial %llu of seed %u, the host's generator gives \"%.9s\"",
+                      m.target, (unsigned long long)trial, seed_first + m.pos, want);
+        hits.push_back(SeedHit{m.pos, m.target, trial});
+      }
+      pow_rand_mul(H->jump, to_next, H->jump);
+    }
+  }
+  std::sort(hits.begin(), hits.end(), [](const SeedHit& a, const SeedHit& b) {
+    return a.pos != b.pos ? a.pos < b.pos : a.trial != b.trial ? a.trial < b.trial : a.target < b.target;
+  });
+  *n_found = hits.size();
+  for (size_t i = 0; i < std::min(cap, hits.size()); ++i)
+    out[i] = pow_seed_match{seed_first + hits[i].pos, hits[i].target, hits[i].trial};
+  if (hits.size() > cap) return f.finish(fail(POW_ENOSPC, "%zu matches, cap %zu", hits.size(), cap));
+  return f.finish(hits.empty() ? 0 : 1);
+}
+
 int pow_cancel(pow_ctx* ctx, uint32_t epoch) {
   if (!ctx) return fail(POW_EINVAL, "null");
   // A plain store into mapped host memory: no HIP call, no stream; the

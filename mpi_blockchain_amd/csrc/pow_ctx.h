@@ -210,6 +210,44 @@ struct PowRandLaunch {
   uint32_t pad;
 };
 
+// K9 (pow_seed_kernel, pow_seed.hip), one launch per (tile of seeds, slice of
+// trials) of pow_find_seed: K8's walk without the hash, every seed of the tile
+// seeded on the device.  What goes up per launch, in one copy:
+struct PowSeedIn {
+  uint32_t jump[POW_RAND_WORDS];   // x^(9 x the slice's first trial): from a seed's draw 0 to the launch's start
+  uint32_t n_targets;              // 1..POW_SEED_MAX_TARGETS
+  uint32_t step[POW_RAND_WORDS];   // x^(9 T (G - 1)): from the end of a lane's run to its next
+  uint32_t pad;
+  unsigned long long pair[62];     // bit d1 of pair[d0]: some target begins with the digits d0, d1
+  unsigned long long pair2[62];    // bit d3 of pair2[d2]: some target has the digits d2, d3 in third and fourth place
+  uint32_t tgt[POW_SEED_MAX_TARGETS][2];  // pow_seed_pack of each target
+};
+static_assert(sizeof(PowSeedIn) % 8 == 0 && offsetof(PowSeedIn, pair) % 8 == 0, "dwords, the table on 8 bytes");
+// ... and what comes down: a counter (reset by the host before the launch) and
+// the matches in the order their lanes reserved them.  A launch that counts more
+// than the list holds fails the call; 64 targets that all occur in one launch
+// under seeds 0 and 1 are 128.
+#define POW_SEED_DEV_CAP 1024u
+struct PowSeedRec {
+  uint32_t pos;     // the seed's position in the request
+  uint32_t target;  // index into the targets
+  uint32_t rel;     // the trial relative to the launch's first
+};
+struct PowSeedOut {
+  uint32_t n;       // matches of the launch (atomic add)
+  uint32_t pad;
+  PowSeedRec rec[POW_SEED_DEV_CAP];
+};
+// The arguments of a launch; gridDim.x = n_seeds x nwg.
+struct PowSeedLaunch {
+  uint32_t seed_first;  // the request's first seed; the seed at position p is seed_first + p mod 2^32
+  uint32_t pos_base;    // the position of the tile's first seed
+  uint32_t n_seeds;     // seeds of the tile
+  uint32_t count;       // trials of the slice, <= 2^26
+  uint32_t run;         // T = 31 x 2^j, j <= 5
+  uint32_t nwg;         // workgroups per seed, <= POW_RAND_MAX_WG
+};
+
 struct pow_ctx {
   int device = 0;
   int cu_count = 0;
@@ -278,7 +316,12 @@ struct pow_ctx {
   DevBuf<uint32_t> d_rtab;           // the two tables of the run T below (pow_rand_tables) ...
   HostBuf<uint32_t> h_rtab;          // ... and the pinned twin they go up from
   uint32_t rand_tab_run = 0;         // the T the tables on the device were made for (0 = none yet)
+  DevBuf<PowSeedIn> d_seed;          // pow_find_seed: a launch's input on the device ...
+  HostBuf<PowSeedIn> h_seed;         // ... and its pinned twin
+  DevBuf<PowSeedOut> d_sout;         // the launch's matches ...
+  HostBuf<PowSeedOut> h_sout;        // ... and their pinned twin (d_rtab, h_rtab: K9 starts from K8's tables)
   void release_buffers() {  // every holder above
+    d_seed.release(), h_seed.release(), d_sout.release(), h_sout.release();
     d_rand.release(), h_rand.release(), d_rrec.release(), h_rrec.release();
     d_rnslot.release(), d_rnchar.release(), d_rtab.release(), h_rtab.release();
     d_out.release(), d_alt.release(), d_sort_tmp.release();
@@ -309,6 +352,9 @@ struct pow_ctx {
   unsigned rand_run = 0;          // pow_mine_rand: K8's run T (0 = the plan)
   int rand_lanes_log2 = -1;       // K8's grid: 2^this lanes (-1 = the plan: K4's grid)
   unsigned rand_launch_log2 = 26; // trials per K8 launch = 2^this
+  unsigned seed_run = 0;          // pow_find_seed: K9's run T (0 = the plan)
+  unsigned seed_wg = 0;           // K9's workgroups per seed (0 = the plan)
+  unsigned seed_launch_log2 = POW_SEED_LAUNCH_LOG2;  // (seed, trial) pairs per K9 launch = 2^this
   // K1' and K2' launches as AQL packets (pow_aql.cpp) instead of
   // hipLaunchKernel: test library only, opt-in there; null = the HIP launch
   // path, the only one the shipped library has.
@@ -344,6 +390,8 @@ hipError_t pow_launch_race(hipStream_t stream, const PowRaceLaunch& L, const uin
                            const PowRaceIn* in, PowSealCtl* ctl, PowChainSlot* slots, PowRaceRec* rec);
 hipError_t pow_launch_rand(hipStream_t stream, const PowRandLaunch& L, const PowRandIn* in, const uint32_t* tab,
                            PowBatchCtl* ctl, PowChainSlot* slots, uint32_t* slot_nonce, PowRandRec* rec);
+hipError_t pow_launch_seed(hipStream_t stream, const PowSeedLaunch& L, const PowSeedIn* in, const uint32_t* tab,
+                           PowSeedOut* out);
 hipError_t pow_sort_u32(void* temp, size_t* temp_bytes, uint32_t* keys, uint32_t* alt, uint32_t n,
                         uint32_t** sorted, hipStream_t stream);
 hipError_t pow_launch_search_lat(bool full, bool any, bool asm_groups, unsigned grid, hipStream_t stream,

@@ -50,6 +50,11 @@ void configure(pow_ctx* ctx) {
   if (const char* rr = getenv("POW_RAND_RUN")) ctx->rand_run = (unsigned)std::min((unsigned long)POW_RAND_MAX_RUN, strtoul(rr, nullptr, 0));
   if (const char* rg = getenv("POW_RAND_LANES_LOG2")) ctx->rand_lanes_log2 = (int)std::min(16ul, strtoul(rg, nullptr, 0));
   if (const char* rn = getenv("POW_RAND_LAUNCH_LOG2")) ctx->rand_launch_log2 = (unsigned)std::min(26ul, strtoul(rn, nullptr, 0));
+  // pow_find_seed: K9's run T (rounded down to 31 x 2^j, 31 to 992), its workgroups per seed (1 to 256)
+  // and the (seed, trial) pairs per launch (2^n, at most 2^30); the result must not depend on any of them
+  if (const char* sr = getenv("POW_SEED_RUN")) ctx->seed_run = (unsigned)std::min(992ul, strtoul(sr, nullptr, 0));
+  if (const char* sw = getenv("POW_SEED_WG")) ctx->seed_wg = (unsigned)std::min((unsigned long)POW_RAND_MAX_WG, strtoul(sw, nullptr, 0));
+  if (const char* sn = getenv("POW_SEED_LAUNCH_LOG2")) ctx->seed_launch_log2 = (unsigned)std::min((unsigned long)POW_SEED_LAUNCH_LOG2, strtoul(sn, nullptr, 0));
   if (const char* g = getenv("POW_GRID_PER_CU")) {  // launch-geometry experiments
     const int per = atoi(g);
     if (per > 0 && per <= 64) ctx->grid_full = (unsigned)ctx->cu_count * (unsigned)per;

@@ -400,6 +400,53 @@ void pow_rand_tables(uint32_t run, uint32_t* tab) {
   }
 }
 
+// ---------------- pow_find_seed (K9) ----------------
+
+bool pow_seed_pack(const char* nonce, uint32_t w[2]) {
+  uint32_t d[POW_NONCE_SIZE - 1];
+  for (int i = 0; i < POW_NONCE_SIZE - 1; ++i) {  // digit_char's inverse
+    const char c = nonce[i];
+    if (c >= 'a' && c <= 'z')
+      d[i] = (uint32_t)(c - 'a');
+    else if (c >= 'A' && c <= 'Z')
+      d[i] = 26u + (uint32_t)(c - 'A');
+    else if (c >= '0' && c <= '9')
+      d[i] = 52u + (uint32_t)(c - '0');
+    else
+      return false;
+  }
+  w[0] = (d[0] << 24) | (d[1] << 18) | (d[2] << 12) | (d[3] << 6) | d[4];
+  w[1] = (d[5] << 18) | (d[6] << 12) | (d[7] << 6) | d[8];
+  return true;
+}
+
+PowSeedPlan pow_seed_plan(uint32_t n_seeds, uint64_t trial_count, uint32_t cu_count, unsigned run_override,
+                          unsigned wg_override, unsigned launch_log2) {
+  PowSeedPlan p;
+  const uint64_t cap = 1ull << std::min(launch_log2, POW_SEED_LAUNCH_LOG2);  // pairs per launch: the cancel latency
+  // A slice is at most 2^26 trials, K8's launch: with a pass of the grid below
+  // 2^26 too, a lane's relative trial stays below 2^27.
+  p.slice = std::max<uint64_t>(1, std::min<uint64_t>(trial_count, std::min<uint64_t>(1ull << 26, cap)));
+  uint64_t tile = std::min<uint64_t>(std::max(1u, n_seeds), std::max<uint64_t>(1, cap / p.slice));
+  // Workgroups per seed: eight per CU over the tile fill the chip, and none
+  // whose first run (at the least T) would start past the slice.
+  const uint64_t one = 256ull * POW_RAND_WORDS;
+  uint64_t nwg = (8ull * std::max(1u, cu_count) + tile - 1) / tile;
+  nwg = std::min(nwg, (p.slice + one - 1) / one);
+  if (wg_override) nwg = wg_override;
+  p.nwg = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(nwg, POW_RAND_MAX_WG));
+  p.tile = (uint32_t)std::min<uint64_t>(tile, (1u << 16) / p.nwg);
+  // T = 31 x 2^j: the largest at which one pass of the grid still lies inside
+  // the slice, so that every lane has a run and hops as seldom as can be.
+  uint32_t run = POW_RAND_WORDS;
+  if (run_override)
+    while (run < 32u * POW_RAND_WORDS && 2 * run <= run_override) run *= 2;
+  else
+    while (run < 32u * POW_RAND_WORDS && (uint64_t)p.nwg * 256u * (2 * run) <= p.slice) run *= 2;
+  p.run = run;
+  return p;
+}
+
 extern "C" {
 
 const char* pow_last_error(void) { return g_err.c_str(); }

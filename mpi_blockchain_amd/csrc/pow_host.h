@@ -1,7 +1,7 @@
 // HIP-free host code of the miner (pow_host.cpp): the error string, the
 // clock, the per-template precompute, the launch splitting and the plans of
 // the fused mining calls (K4, K5, K6), and the reference's rand() stream with
-// the plan of K8.  Pure integer code: it compiles with a
+// the plans of K8 and K9.  Pure integer code: it compiles with a
 // plain C++ compiler and no ROCm include path, so tests/host_unit.cpp and
 // tests/{race,fused}_plan_unit.cpp run it on the CPU under sanitizers.  Library-internal
 // (pow_api.cpp, pow_group.cpp, pow_aql.cpp, pow_hooks.cpp); not part of the C
@@ -131,5 +131,29 @@ PowRandPlan pow_rand_plan(unsigned diff, uint64_t trial_count, uint32_t cu_count
 // POW_RAND_MAX_WG.  tab holds POW_RAND_TAB_WORDS words.
 #define POW_RAND_TAB_WORDS (POW_RAND_WORDS * 256u + POW_RAND_MAX_WG * POW_RAND_WORDS)
 void pow_rand_tables(uint32_t run, uint32_t* tab);
+
+// ---- pow_find_seed (K9): the inverse of pow_rand_nonces ----
+// A target's nine base-62 digits as the kernel compares them: w[0] = digits
+// 0..4 and w[1] = digits 5..8, six bits each, the first digit highest.
+// false, with w not written: a character outside a-z, A-Z, 0-9 in nonce[0..8].
+bool pow_seed_pack(const char* nonce, uint32_t w[2]);
+// The plan of pow_find_seed: the request's n_seeds x trial_count pairs are cut
+// into tiles of `tile` seeds and slices of `slice` trials, one launch per (tile,
+// slice) with `nwg` workgroups per seed whose lanes walk runs of `run` trials.
+// Pure: the chip's CU count and the test library's overrides (run_override,
+// wg_override: 0 = the plan; launch_log2: POW_SEED_LAUNCH_LOG2 is the shipped
+// value).  It holds that 1 <= nwg <= POW_RAND_MAX_WG (table B), run = 31 x 2^j
+// with j <= 5 (an override: rounded down to one, at least 31), tile x nwg <=
+// 2^16 workgroups, 1 <= slice <= 2^26 and nwg x 256 x run <= 2^26 (a lane's
+// relative trial stays below 2^27) and tile x slice <= 2^launch_log2 pairs.
+#define POW_SEED_LAUNCH_LOG2 30u
+struct PowSeedPlan {
+  uint32_t tile;   // seeds per launch
+  uint32_t nwg;    // workgroups per seed
+  uint32_t run;    // T
+  uint64_t slice;  // trials per launch
+};
+PowSeedPlan pow_seed_plan(uint32_t n_seeds, uint64_t trial_count, uint32_t cu_count, unsigned run_override,
+                          unsigned wg_override, unsigned launch_log2);
 
 #pragma GCC visibility pop

@@ -12,7 +12,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import HASH_SIZE, NONCE_SIZE, Block, PowStats, check, load
+from ._lib import HASH_SIZE, NONCE_SIZE, SEED_MAX_SEEDS, SEED_MAX_TARGETS, Block, PowStats, SeedMatchRec, check, load
 from .block import DEFAULT_DIFFICULTY, field, nonce_from_counter
 
 
@@ -77,6 +77,31 @@ class MineRandResult:
     trial: int            # the lowest solving trial of the window: the reference's stream then stands at trial + 1
     hashes: int           # trials issued
     kernel_ms: float      # GPU time of the call
+
+
+@dataclass(frozen=True)
+class SeedMatch:
+    seed: int             # the srand() argument
+    trial: int            # absolute trial: rand_nonces(seed, trial, 1) gives the target
+    target: int           # index into the nonces that were searched for
+
+
+@dataclass
+class RandProvenance:
+    """What :func:`audit_rand_provenance` found; per-owner entries are keyed by
+    ``node_owner_number``, per-block ones follow the chain's order."""
+
+    seeds: dict               # owner -> the seed that explains most of its blocks (lowest in the window on a tie); None if none does
+    trials: list              # per block: its trial under its owner's seed, or None
+    not_from_generator: list  # positions of the blocks no (seed, trial) of the window explains
+    one_seed: dict            # owner -> every block of the owner matches under its seed
+    seed_in_window: dict      # owner -> that seed minus the owner's rank lies within the seed window
+    trials_increase: dict     # owner -> its trials strictly increase with its blocks' index
+    matches: list             # every SeedMatch of the search
+
+    @property
+    def ok(self) -> bool:
+        return bool(self.seeds) and all(all(v.values()) for v in (self.one_seed, self.seed_in_window, self.trials_increase))
 
 
 def rand_nonces(seed: int, start: int = 0, n: int = 1) -> list[bytes]:
@@ -281,6 +306,26 @@ class GpuMiner:
             return None
         return MineRandResult(out, trial.value, hashes.value, self.stats()["kernel_ms"])
 
+    def find_seed(self, nonces, seed_first: int, n_seeds: int, start: int = 0, count: int = 1 << 32,
+                  cap: int = 1024, epoch: int | None = None) -> list[SeedMatch]:
+        """pow_find_seed, the inverse of :func:`rand_nonces`: every (seed,
+        trial) with seed in [seed_first, seed_first + n_seeds) mod 2^32 and
+        trial in [start, start + count) whose nine characters equal one of
+        `nonces` (1 to 64 byte strings of at least nine characters), sorted by
+        (position of the seed in the window, trial, target).  Seeds 0 and 1
+        share a stream and are both reported.  More matches than `cap` raise
+        PowError (POW_ENOSPC); [] also if :meth:`cancel` was called meanwhile."""
+        nonces = [bytes(n) for n in nonces]
+        if any(len(n) < NONCE_SIZE - 1 for n in nonces):
+            raise ValueError("a nonce has nine characters")
+        buf = b"".join(n[:NONCE_SIZE - 1] + b"\0" for n in nonces)
+        out = (SeedMatchRec * max(cap, 1))()
+        n_found = ctypes.c_size_t()
+        ep = self._cancel.value if epoch is None else epoch
+        check(self.L.pow_find_seed(self.ctx, buf, len(nonces), seed_first & 0xFFFFFFFF, n_seeds, start, count,
+                                   ctypes.byref(self._cancel), ep, out, cap, ctypes.byref(n_found), None), self.L)
+        return [SeedMatch(out[i].seed, out[i].trial, out[i].target) for i in range(n_found.value)]
+
     def mine_chain(self, parent: Block, n: int, difficulty: int = DEFAULT_DIFFICULTY, owner: int = 0,
                    created_at=None, ctr_start: int = 0, ctr_count: int = 1 << 32,
                    epoch: int | None = None) -> MineChainResult:
@@ -476,9 +521,56 @@ def replay_proof_of_work(miner: GpuMiner, last: Block, rank: int, seed: int, n_b
     return blocks, at
 
 
+def audit_rand_provenance(miner: GpuMiner, chain, seed_window: tuple[int, int] | None = None,
+                          count: int = 1 << 32) -> RandProvenance:
+    """Were these blocks mined by reference ranks, and from which seeds?  The
+    reference seeds with ``srand(time(NULL) + rank)`` (node.cpp:386) and keeps
+    the seed nowhere, so it is recovered: one :meth:`GpuMiner.find_seed` over
+    every block's nonce, trials [0, count) of every seed of the window.
+    chain: at most 64 ``Block`` s, tip first.  seed_window: (first seed, number
+    of seeds); None: from an hour before the earliest ``created_at`` to the
+    latest plus the highest rank.  Nothing is raised on a failed verdict: they
+    are all in the result (:class:`RandProvenance`)."""
+    chain = list(chain)
+    if not 1 <= len(chain) <= SEED_MAX_TARGETS:
+        raise ValueError(f"a chain of 1 to {SEED_MAX_TARGETS} blocks")
+    if seed_window is None:
+        stamps = [b.created_at for b in chain]
+        first = max(0, min(stamps) - 3600)
+        seed_window = (first, max(stamps) + max(b.node_owner_number for b in chain) - first + 1)
+    first, n_seeds = seed_window[0] & 0xFFFFFFFF, seed_window[1]
+    if not 1 <= n_seeds <= SEED_MAX_SEEDS:
+        raise ValueError(f"a window of {n_seeds} seeds (1 to {SEED_MAX_SEEDS})")
+    nonces = [field(b, "nonce")[:NONCE_SIZE - 1] for b in chain]
+    # a nonce with a byte outside the alphabet is not the generator's: searched for apart from the rest
+    drawn = [k for k, n in enumerate(nonces) if len(n) == NONCE_SIZE - 1 and n.isalnum() and n.isascii()]
+    found = miner.find_seed([nonces[k] for k in drawn], first, n_seeds, 0, count, cap=1 << 16) if drawn else []
+    matches = [SeedMatch(m.seed, m.trial, drawn[m.target]) for m in found]
+    pos = lambda seed: (seed - first) & 0xFFFFFFFF  # noqa: E731
+    by_block: dict = {}
+    for m in matches:  # block -> seed -> its lowest trial
+        by_block.setdefault(m.target, {}).setdefault(m.seed, m.trial)
+    rep = RandProvenance({}, [None] * len(chain), [k for k in range(len(chain)) if k not in by_block], {}, {}, {}, matches)
+    for owner in sorted({b.node_owner_number for b in chain}):
+        mine = [k for k, b in enumerate(chain) if b.node_owner_number == owner]
+        cover: dict = {}
+        for k in mine:
+            for seed in by_block.get(k, {}):
+                cover[seed] = cover.get(seed, 0) + 1
+        seed = min(cover, key=lambda s: (-cover[s], pos(s))) if cover else None
+        rep.seeds[owner] = seed
+        rep.one_seed[owner] = seed is not None and cover[seed] == len(mine)
+        rep.seed_in_window[owner] = seed is not None and pos(seed - owner) < n_seeds
+        for k in mine:
+            rep.trials[k] = by_block.get(k, {}).get(seed)
+        order = [rep.trials[k] for k in sorted(mine, key=lambda k: chain[k].index)]
+        rep.trials_increase[owner] = None not in order and all(a < b for a, b in zip(order, order[1:]))
+    return rep
+
+
 def block_hex(b: Block) -> str:
     return field(b, "block_hash").split(b"\0", 1)[0].decode()
 
 
-__all__ = ["GpuMiner", "DeviceBuffer", "StopBoard", "MineResult", "MineRandResult", "rand_nonces", "replay_proof_of_work", "MineChainResult", "MineBatchResult", "VerifyResult", "VerifyChainsResult", "refresh_template", "proof_of_work_round", "block_hex",
+__all__ = ["GpuMiner", "DeviceBuffer", "StopBoard", "MineResult", "MineRandResult", "rand_nonces", "replay_proof_of_work", "SeedMatch", "RandProvenance", "audit_rand_provenance", "MineChainResult", "MineBatchResult", "VerifyResult", "VerifyChainsResult", "refresh_template", "proof_of_work_round", "block_hex",
            "nonce_from_counter"]

@@ -1,0 +1,228 @@
+"""pow_find_seed (K9) on the GPU, at the smallest shapes at which the kernel can
+go wrong.  The expected sets come from tests/seed_util.py's brute force over
+pow_rand_nonces and from tests/golden/rand_replay.json, which the reference's
+own gen_random_nonce made; both are pinned on the CPU in test_seed_host.py."""
+import ctypes
+import os
+import subprocess
+
+import pytest
+
+import seed_util
+from seed_util import call, check_against_ref, golden_nonces, miner_with, nonce_at
+from mpi_blockchain_amd import _lib
+from mpi_blockchain_amd.block import make_block
+from mpi_blockchain_amd.miner import GpuMiner, SeedMatch, StopBoard, audit_rand_provenance
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "mpi_blockchain_amd")
+SEED = 1700000003  # time + rank
+LIMIT = seed_util.LIMIT
+
+
+@pytest.fixture(scope="module")
+def shipped():
+    with GpuMiner(0) as m:
+        yield m
+
+
+def placed(seed, trials):
+    """Targets at the given trials of a seed, and the matches they make there."""
+    return [nonce_at(seed, t) for t in trials], [(seed, k, t) for k, t in enumerate(trials)]
+
+
+# ---- 1: the unrolled iteration's boundaries, and the device's seeding ----
+@pytest.mark.parametrize("seed", [SEED, 0x80000000, 0xFFFFFFFF])
+def test_unroll_boundaries(shipped, seed):
+    """Trials 0, 30, 31, 32 and 63: the start, the end and both sides of one
+    31-trial iteration.  Seeds at or above 2^31 take the negative branch of the
+    Lehmer step.  The targets are the reference's own first 64 nonces."""
+    table = golden_nonces(seed)
+    trials = [0, 30, 31, 32, 63]
+    got = check_against_ref(shipped, [table[t] for t in trials], seed, 1, 0, 64)
+    assert got == [(seed, k, t) for k, t in enumerate(trials)]
+    # ... and all 64 of them, each at its own trial
+    assert check_against_ref(shipped, table, seed, 1, 0, 64) == [(seed, t, t) for t in range(64)]
+
+
+# ---- 2: lane, workgroup and pass seams ----
+@pytest.mark.parametrize("run", [31, 62])
+def test_lane_workgroup_and_pass_seams(run):
+    trials = sorted({t for r in (31, run) for t in (r * 256 - 1, r * 256, r * 512 - 1, r * 512, r * 512 + 1)} |
+                    {run - 1, run, 2 * run})
+    nonces, want = placed(SEED, trials)
+    with miner_with(POW_SEED_RUN=run, POW_SEED_WG=2) as m:
+        assert check_against_ref(m, nonces, SEED, 1, 0, 62 * 512 + 64) == want
+        assert m.stats()["launches"] == 1
+
+
+# ---- 3: the seam between two launches over the same seeds ----
+def test_slice_seams():
+    start, n = 5, 1 << 13
+    trials = [start, start + n - 1, start + n, start + 2 * n - 1, start + 2 * n, start + 3 * n - 1]
+    nonces, want = placed(SEED, trials)
+    with miner_with(POW_SEED_LAUNCH_LOG2=13) as m:
+        assert check_against_ref(m, nonces, SEED, 1, start, 3 * n) == want
+        assert m.stats()["launches"] == 3
+
+
+# ---- 4: the window's ends: lanes walk past the upper one ----
+def test_window_exclusion(shipped):
+    start, count = 1000, 500
+    nonces, want = placed(SEED, [start - 1, start + count])
+    rc, got, n_found, pairs, untouched = call(shipped, nonces, SEED, 1, start, count)
+    assert (rc, got, n_found, pairs, untouched) == (0, [], 0, count, True), shipped.L.pow_last_error()
+    assert check_against_ref(shipped, nonces, SEED, 1, start - 1, count + 2) == want
+    # one side at a time
+    assert check_against_ref(shipped, nonces, SEED, 1, start - 1, count + 1) == want[:1]
+    assert check_against_ref(shipped, nonces, SEED, 1, start, count + 1) == want[1:]
+
+
+# ---- 5: a deep start: the launch's polynomial ----
+def test_deep_start(shipped):
+    start, count = (1 << 40) + 7, 4096
+    nonces, want = placed(SEED, [start, start + 30, start + 31, start + 2047, start + 4095])
+    assert check_against_ref(shipped, nonces, SEED, 1, start, count) == want
+    # the last trial below POW_RAND_TRIAL_LIMIT
+    nonces, want = placed(0x80000000, [LIMIT - 64, LIMIT - 1])
+    assert check_against_ref(shipped, nonces, 0x80000000, 1, LIMIT - 64, 64) == want
+
+
+# ---- 6: a window of seeds through 2^32, and seeds 0 and 1 ----
+def test_seed_wrap_and_the_tie_of_0_and_1(shipped):
+    nonces = [nonce_at(1, 5)]
+    want = [(0, 0, 5), (1, 0, 5)]  # positions 2 and 3 of the window
+    assert check_against_ref(shipped, nonces, 0xFFFFFFFE, 4, 0, 64) == want
+    rc, got, n_found, pairs, untouched = call(shipped, nonces, 0xFFFFFFFE, 4, 0, 64, cap=1)
+    assert (rc, got, n_found, untouched) == (_lib.POW_ENOSPC, want[:1], 2, True)
+    assert b"2 matches, cap 1" in shipped.L.pow_last_error()
+    # count only
+    rc = shipped.L.pow_find_seed(shipped.ctx, seed_util.pack(nonces), 1, 0xFFFFFFFE, 4, 0, 64, None, 0, None, 0,
+                                 ctypes.byref(ctypes.c_size_t()), None)
+    assert rc == _lib.POW_ENOSPC
+    with pytest.raises(_lib.PowError):
+        shipped.find_seed(nonces, 0xFFFFFFFE, 4, 0, 64, cap=1)
+    assert shipped.find_seed(nonces, 0xFFFFFFFE, 4, 0, 64) == [SeedMatch(0, 5, 0), SeedMatch(1, 5, 0)]
+
+
+# ---- 7: the most targets ----
+def test_multi_target(shipped):
+    """64 targets drawn from 8 seeds x 4,096 trials: exactly the brute force's
+    set, none missing and no false match; then with the last one replaced by a
+    nonce the window does not hold (a call takes 64 targets at the most)."""
+    lcg, spots = 12345, []
+    for _ in range(64):
+        lcg = (lcg * 1664525 + 1013904223) & 0xFFFFFFFF
+        spots.append(((lcg >> 8) % 8, (lcg >> 11) % 4096))
+    nonces = [nonce_at(SEED + p, 77 + t) for p, t in spots]
+    got = check_against_ref(shipped, nonces, SEED, 8, 77, 4096)
+    assert sorted(got) == sorted((SEED + p, k, 77 + t) for k, (p, t) in enumerate(spots))
+    absent = nonce_at(SEED + 8, 77)  # the seed after the window's last
+    got = check_against_ref(shipped, nonces[:63] + [absent], SEED, 8, 77, 4096)
+    assert len(got) == 63 and all(k != 63 for _, k, _ in got)
+    # the same nonce twice in the list is reported under both indices
+    assert check_against_ref(shipped, [nonces[0], nonces[1], nonces[0]], SEED, 8, 77, 4096, cap=8)
+
+
+# ---- 8: the seam between two tiles of seeds ----
+def test_seed_tile_seam():
+    """256 workgroups per seed leave 2^16 / 256 = 256 seeds to a launch: 257
+    seeds are two tiles."""
+    first = 0xFFFFFF80  # ... and the window wraps inside the first
+    spots = [(0, 0), (255, 40), (255, 511), (256, 0), (256, 33)]
+    nonces = [nonce_at(first + p, t) for p, t in spots]
+    with miner_with(POW_SEED_WG=256) as m:
+        got = check_against_ref(m, nonces, first, 257, 0, 512)
+        assert got == [((first + p) & 0xFFFFFFFF, k, t) for k, (p, t) in enumerate(spots)]
+        assert m.stats()["launches"] == 2
+
+
+# ---- 9: the reference's own blocks ----
+def test_golden_end_to_end(shipped):
+    for r in seed_util.replay()["replays"]:
+        seed, blocks = r["seed"], [_lib.Block.from_buffer_copy(bytes.fromhex(b["block_hex"])) for b in r["blocks"]]
+        nonces = [bytes(b.nonce) for b in blocks]
+        twins = {0, 1} if seed in (0, 1) else {seed}
+        want = [(s, k, b["trial"]) for s in sorted(twins, key=lambda s: (s - (seed - 3)) & 0xFFFFFFFF)
+                for k, b in enumerate(r["blocks"])]
+        got = check_against_ref(shipped, nonces, seed - 3, 7, 0, r["total_trials"])
+        assert got == want, (seed, got, want)
+        # the audit, over a window that holds the seed and the seed minus the rank
+        rep = audit_rand_provenance(shipped, blocks[::-1], (seed - r["rank"] - 1, r["rank"] + 3), r["total_trials"])
+        rank = r["rank"]
+        assert rep.ok and rep.not_from_generator == [], rep
+        assert rep.seeds[rank] in twins and rep.trials == [b["trial"] for b in r["blocks"]][::-1]
+        assert rep.one_seed == {rank: True} and rep.seed_in_window == {rank: True} and rep.trials_increase == {rank: True}
+        # the same blocks in the wrong order of indices fail that verdict alone
+        swapped = [_lib.Block.from_buffer_copy(bytes(b)) for b in blocks]
+        swapped[0].index, swapped[2].index = swapped[2].index, swapped[0].index
+        rep = audit_rand_provenance(shipped, swapped[::-1], (seed - rank - 1, rank + 3), r["total_trials"])
+        assert not rep.ok and rep.one_seed == {rank: True} and rep.trials_increase == {rank: False}
+
+
+def test_audit_reports_counter_nonces_as_not_from_the_generator(shipped):
+    parent = make_block(0, 0, 9, 1700000000)
+    res = shipped.mine_chain(parent, 3, 9, owner=1, created_at=[1700000000, 1700000017, 1700000034])
+    assert res.complete
+    rep = audit_rand_provenance(shipped, list(res.blocks), (1700000000 - 8, 64), 1 << 12)
+    assert not rep.ok and rep.not_from_generator == [0, 1, 2] and rep.matches == []
+    assert rep.seeds == {1: None} and rep.trials == [None] * 3
+    assert rep.one_seed == {1: False} and rep.seed_in_window == {1: False} and rep.trials_increase == {1: False}
+    # the default window: from an hour before the first block to the last one's second plus the rank
+    rep = audit_rand_provenance(shipped, list(res.blocks), None, 64)
+    assert rep.not_from_generator == [0, 1, 2] and shipped.stats()["hashes"] == (3600 + 34 + 1 + 1) * 64
+
+
+# ---- 10: cancel, the stop board and the statistics ----
+def test_cancel_at_entry(shipped):
+    nonces, _ = placed(SEED, [3])
+    word = ctypes.c_uint32(1)
+    rc, got, n_found, pairs, untouched = call(shipped, nonces, SEED, 1, 0, 64, cancel=ctypes.byref(word), epoch=0)
+    assert (rc, got, n_found, pairs, untouched) == (0, [], 0, 0, True)
+    assert shipped.stats()["launches"] == 0 and shipped.stats()["hashes"] == 0
+    rc, got, *_ = call(shipped, nonces, SEED, 1, 0, 64, cancel=ctypes.byref(word), epoch=1)
+    assert rc == 1 and got == [(SEED, 0, 3)]
+
+
+def test_context_bound_to_a_stop_board_is_refused():
+    nonces, _ = placed(SEED, [3])
+    with GpuMiner(0) as m, StopBoard(2) as board:
+        m.bind_board(board, 0, 1)
+        rc, got, n_found, pairs, untouched = call(m, nonces, SEED, 1, 0, 64)
+        assert (rc, n_found, pairs, untouched) == (_lib.POW_EINVAL, 12345, 12345, True)
+        assert b"stop board" in m.L.pow_last_error()
+        m.bind_board(None)
+        assert call(m, nonces, SEED, 1, 0, 64)[:3] == (1, [(SEED, 0, 3)], 1)
+
+
+def test_stats(shipped):
+    nonces, want = placed(SEED + 63, [(1 << 20) - 1])
+    # 64 seeds x 2^20 trials are 2^26 pairs: one launch of the shipped plan
+    rc, got, n_found, pairs, _ = call(shipped, nonces, SEED, 64, 0, 1 << 20)
+    assert (rc, got, n_found, pairs) == (1, want, 1, 1 << 26), shipped.L.pow_last_error()
+    s = shipped.stats()
+    assert (s["launches"], s["hashes"]) == (1, 1 << 26) and s["kernel_ms"] > 0
+    # 2^13 pairs per launch: a seed per tile, and ceil((3 x 2^13 + 5) / 2^13) = 4 slices for each of 4 seeds
+    count = 3 * (1 << 13) + 5
+    nonces, want = placed(SEED + 3, [count - 1])
+    with miner_with(POW_SEED_LAUNCH_LOG2=13, POW_SEED_WG=1) as m:
+        rc, got, n_found, pairs, _ = call(m, nonces, SEED, 4, 0, count)
+        assert (rc, got, n_found, pairs) == (1, want, 1, 4 * count), m.L.pow_last_error()
+        s = m.stats()
+        assert (s["launches"], s["hashes"]) == (16, 4 * count) and s["kernel_ms"] > 0
+
+
+# ---- 11: the C example ----
+def test_c_example(tmp_path):
+    exe = str(tmp_path / "find_seed")
+    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "examples", "find_seed.c"), "-L", PKG, "-lpow_gpu",
+                    f"-Wl,-rpath,{PKG}", "-o", exe], check=True)
+    p = subprocess.run([exe, "1234", "9"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stdout + p.stderr
+    seed = 1700000000 - 1234 + 2
+    assert f"mined 3 blocks with seed {seed}" in p.stdout
+    assert f"recovered seed {seed}: rank 2 started 1234 s before its first block" in p.stdout
+    assert p.stdout.count(f": seed {seed} trial ") == 3 and "3 matches" in p.stdout
