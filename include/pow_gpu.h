@@ -244,6 +244,89 @@ int pow_verify_chains(pow_ctx* ctx, const pow_block* blocks, const uint32_t* len
                       uint32_t* n_bad     /* n_chains, may be NULL */,
                       size_t* best        /* may be NULL */);
 
+/* "Which blocks of this pool hang together, which chains are sound, and which
+ * tip wins?": the block tree of a pool of n raw structs in ANY order, as a
+ * node holds them in map<string,Block> node_blocks (blocks of every rival and
+ * fork, in the order they arrived), with the audit of pow_verify_chain for
+ * the chain under every block at once.  It replaces the walks by
+ * previous_block_hash of sanity_test, verify_chain_indexes, look_for_block and
+ * find_block (node.cpp:40-148).  The structs go up as they are, in
+ * pow_verify_chain's tiles of 2^16; there is no per-block host work.
+ * Names.  A block has a name exactly when it is not flagged POW_V_HASH (its
+ * stored text is the 64 lowercase hex characters of its computed digest and
+ * block_hash[64] is NUL); its name is then that digest.  A block flagged
+ * POW_V_HASH is nobody's parent, so a forged block that copies an honest
+ * block's stored text cannot shadow it.  This differs from pow_verify_chain,
+ * where a child whose previous_block_hash equals the stored text of a
+ * POW_V_HASH parent gets no link flag: there the order says who the parent is,
+ * here only the name does.  Of several blocks with one digest (the same block
+ * received twice, or blocks that differ only in bytes that are not hashed:
+ * the high bytes of index, owner and created_at, and the padding) the one at
+ * the lowest pool position is the parent, as std::map::insert keeps what came
+ * first; the others find their own parent like anyone else and have no child.
+ * A block's parent.  previous_block_hash is read as the reference's (string)
+ * cast reads it: cut at the first NUL, at most 256 bytes (bytes after the NUL
+ * are hashed, but not linked).  The empty string: POW_POOL_ROOT.  Exactly 64
+ * characters of 0-9a-f, then NUL: the named block of that digest, or
+ * POW_POOL_NONE if the pool holds none.  Anything else (63 characters, 64 and
+ * no NUL behind them, an uppercase digit, a field without a NUL):
+ * POW_POOL_NONE, since no name can equal it.
+ * status[i] (n bytes, may be NULL): POW_V_HASH and POW_V_WORK exactly as
+ * pow_verify_chain gives them; POW_V_LINK: the parent is POW_POOL_NONE;
+ * POW_V_INDEX: the parent is a block and index - 1 != its index in uint32_t
+ * arithmetic (index 0 over 0xFFFFFFFF passes).  A root gets neither.
+ * parent[i] (n entries, may be NULL): a pool position, POW_POOL_ROOT or
+ * POW_POOL_NONE.  depth[i] (may be NULL): the blocks on the walk from i along
+ * parent to its end, i included; n_bad[i] (may be NULL): the flagged blocks on
+ * that walk.  The chain under tip i is sound exactly when n_bad[i] == 0 (it
+ * then ends at a root: an orphan end carries POW_V_LINK): the reference's
+ * sanity_test plus hash and work, for every possible tip.  A walk that does
+ * not end (a cycle of names, which needs a SHA-256 cycle) gives every block on
+ * or above it depth 0, n_bad 0xFFFFFFFF and POW_V_LINK.
+ * *best (may be NULL): among the blocks with n_bad == 0 the one with the
+ * greatest index in plain uint32_t comparison, pow_verify_chains' fork choice
+ * for the same reason; ties go to the lowest pool position; SIZE_MAX if no
+ * block qualifies.
+ * Returns 1 if no block is flagged, 0 otherwise; n = 0 returns 1 with *best =
+ * SIZE_MAX.  POW_EINVAL, checked in this order before the context is touched
+ * and with nothing written: diff_bits > 256; n > POW_POOL_MAX_BLOCKS; a null
+ * ctx, or a null pool with n > 0.  POW_EHIP if the table overflowed, which a
+ * table of at least 2 n slots cannot.
+ * Device memory: pow_verify_chain's 36 MB, and 98 bytes per block (two
+ * digests, index, parent and the ranking's six words) plus a table of 4-byte
+ * slots, the lowest power of two that is at least 2 n (8 to 16 bytes per
+ * block): 111 MB at 2^20 blocks.  It only grows.
+ * Known limit: the table is open-addressed from a slot the digest's last word
+ * names.  An adversary who grinds many blocks onto one start slot makes the
+ * probes long (and the call slow), never wrong or unbounded: a probe ends
+ * after one pass of the table.
+ * pow_get_stats: kernel_ms, launches (one per tile, insert, join, one per
+ * round of ceil(log2 n) rounds of pointer jumping, fork choice), hashes = n.
+ * pow_warmup does not launch this call's kernels.
+ * Cost (MI355X, profiles/index_blocks/README.md; medians of 9 calls on
+ * shuffled sound pools at d = 0, against the reference's way at -O2 on one
+ * CPU thread of the same box, a std::map keyed on the stored text and the
+ * sanity_test walk from every tip with block_to_hash per block, and against
+ * extracting every tip's chain on the host for one pow_verify_chains call):
+ * the call is slower than both below a few dozen blocks: 5 blocks in one
+ * chain take 99 us (7 launches, kernels 44 us) against 6 us and 65 us, 16
+ * blocks 102 us against 18 us and 68 us.  The published shape as a pool (3
+ * rivals x 10 heights on a root: 31 blocks, 21 tips): 117 us against 138 us
+ * and 115 us, the crossover.  200 blocks with 8 tips: 137 us against 0.91 ms
+ * and 0.24 ms; 4,096: 0.21 ms against 22.7 ms and 5.7 ms; 2^16: 0.89 ms
+ * (kernels 0.17 ms) against 555 ms and 286 ms; 2^20: 12.6 ms (39 launches,
+ * kernels 1.8 ms; the rest is the copy of 579 MB of structs) against 18.9 s
+ * and 14.9 s. */
+#define POW_POOL_MAX_BLOCKS (1u << 20)
+#define POW_POOL_ROOT 0xFFFFFFFFu /* previous_block_hash is the empty string */
+#define POW_POOL_NONE 0xFFFFFFFEu /* names a parent the pool does not hold */
+int pow_index_blocks(pow_ctx* ctx, const pow_block* pool, size_t n, unsigned diff_bits,
+                     uint8_t* status  /* n, may be NULL */,
+                     uint32_t* parent /* n, may be NULL */,
+                     uint32_t* depth  /* n, may be NULL */,
+                     uint32_t* n_bad  /* n, may be NULL */,
+                     size_t* best     /* may be NULL */);
+
 /* Mining round: replaces node.cpp:302-308 (nonce -> hash -> test) for every
  * counter in [ctr_start, ctr_start + ctr_count).  The header fields and the
  * 256-byte previous_block_hash are taken from `tmpl` as they are (the caller

@@ -29,6 +29,7 @@ GROUP_ID_BYTES = 128
 BOARD_MAX_SLOTS, BOARD_MAX_TAG = 64, 1023
 POW_REDUCE_MIN, POW_REDUCE_MAX, POW_REDUCE_SUM = 0, 1, 2
 POW_V_HASH, POW_V_WORK, POW_V_LINK, POW_V_INDEX = 1, 2, 4, 8
+POOL_MAX_BLOCKS, POOL_ROOT, POOL_NONE = 1 << 20, 0xFFFFFFFF, 0xFFFFFFFE
 
 
 class PowError(RuntimeError):
@@ -140,6 +141,9 @@ def load(test_hooks: bool = False) -> ctypes.CDLL:
         "pow_verify_chains": ([ctypes.c_void_p, P, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t, ctypes.c_uint,
                                ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
                                c_sizep], ctypes.c_int),
+        "pow_index_blocks": ([ctypes.c_void_p, P, ctypes.c_size_t, ctypes.c_uint, ctypes.c_void_p,
+                              ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+                              ctypes.POINTER(ctypes.c_uint32), c_sizep], ctypes.c_int),
         "pow_mine_chain": ([ctypes.c_void_p, P, ctypes.c_size_t, ctypes.c_uint, ctypes.c_uint32, c_u64p,
                             ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, P,
                             c_sizep, c_u64p], ctypes.c_int),
@@ -200,7 +204,7 @@ def load(test_hooks: bool = False) -> ctypes.CDLL:
 EXPORTS = ("pow_device_count", "pow_init", "pow_warmup", "pow_destroy", "pow_last_error", "pow_get_stats", "pow_launch_path",
            "pow_device_info", "pow_device_pci_bus_id",
            "pow_nonce_from_counter", "pow_block_to_bytes", "pow_solves_problem", "pow_hash_blocks",
-           "pow_hash_block", "pow_verify_chain", "pow_verify_chains", "pow_mine_chain", "pow_mine_batch", "pow_mine_race", "pow_mine_rand", "pow_rand_nonces", "pow_find_seed", "pow_mine", "pow_mine_any", "pow_cancel", "pow_sweep", "pow_sweep_device", "pow_dev_alloc", "pow_dev_free",
+           "pow_hash_block", "pow_verify_chain", "pow_verify_chains", "pow_index_blocks", "pow_mine_chain", "pow_mine_batch", "pow_mine_race", "pow_mine_rand", "pow_rand_nonces", "pow_find_seed", "pow_mine", "pow_mine_any", "pow_cancel", "pow_sweep", "pow_sweep_device", "pow_dev_alloc", "pow_dev_free",
            "pow_dev_read", "pow_valu_peak", "pow_valu_rate", "pow_valu_rate_ctx", "pow_group_partition", "pow_group_unique_id", "pow_group_init",
            "pow_group_init_within",
            "pow_group_init_custom", "pow_group_destroy", "pow_group_info", "pow_group_rccl_path", "pow_group_last_search",

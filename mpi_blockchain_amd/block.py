@@ -16,6 +16,10 @@ reference                  here
 ``check_chain`` and more   :func:`verify_chain` (host statement of what
                            ``pow_verify_chain`` checks on the GPU:
                            :meth:`mpi_blockchain_amd.miner.GpuMiner.verify_chain`)
+a pool in any order       :func:`index_blocks` and :func:`chain_from` (host statement of
+                           ``pow_index_blocks``: the block tree of ``node_blocks``, every
+                           chain in it audited, and the fork choice:
+                           :meth:`mpi_blockchain_amd.miner.GpuMiner.index_blocks`)
 the same, many chains     :func:`verify_chains` and :func:`best_chain` (host statement of
                            ``pow_verify_chains``' verdicts and fork choice:
                            :meth:`mpi_blockchain_amd.miner.GpuMiner.verify_chains`)
@@ -34,7 +38,7 @@ import hashlib
 import random
 import time
 
-from ._lib import HASH_SIZE, MSG_BYTES, NONCE_SIZE, Block, check, load
+from ._lib import HASH_SIZE, MSG_BYTES, NONCE_SIZE, POOL_NONE, POOL_ROOT, Block, check, load
 
 # block.h:4-9, node.h:7-10
 DEFAULT_DIFFICULTY = 9
@@ -49,7 +53,7 @@ MAX_BLOCKS = 200
 ALPHABET = "abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789"
 
 __all__ = ["Block", "make_block", "block_to_str", "solves_problem", "nonce_from_counter",
-           "gen_random_nonce", "field", "set_field", "verify_chain", "verify_chains", "best_chain", "mine_chain", "mine_batch", "V_HASH", "V_WORK", "V_LINK", "V_INDEX", "DEFAULT_DIFFICULTY", "BLOCKS_TO_MINE",
+           "gen_random_nonce", "field", "set_field", "verify_chain", "verify_chains", "best_chain", "index_blocks", "chain_from", "POOL_ROOT", "POOL_NONE", "mine_chain", "mine_batch", "V_HASH", "V_WORK", "V_LINK", "V_INDEX", "DEFAULT_DIFFICULTY", "BLOCKS_TO_MINE",
            "VALIDATION_MINUTES", "VALIDATION_BLOCKS", "HASH_SIZE", "NONCE_SIZE", "MSG_BYTES"]
 
 
@@ -170,6 +174,78 @@ def best_chain(chains, statuses) -> int | None:
         if best is None or chain[0].index > chains[best][0].index:
             best = c
     return best
+
+
+def index_blocks(pool, difficulty: int = DEFAULT_DIFFICULTY):
+    """``(status, parent, depth, n_bad, best)`` of a pool of blocks in any
+    order: what ``pow_index_blocks`` computes on the GPU, stated on the host
+    with hashlib and a dict.
+
+    A block that is not flagged ``V_HASH`` has a name, its digest's hex; of
+    several blocks with one name the lowest position keeps it (a dict's
+    ``setdefault``, as ``std::map::insert``).  A block's parent is
+    ``POOL_ROOT`` if its ``previous_block_hash`` as a C string is empty, the
+    block of that name if there is one, ``POOL_NONE`` otherwise.  ``V_HASH``
+    and ``V_WORK`` are :func:`verify_chain`'s; ``V_LINK``: the parent is
+    ``POOL_NONE``; ``V_INDEX``: the parent is a block and ``index - 1`` is not
+    its index in 32 bits.  ``depth[i]`` counts the blocks on the walk from i
+    along ``parent``, i included, ``n_bad[i]`` the flagged ones among them.
+    ``best`` is the block with ``n_bad == 0`` and the greatest index, the
+    lowest position on a tie; None if there is none."""
+    if not 0 <= difficulty <= 256:
+        raise ValueError(f"difficulty {difficulty} not in 0..256")
+    n = len(pool)
+    status, names = [], {}
+    for i, b in enumerate(pool):
+        digest = hashlib.sha256(block_to_str(b)).digest()
+        stored = field(b, "block_hash")
+        flags = 0
+        if stored[:64] != digest.hex().encode() or stored[64] != 0:
+            flags |= V_HASH
+        else:
+            names.setdefault(digest.hex().encode(), i)
+        if 256 - int.from_bytes(digest, "big").bit_length() < difficulty:
+            flags |= V_WORK
+        status.append(flags)
+    parent = []
+    for i, b in enumerate(pool):
+        prev = _c_string(field(b, "previous_block_hash"))
+        p = POOL_ROOT if prev == b"" else names.get(prev, POOL_NONE)
+        if p == POOL_NONE:
+            status[i] |= V_LINK
+        elif p != POOL_ROOT and (b.index - 1) & 0xFFFFFFFF != pool[p].index:
+            status[i] |= V_INDEX
+        parent.append(p)
+    depth, n_bad = [None] * n, [None] * n
+    for i in range(n):
+        walk = []
+        j = i
+        while j < n and depth[j] is None:  # names are digests: a walk cannot come back to itself
+            walk.append(j)
+            j = parent[j]
+        d, f = (depth[j], n_bad[j]) if j < n else (0, 0)
+        for k in reversed(walk):
+            d, f = d + 1, f + (1 if status[k] else 0)
+            depth[k], n_bad[k] = d, f
+    best = None
+    for i in range(n):
+        if n_bad[i] == 0 and (best is None or pool[i].index > pool[best].index):
+            best = i
+    return status, parent, depth, n_bad, best
+
+
+def chain_from(pool, parent, i: int):
+    """The chain under block i of a pool as a ctypes ``Block`` array, tip
+    first, ready for :func:`verify_chain`: i, its parent, and so on along
+    `parent` (``index_blocks``' second result) to the walk's end."""
+    walk = []
+    while i < len(pool):
+        walk.append(i)
+        i = parent[i]
+    arr = (Block * len(walk))()
+    for k, j in enumerate(walk):
+        ctypes.memmove(ctypes.byref(arr, k * ctypes.sizeof(Block)), ctypes.addressof(pool[j]), ctypes.sizeof(Block))
+    return arr
 
 
 def mine_chain(parent: Block, n: int, difficulty: int = DEFAULT_DIFFICULTY, owner: int = 0, created_at=None,

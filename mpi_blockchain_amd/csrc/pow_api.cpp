@@ -719,6 +719,56 @@ int pow_verify_chains(pow_ctx* ctx, const pow_block* blocks, const uint32_t* len
   return clean ? 1 : 0;
 }
 
+// K10 over a pool: K10a tile by tile into the call's arrays, which stay on the
+// device, then the table, the join, the rounds and the fork choice queued back
+// to back behind one reset, with one bounded wait and one set of copies down.
+int pow_index_blocks(pow_ctx* ctx, const pow_block* pool, size_t n, unsigned diff_bits, uint8_t* status,
+                     uint32_t* parent, uint32_t* depth, uint32_t* n_bad, size_t* best) {
+  if (diff_bits > 256) return fail(POW_EINVAL, "diff_bits %u > 256", diff_bits);
+  if (n > POW_POOL_MAX_BLOCKS) return fail(POW_EINVAL, "pool too large (%zu blocks > %u)", n, POW_POOL_MAX_BLOCKS);
+  if (!ctx || (!pool && n)) return fail(POW_EINVAL, "null");
+  ctx->stats = pow_stats{};
+  if (best) *best = SIZE_MAX;
+  if (n == 0) return 1;
+  if (int rc = set_dev(ctx)) return rc;
+  if (int rc = ensure_verify_tile(ctx, std::min(n, kVerifyTile))) return rc;
+  const PowPoolPlan plan = pow_pool_plan((uint32_t)n, ctx->pool_slots_log2);
+  RESERVE(ctx->d_pool, plan.words);
+  RESERVE(ctx->h_pool, 1);
+  const PowPoolDev D = pow_pool_dev(ctx->d_pool.p, plan, (uint32_t)n);
+  if (int rc = verify_tiles(
+          ctx, pool, n, "pool audit kernel", [](const VerifyTile&) -> int { return POW_OK; },
+          [&](const VerifyTile& t) -> int {
+            HIP_OK(pow_launch_pool_audit(ctx->stream, (const uint32_t*)ctx->d_vblk.p, (uint32_t)t.tn, (uint32_t)t.t0,
+                                         diff_bits, D));
+            HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+            return POW_OK;
+          },
+          [](const VerifyTile&) {}))
+    return rc;
+  if (int rc = timed_begin(ctx)) return rc;
+  HIP_OK(hipMemsetAsync(D.ctl, 0, sizeof(PowPoolCtl), ctx->stream));
+  HIP_OK(hipMemsetAsync(D.table, 0xFF, (size_t)D.slots * sizeof(uint32_t), ctx->stream));  // every call: no stale slot
+  HIP_OK(pow_launch_pool_insert(ctx->stream, D));
+  HIP_OK(pow_launch_pool_join(ctx->stream, D));
+  for (uint32_t r = 0; r < plan.rounds; ++r) HIP_OK(pow_launch_pool_round(ctx->stream, D, r));
+  const uint32_t last = plan.rounds & 1u;  // the buffers the last round wrote
+  HIP_OK(pow_launch_pool_finish(ctx->stream, D, last));
+  HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+  PowPoolCtl* const ctl = ctx->h_pool.p;
+  HIP_OK(hipMemcpyAsync(ctl, D.ctl, sizeof(PowPoolCtl), hipMemcpyDeviceToHost, ctx->stream));
+  if (status) HIP_OK(hipMemcpyAsync(status, D.status, n, hipMemcpyDeviceToHost, ctx->stream));
+  if (parent) HIP_OK(hipMemcpyAsync(parent, D.parent, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (depth) HIP_OK(hipMemcpyAsync(depth, D.depth[last], n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (n_bad) HIP_OK(hipMemcpyAsync(n_bad, D.bad[last], n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  // + 100 ns per block and round
+  if (int rc = timed_end(ctx, "pool index kernels", 100ull * n * (plan.rounds + 1u), 3u + plan.rounds, &ctx->stats))
+    return rc;
+  if (ctl->err) return fail(POW_EHIP, "pool table overflow (%zu blocks, %u slots)", n, D.slots);
+  if (best && ctl->best) *best = (size_t)(uint32_t)~(uint32_t)ctl->best;
+  return ctl->n_flagged == 0 ? 1 : 0;
+}
+
 int pow_sweep_device(pow_ctx* ctx, const pow_block* tmpl, uint64_t ctr_start, uint64_t ctr_count,
                      unsigned diff_bits, uint32_t* dev_out, size_t cap, size_t* n_found,
                      uint64_t* min_ctr) {

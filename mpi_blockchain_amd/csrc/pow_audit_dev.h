@@ -1,6 +1,9 @@
-// What the audit kernels K3 (pow_verify.hip) and K7 (pow_verify_batch.hip)
-// share: the audit of one block from its raw 552-byte struct in LDS, and the
-// copy of a workgroup's tile into LDS.  Each kernel is one translation unit
+// What the audit kernels K3 (pow_verify.hip), K7 (pow_verify_batch.hip) and
+// K10a (pow_pool.hip) share: the audit of one block from its raw 552-byte
+// struct in LDS, in two parts (hash_block: its digest; own_flags: what it shows
+// on its own; audit_block: both and the checks against its parent, which K10a
+// does not take: a pool's parent is found by name), and the copy of a
+// workgroup's tile into LDS.  Each kernel is one translation unit
 // that includes this header; a kernel keeps what a lane's block is, whether it
 // has a parent in its chain, and where its verdict goes.
 //
@@ -69,12 +72,9 @@ __device__ __forceinline__ void load_tile(uint32_t* lds, const uint32_t* __restr
   if (lane < (ndw & 3u)) lds[4u * nvec + lane] = src[4u * nvec + lane];
 }
 
-// The flags (POW_V_*) of the block at b, a raw struct in LDS.  has_parent: the
-// struct behind it (b + BLK_DW) is its parent; it is read only then.
-__device__ __forceinline__ uint32_t audit_block(const uint32_t* b, bool has_parent, uint32_t diff) {
-  uint32_t flags = 0;
-  // ---- block_to_hash ----
-  uint32_t h[8];
+// block_to_hash of the block at b, a raw struct in LDS: its digest into h.
+// The one place the audit kernels call the compression.
+__device__ __forceinline__ void hash_block(const uint32_t* b, uint32_t h[8]) {
 #pragma unroll
   for (int k = 0; k < 8; ++k) h[k] = IV[k];
 #pragma unroll 1
@@ -91,6 +91,11 @@ __device__ __forceinline__ uint32_t audit_block(const uint32_t* b, bool has_pare
     }
     compress(h, w);
   }
+}
+
+// The flags a block has on its own, given its digest h: POW_V_HASH and POW_V_WORK.
+__device__ __forceinline__ uint32_t own_flags(const uint32_t* b, const uint32_t h[8], uint32_t diff) {
+  uint32_t flags = 0;
   // ---- POW_V_HASH: the stored text, 64 characters from struct byte 290, then NUL ----
   uint32_t diffs = 0;
 #pragma unroll
@@ -103,6 +108,15 @@ __device__ __forceinline__ uint32_t audit_block(const uint32_t* b, bool has_pare
   if (diffs) flags |= POW_V_HASH;
   // ---- POW_V_WORK: on the computed digest ----
   if (leading_zero_bits(h) < diff) flags |= POW_V_WORK;
+  return flags;
+}
+
+// The flags (POW_V_*) of the block at b, a raw struct in LDS.  has_parent: the
+// struct behind it (b + BLK_DW) is its parent; it is read only then.
+__device__ __forceinline__ uint32_t audit_block(const uint32_t* b, bool has_parent, uint32_t diff) {
+  uint32_t h[8];
+  hash_block(b, h);  // ---- block_to_hash ----
+  uint32_t flags = own_flags(b, h, diff);
   // ---- POW_V_LINK, POW_V_INDEX: against the parent, the next block ----
   if (has_parent) {
     const uint32_t* const p = b + BLK_DW;

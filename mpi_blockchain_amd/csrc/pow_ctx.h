@@ -248,6 +248,39 @@ struct PowSeedLaunch {
   uint32_t nwg;         // workgroups per seed, <= POW_RAND_MAX_WG
 };
 
+// K10 (pow_pool.hip), the kernels of pow_index_blocks.  What a block's
+// previous_block_hash can be (K10a writes it, K10c reads it):
+enum { POW_PREV_EMPTY = 0, POW_PREV_DIGEST = 1, POW_PREV_UNMATCHABLE = 2 };
+// The call's control words: reset by the host before K10b.
+struct PowPoolCtl {
+  unsigned int err;         // K10b: a lane found no slot (atomic or)
+  unsigned int n_flagged;   // K10e: blocks with a non-zero status (atomic add)
+  unsigned long long best;  // K10e: the greatest index << 32 | ~position among n_bad == 0 (atomic max); 0 = none
+};
+static_assert(sizeof(PowPoolCtl) == 16, "four words of the plan");
+// The arrays of a call, each n entries unless said: device addresses in the
+// call's one buffer, at the plan's offsets (pow_pool_plan, pow_host.h).
+struct PowPoolDev {
+  PowPoolCtl* ctl;
+  uint32_t* dig;     // 8 n: the computed digests
+  uint32_t* prev;    // 8 n: the parsed previous_block_hash
+  uint32_t* index;
+  uint32_t* parent;
+  uint32_t* next[2];
+  uint32_t* depth[2];
+  uint32_t* bad[2];
+  uint8_t* status;
+  uint8_t* kind;
+  uint32_t* table;   // slots
+  uint32_t n, slots;
+};
+inline PowPoolDev pow_pool_dev(uint32_t* base, const PowPoolPlan& p, uint32_t n) {
+  return PowPoolDev{(PowPoolCtl*)(base + p.ctl), base + p.dig, base + p.prev, base + p.index, base + p.parent,
+                    {base + p.next[0], base + p.next[1]}, {base + p.depth[0], base + p.depth[1]},
+                    {base + p.bad[0], base + p.bad[1]}, (uint8_t*)(base + p.status), (uint8_t*)(base + p.kind),
+                    base + p.table, n, p.slots};
+}
+
 struct pow_ctx {
   int device = 0;
   int cu_count = 0;
@@ -320,7 +353,10 @@ struct pow_ctx {
   HostBuf<PowSeedIn> h_seed;         // ... and its pinned twin
   DevBuf<PowSeedOut> d_sout;         // the launch's matches ...
   HostBuf<PowSeedOut> h_sout;        // ... and their pinned twin (d_rtab, h_rtab: K9 starts from K8's tables)
+  DevBuf<uint32_t> d_pool;           // pow_index_blocks: every array of the call (pow_pool_plan), in words ...
+  HostBuf<PowPoolCtl> h_pool;        // ... and the pinned twin of its control words
   void release_buffers() {  // every holder above
+    d_pool.release(), h_pool.release();
     d_seed.release(), h_seed.release(), d_sout.release(), h_sout.release();
     d_rand.release(), h_rand.release(), d_rrec.release(), h_rrec.release();
     d_rnslot.release(), d_rnchar.release(), d_rtab.release(), h_rtab.release();
@@ -355,6 +391,7 @@ struct pow_ctx {
   unsigned seed_run = 0;          // pow_find_seed: K9's run T (0 = the plan)
   unsigned seed_wg = 0;           // K9's workgroups per seed (0 = the plan)
   unsigned seed_launch_log2 = POW_SEED_LAUNCH_LOG2;  // (seed, trial) pairs per K9 launch = 2^this
+  unsigned pool_slots_log2 = 0;   // pow_index_blocks: the table's slots = 2^this, at least n + 1 (0 = the plan)
   // K1' and K2' launches as AQL packets (pow_aql.cpp) instead of
   // hipLaunchKernel: test library only, opt-in there; null = the HIP launch
   // path, the only one the shipped library has.
@@ -392,6 +429,12 @@ hipError_t pow_launch_rand(hipStream_t stream, const PowRandLaunch& L, const Pow
                            PowBatchCtl* ctl, PowChainSlot* slots, uint32_t* slot_nonce, PowRandRec* rec);
 hipError_t pow_launch_seed(hipStream_t stream, const PowSeedLaunch& L, const PowSeedIn* in, const uint32_t* tab,
                            PowSeedOut* out);
+hipError_t pow_launch_pool_audit(hipStream_t stream, const uint32_t* blocks, uint32_t n_check, uint32_t base,
+                                 unsigned diff, const PowPoolDev& D);
+hipError_t pow_launch_pool_insert(hipStream_t stream, const PowPoolDev& D);
+hipError_t pow_launch_pool_join(hipStream_t stream, const PowPoolDev& D);
+hipError_t pow_launch_pool_round(hipStream_t stream, const PowPoolDev& D, uint32_t r);
+hipError_t pow_launch_pool_finish(hipStream_t stream, const PowPoolDev& D, uint32_t which);
 hipError_t pow_sort_u32(void* temp, size_t* temp_bytes, uint32_t* keys, uint32_t* alt, uint32_t n,
                         uint32_t** sorted, hipStream_t stream);
 hipError_t pow_launch_search_lat(bool full, bool any, bool asm_groups, unsigned grid, hipStream_t stream,

@@ -3,7 +3,8 @@
 // libpow_gpu.so.  The test and tuning switches read from the environment at
 // pow_init, the direct-dispatch launch path (pow_aql.cpp, POW_AQL=1), the stall
 // kernel of the watchdog tests, the stand-in RCCL of the shard tests and
-// pow_test_leading_zero_bits, the only export the shipped library does not have.
+// the exports the shipped library does not have: pow_test_leading_zero_bits and
+// pow_test_pool_rank.
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -12,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <thread>
+#include <vector>
 
 #include "pow_aql.h"
 #include "pow_ctx.h"
@@ -55,6 +57,8 @@ void configure(pow_ctx* ctx) {
   if (const char* sr = getenv("POW_SEED_RUN")) ctx->seed_run = (unsigned)std::min(992ul, strtoul(sr, nullptr, 0));
   if (const char* sw = getenv("POW_SEED_WG")) ctx->seed_wg = (unsigned)std::min((unsigned long)POW_RAND_MAX_WG, strtoul(sw, nullptr, 0));
   if (const char* sn = getenv("POW_SEED_LAUNCH_LOG2")) ctx->seed_launch_log2 = (unsigned)std::min((unsigned long)POW_SEED_LAUNCH_LOG2, strtoul(sn, nullptr, 0));
+  // pow_index_blocks: the table's slots (2^n, never below the pool's blocks + 1); the result must not depend on it
+  if (const char* ps = getenv("POW_POOL_SLOTS_LOG2")) ctx->pool_slots_log2 = (unsigned)std::min(21ul, strtoul(ps, nullptr, 0));
   if (const char* g = getenv("POW_GRID_PER_CU")) {  // launch-geometry experiments
     const int per = atoi(g);
     if (per > 0 && per <= 64) ctx->grid_full = (unsigned)ctx->cu_count * (unsigned)per;
@@ -198,5 +202,39 @@ extern "C" int pow_test_leading_zero_bits(pow_ctx* ctx, const uint32_t* digests,
     (void)hipFree(d_in);
     (void)hipFree(d_out);
   }
+  return rc;
+}
+
+// K10d and K10e (pow_pool.hip) on a next[] of the caller's choosing, the only
+// way to rank a cycle: next[i] is a position below n or anything at or above n
+// (the end of a walk), every node counts 1 and none is flagged.  depth_out and
+// n_bad_out = n words each: what pow_index_blocks would give for that tree.
+extern "C" int pow_test_pool_rank(pow_ctx* ctx, const uint32_t* next, size_t n, uint32_t* depth_out, uint32_t* n_bad_out) {
+  if (!ctx || ((!next || !depth_out || !n_bad_out) && n)) return fail(POW_EINVAL, "null");
+  if (n > POW_POOL_MAX_BLOCKS) return fail(POW_EINVAL, "too many nodes (%zu > 2^20)", n);
+  if (n == 0) return POW_OK;
+  HIP_OK(hipSetDevice(ctx->device));
+  const PowPoolPlan plan = pow_pool_plan((uint32_t)n, 0);
+  uint32_t* base = nullptr;
+  int rc = POW_OK;
+  auto step = [&](hipError_t e, const char* what) {
+    if (rc == POW_OK && e != hipSuccess) rc = fail(POW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
+  };
+  step(hipMalloc(&base, plan.words * sizeof(uint32_t)), "hipMalloc");
+  if (rc != POW_OK) return rc;
+  const PowPoolDev D = pow_pool_dev(base, plan, (uint32_t)n);
+  const uint32_t last = plan.rounds & 1u;
+  std::vector<uint32_t> ones(n, 1u);
+  step(hipMemsetAsync(base, 0, plan.words * sizeof(uint32_t), ctx->stream), "reset");  // status, index, bad, ctl: all zero
+  step(hipMemcpyAsync(D.next[0], next, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream), "copy in");
+  step(hipMemcpyAsync(D.depth[0], ones.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream), "copy in");
+  for (uint32_t r = 0; r < plan.rounds; ++r) step(pow_launch_pool_round(ctx->stream, D, r), "pow_pool_round_kernel");
+  step(pow_launch_pool_finish(ctx->stream, D, last), "pow_pool_finish_kernel");
+  step(hipMemcpyAsync(depth_out, D.depth[last], n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream), "copy out");
+  step(hipMemcpyAsync(n_bad_out, D.bad[last], n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream), "copy out");
+  // waited for even after a failed step: the copies queued so far read `ones`
+  const int waited = pow_ctx_stream_wait(ctx, "pow_test_pool_rank", 100ull * n * (plan.rounds + 1u));
+  if (rc == POW_OK) rc = waited;
+  if (waited == POW_OK || !ctx->wedged) (void)hipFree(base);  // after a watchdog the launches may still write
   return rc;
 }

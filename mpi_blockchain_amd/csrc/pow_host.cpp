@@ -447,6 +447,40 @@ PowSeedPlan pow_seed_plan(uint32_t n_seeds, uint64_t trial_count, uint32_t cu_co
   return p;
 }
 
+PowPoolPlan pow_pool_plan(uint32_t n, unsigned slots_log2) {
+  PowPoolPlan p;
+  // The lowest power of two that is at least 2 n; an override may go below it,
+  // down to the lowest one that still leaves a slot empty.
+  uint32_t least = 1;
+  while (least < n + 1u) least *= 2;
+  uint32_t slots = 2;
+  while (slots < 2ull * n) slots *= 2;
+  if (slots_log2) slots = std::max(least, 1u << std::min(slots_log2, 21u));
+  p.slots = slots;
+  p.rounds = 0;
+  while ((1ull << p.rounds) < n) ++p.rounds;
+  const uint32_t bytes = (n + 3u) / 4u;  // n bytes in whole words
+  uint32_t at = 0;
+  auto take = [&](uint32_t words) {
+    const uint32_t here = at;
+    at += words;
+    return here;
+  };
+  p.ctl = take(4);
+  p.dig = take(8u * n);
+  p.prev = take(8u * n);
+  p.index = take(n);
+  p.parent = take(n);
+  for (int k = 0; k < 2; ++k) p.next[k] = take(n);
+  for (int k = 0; k < 2; ++k) p.depth[k] = take(n);
+  for (int k = 0; k < 2; ++k) p.bad[k] = take(n);
+  p.status = take(bytes);
+  p.kind = take(bytes);
+  p.table = take(slots);
+  p.words = at;
+  return p;
+}
+
 extern "C" {
 
 const char* pow_last_error(void) { return g_err.c_str(); }

@@ -156,4 +156,33 @@ struct PowSeedPlan {
 PowSeedPlan pow_seed_plan(uint32_t n_seeds, uint64_t trial_count, uint32_t cu_count, unsigned run_override,
                           unsigned wg_override, unsigned launch_log2);
 
+// ---- pow_index_blocks (K10): a pool's block tree ----
+// The plan of a pool of n blocks (1..POW_POOL_MAX_BLOCKS): the table's slots,
+// the ranking's rounds, and where each array lies in the call's one device
+// buffer, in 32-bit words from its start.  Pure; slots_log2 is the test
+// library's override (0 = the plan).  It holds that slots is a power of two,
+// slots >= 2 n (an override: 2^slots_log2, raised to the lowest power of two
+// that is at least n + 1, so that a probe always meets an empty slot), rounds =
+// ceil(log2 n) (2^rounds >= n: the deepest walk of n blocks has ended), no two
+// arrays overlap, dig and prev lie on 16 bytes and ctl on 8, and words holds
+// them all: 4 + 24 n + 2 ceil(n / 4) + slots, that is 98 bytes per block and 4
+// per slot (8 to 16 per block): 111 MB at 2^20 blocks.
+struct PowPoolPlan {
+  uint32_t slots;     // of the table
+  uint32_t rounds;    // of pointer jumping
+  uint32_t ctl;       // PowPoolCtl: 4 words
+  uint32_t dig;       // 8 n: the computed digests
+  uint32_t prev;      // 8 n: the parsed previous_block_hash
+  uint32_t index;     // n
+  uint32_t parent;    // n
+  uint32_t next[2];   // n each: the ranking's ping-pong buffers ...
+  uint32_t depth[2];
+  uint32_t bad[2];
+  uint32_t status;    // n bytes
+  uint32_t kind;      // n bytes
+  uint32_t table;     // slots
+  uint64_t words;     // all of it
+};
+PowPoolPlan pow_pool_plan(uint32_t n, unsigned slots_log2);
+
 #pragma GCC visibility pop

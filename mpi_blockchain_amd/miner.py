@@ -42,6 +42,16 @@ class VerifyChainsResult:
 
 
 @dataclass
+class IndexBlocksResult:
+    ok: bool              # no block of the pool is flagged (pow_index_blocks returned 1)
+    best: int | None      # the fork choice: the block with n_bad == 0 and the highest index (lowest position on a tie); None if none
+    status: np.ndarray    # np.uint8 per block, as VerifyResult.status
+    parent: np.ndarray    # np.uint32 per block: a pool position, block.POOL_ROOT or block.POOL_NONE
+    depth: np.ndarray     # np.uint32 per block: the blocks of the chain under it, itself included
+    n_bad: np.ndarray     # np.uint32 per block: the flagged ones among them; 0 = the chain under it is sound
+
+
+@dataclass
 class MineChainResult:
     blocks: ctypes.Array  # the mined chain, tip first: Block * n_mined
     n_mined: int          # blocks mined
@@ -206,6 +216,24 @@ class GpuMiner:
         dg = ctypes.create_string_buffer(32)
         check(self.L.pow_hash_block(self.ctx, ctypes.byref(b), dg, None), self.L)
         return dg.raw
+
+    # ---- the block tree of a pool (node_blocks walked by previous_block_hash) ----
+    def index_blocks(self, pool, difficulty: int = DEFAULT_DIFFICULTY) -> IndexBlocksResult:
+        """pow_index_blocks over a pool of blocks in any order: a list of
+        Blocks or a ctypes ``Block * n`` array (passed as it is).  The host
+        statement of the result is :func:`mpi_blockchain_amd.block.index_blocks`;
+        :func:`mpi_blockchain_amd.block.chain_from` extracts a tip's chain."""
+        n = len(pool)
+        arr = pool if isinstance(pool, ctypes.Array) else (Block * max(n, 1))(*pool)
+        status = np.zeros(n, dtype=np.uint8)
+        parent, depth, bad = (np.zeros(n, dtype=np.uint32) for _ in range(3))
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        best = ctypes.c_size_t()
+        rc = check(self.L.pow_index_blocks(self.ctx, arr, n, difficulty, status.ctypes.data_as(ctypes.c_void_p),
+                                           parent.ctypes.data_as(u32p), depth.ctypes.data_as(u32p),
+                                           bad.ctypes.data_as(u32p), ctypes.byref(best)), self.L)
+        return IndexBlocksResult(rc == 1, None if best.value == ctypes.c_size_t(-1).value else best.value,
+                                 status, parent, depth, bad)
 
     # ---- chain audit (check_first + check_chain + solves_problem for every block) ----
     def verify_chain(self, blocks, difficulty: int = DEFAULT_DIFFICULTY) -> VerifyResult:
