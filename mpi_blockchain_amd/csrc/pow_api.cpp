@@ -969,6 +969,15 @@ int check_fused_args(unsigned diff_bits, uint64_t ctr_start, uint64_t ctr_count,
   return POW_OK;
 }
 
+// The window of trials that pow_mine_rand and pow_find_seed take.
+int check_trial_window(uint64_t trial_start, uint64_t trial_count) {
+  if (trial_count == 0 || trial_count > (1ull << 32))
+    return fail(POW_EINVAL, "trial_count %llu not in 1..2^32", (unsigned long long)trial_count);
+  if (trial_start > POW_RAND_TRIAL_LIMIT || trial_count > POW_RAND_TRIAL_LIMIT - trial_start)
+    return fail(POW_EINVAL, "trial range past POW_RAND_TRIAL_LIMIT (2^56)");
+  return POW_OK;
+}
+
 // The head of a K4, K5 or K6 launch's arguments (the caller has zeroed them).
 void fill_head(PowWalkHead* w, uint64_t ctr_start, uint64_t ctr_count, unsigned diff_bits) {
   PowLaunchLat digits;
@@ -1242,10 +1251,7 @@ int ensure_race(pow_ctx* ctx) {
 // The counter of a nonce pow_nonce_from_counter made (block.cpp:61-72's alphabet).
 uint64_t counter_of_nonce(const char* nonce) {
   uint64_t c = 0;
-  for (int i = 0; i < 9; ++i) {
-    const char ch = nonce[i];
-    c = c * 62 + (uint64_t)(ch >= 'a' ? ch - 'a' : ch >= 'A' ? ch - 'A' + 26 : ch - '0' + 52);
-  }
+  for (int i = 0; i < 9; ++i) c = c * 62 + (uint64_t)digit_of(nonce[i]);
   return c;
 }
 
@@ -1358,6 +1364,25 @@ int ensure_rand(pow_ctx* ctx) {
   return POW_OK;
 }
 
+// The tables of the run T that a launch of K8 or K9 reads go up once, in front of the first launch
+// that needs them and under its bounded wait: they count as there, and their pinned twin as free,
+// once that wait has returned (rand_timed_end).
+int stage_rand_tables(pow_ctx* ctx, uint32_t run) {
+  if (ctx->rand_tab_run == run) return POW_OK;
+  pow_rand_tables(run, ctx->h_rtab.p);
+  ctx->rand_tab_run = 0;
+  HIP_OK(hipMemcpyAsync(ctx->d_rtab.p, ctx->h_rtab.p, POW_RAND_TAB_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice,
+                        ctx->stream));
+  return POW_OK;
+}
+
+// timed_end for one launch that read the tables of `run`.
+int rand_timed_end(pow_ctx* ctx, const char* what, uint64_t extra_ns, uint32_t run, pow_stats* s) {
+  if (int rc = timed_end(ctx, what, extra_ns, 1u, s)) return rc;
+  ctx->rand_tab_run = run;
+  return POW_OK;
+}
+
 }  // namespace
 
 // K8, one launch per 2^26 trials of the window, in ascending order; the first
@@ -1366,10 +1391,7 @@ int pow_mine_rand(pow_ctx* ctx, const pow_block* tmpl, uint32_t seed, uint64_t t
                   unsigned diff_bits, const volatile uint32_t* cancel_word, uint32_t epoch, pow_block* out,
                   uint64_t* found_trial, uint64_t* hashes_done) {
   if (diff_bits > 32) return fail(POW_EINVAL, "diff_bits %u > 32", diff_bits);
-  if (trial_count == 0 || trial_count > (1ull << 32))
-    return fail(POW_EINVAL, "trial_count %llu not in 1..2^32", (unsigned long long)trial_count);
-  if (trial_start > POW_RAND_TRIAL_LIMIT || trial_count > POW_RAND_TRIAL_LIMIT - trial_start)
-    return fail(POW_EINVAL, "trial range past POW_RAND_TRIAL_LIMIT (2^56)");
+  if (int rc = check_trial_window(trial_start, trial_count)) return rc;
   if (!ctx || !tmpl || !out) return fail(POW_EINVAL, "null");
   if (ctx->board) return fail(POW_EINVAL, "pow_mine_rand does not run on a context bound to a stop board");
   FusedCall f(ctx, nullptr, hashes_done);
@@ -1389,36 +1411,22 @@ int pow_mine_rand(pow_ctx* ctx, const pow_block* tmpl, uint32_t seed, uint64_t t
   memset(&L, 0, sizeof L);
   L.run = plan.run;
   L.nwg = plan.nwg;
-  uint32_t to_next[POW_RAND_WORDS];  // from a launch's first trial to the next launch's
-  pow_rand_power(9ull * L.run * ((uint64_t)L.nwg * 256u - 1u), H->step);
-  pow_rand_power(9ull * plan.launch, to_next);
-  {
-    uint32_t jump[POW_RAND_WORDS];
-    pow_rand_seed(seed, H->state);
-    pow_rand_power(9ull * trial_start, jump);
-    pow_rand_apply(jump, H->state, H->state);
-  }
+  uint32_t first[POW_RAND_WORDS], to_next[POW_RAND_WORDS];
+  pow_rand_jumps(L.run, L.nwg, trial_start, plan.launch, H->step, first, to_next);
+  pow_rand_seed(seed, H->state);
+  pow_rand_apply(first, H->state, H->state);
   for (uint64_t off = 0; off < trial_count; off += plan.launch) {
     if (cancel_moved(cancel_word, epoch)) return f.finish(0);
     const uint64_t n = std::min<uint64_t>(plan.launch, trial_count - off);
     L.count = (uint32_t)n;
-    if (ctx->rand_tab_run != plan.run) {
-      // The tables of this T go up once, in front of the first launch that
-      // needs them and under its bounded wait: they count as there, and their
-      // pinned twin as free, once that wait has returned.
-      pow_rand_tables(plan.run, ctx->h_rtab.p);
-      ctx->rand_tab_run = 0;
-      HIP_OK(hipMemcpyAsync(ctx->d_rtab.p, ctx->h_rtab.p, POW_RAND_TAB_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice,
-                            ctx->stream));
-    }
+    if (int rc = stage_rand_tables(ctx, plan.run)) return rc;
     H->ctl = PowBatchCtl{~0ull, 0ull};
     HIP_OK(hipMemcpyAsync(D, H, sizeof *H, hipMemcpyHostToDevice, ctx->stream));
     if (int rc = timed_begin(ctx)) return rc;
     HIP_OK(pow_launch_rand(ctx->stream, L, D, ctx->d_rtab.p, &D->ctl, ctx->d_rnslot.p, ctx->d_rnchar.p, ctx->d_rrec.p));
     HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
     HIP_OK(hipMemcpyAsync(ctx->h_rrec.p, ctx->d_rrec.p, sizeof(PowRandRec), hipMemcpyDeviceToHost, ctx->stream));
-    if (int rc = timed_end(ctx, "rand mining launch", 2ull * n, 1u, &f.total)) return rc;  // 2 ns per trial
-    ctx->rand_tab_run = plan.run;
+    if (int rc = rand_timed_end(ctx, "rand mining launch", 2ull * n, plan.run, &f.total)) return rc;  // 2 ns per trial
     const PowRandRec& r = *ctx->h_rrec.p;
     f.total.hashes += r.trials;
     if (r.rel == ~0ull) {
@@ -1477,10 +1485,7 @@ int pow_find_seed(pow_ctx* ctx, const char* nonces, size_t n_targets, uint32_t s
   if (n_targets == 0 || n_targets > POW_SEED_MAX_TARGETS)
     return fail(POW_EINVAL, "n_targets %zu not in 1..%d", n_targets, POW_SEED_MAX_TARGETS);
   if (n_seeds == 0 || n_seeds > POW_SEED_MAX_SEEDS) return fail(POW_EINVAL, "n_seeds %u not in 1..2^20", n_seeds);
-  if (trial_count == 0 || trial_count > (1ull << 32))
-    return fail(POW_EINVAL, "trial_count %llu not in 1..2^32", (unsigned long long)trial_count);
-  if (trial_start > POW_RAND_TRIAL_LIMIT || trial_count > POW_RAND_TRIAL_LIMIT - trial_start)
-    return fail(POW_EINVAL, "trial range past POW_RAND_TRIAL_LIMIT (2^56)");
+  if (int rc = check_trial_window(trial_start, trial_count)) return rc;
   if (!ctx || !nonces || !n_found || (!out && cap)) return fail(POW_EINVAL, "null");
   uint32_t tgt[POW_SEED_MAX_TARGETS][2];
   for (size_t k = 0; k < n_targets; ++k)
@@ -1509,9 +1514,7 @@ int pow_find_seed(pow_ctx* ctx, const char* nonces, size_t n_targets, uint32_t s
   L.run = plan.run;
   L.nwg = plan.nwg;
   uint32_t first[POW_RAND_WORDS], to_next[POW_RAND_WORDS];  // to the call's first trial; from a slice's to the next's
-  pow_rand_power(9ull * L.run * ((uint64_t)L.nwg * 256u - 1u), H->step);
-  pow_rand_power(9ull * trial_start, first);
-  pow_rand_power(9ull * plan.slice, to_next);
+  pow_rand_jumps(L.run, L.nwg, trial_start, plan.slice, H->step, first, to_next);
   std::vector<SeedHit> hits;
   for (uint32_t base = 0; base < n_seeds; base += plan.tile) {
     L.pos_base = base;
@@ -1521,12 +1524,7 @@ int pow_find_seed(pow_ctx* ctx, const char* nonces, size_t n_targets, uint32_t s
       if (cancel_moved(cancel_word, epoch)) return f.finish(0);
       const uint64_t n = std::min<uint64_t>(plan.slice, trial_count - off);
       L.count = (uint32_t)n;
-      if (ctx->rand_tab_run != plan.run) {  // the tables of this T, as pow_mine_rand's
-        pow_rand_tables(plan.run, ctx->h_rtab.p);
-        ctx->rand_tab_run = 0;
-        HIP_OK(hipMemcpyAsync(ctx->d_rtab.p, ctx->h_rtab.p, POW_RAND_TAB_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice,
-                              ctx->stream));
-      }
+      if (int rc = stage_rand_tables(ctx, plan.run)) return rc;
       HIP_OK(hipMemcpyAsync(ctx->d_seed.p, H, sizeof *H, hipMemcpyHostToDevice, ctx->stream));
       HIP_OK(hipMemsetAsync(ctx->d_sout.p, 0, offsetof(PowSeedOut, rec), ctx->stream));
       if (int rc = timed_begin(ctx)) return rc;
@@ -1534,8 +1532,7 @@ int pow_find_seed(pow_ctx* ctx, const char* nonces, size_t n_targets, uint32_t s
       HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
       HIP_OK(hipMemcpyAsync(ctx->h_sout.p, ctx->d_sout.p, sizeof(PowSeedOut), hipMemcpyDeviceToHost, ctx->stream));
       const uint64_t pairs = (uint64_t)L.n_seeds * n;
-      if (int rc = timed_end(ctx, "seed search launch", 2ull * pairs, 1u, &f.total)) return rc;  // 2 ns per pair
-      ctx->rand_tab_run = plan.run;
+      if (int rc = rand_timed_end(ctx, "seed search launch", 2ull * pairs, plan.run, &f.total)) return rc;  // 2 ns per pair
       f.total.hashes += pairs;
       const PowSeedOut& r = *ctx->h_sout.p;
       if (r.n > POW_SEED_DEV_CAP)

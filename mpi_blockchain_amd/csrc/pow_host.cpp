@@ -83,6 +83,11 @@ uint32_t diff_thr(unsigned diff) { return diff >= 32 ? 0u : (0xFFFFFFFFu >> diff
 
 }  // namespace
 
+// digit_char's inverse.
+int digit_of(char c) {
+  return c >= 'a' && c <= 'z' ? c - 'a' : c >= 'A' && c <= 'Z' ? c - 'A' + 26 : c >= '0' && c <= '9' ? c - '0' + 52 : -1;
+}
+
 int fail(int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
@@ -400,20 +405,21 @@ void pow_rand_tables(uint32_t run, uint32_t* tab) {
   }
 }
 
+void pow_rand_jumps(uint32_t run, uint32_t nwg, uint64_t trial_start, uint64_t per_launch, uint32_t step[POW_RAND_WORDS],
+                    uint32_t first[POW_RAND_WORDS], uint32_t to_next[POW_RAND_WORDS]) {
+  pow_rand_power(9ull * run * ((uint64_t)nwg * 256u - 1u), step);
+  pow_rand_power(9ull * trial_start, first);
+  pow_rand_power(9ull * per_launch, to_next);
+}
+
 // ---------------- pow_find_seed (K9) ----------------
 
 bool pow_seed_pack(const char* nonce, uint32_t w[2]) {
   uint32_t d[POW_NONCE_SIZE - 1];
-  for (int i = 0; i < POW_NONCE_SIZE - 1; ++i) {  // digit_char's inverse
-    const char c = nonce[i];
-    if (c >= 'a' && c <= 'z')
-      d[i] = (uint32_t)(c - 'a');
-    else if (c >= 'A' && c <= 'Z')
-      d[i] = 26u + (uint32_t)(c - 'A');
-    else if (c >= '0' && c <= '9')
-      d[i] = 52u + (uint32_t)(c - '0');
-    else
-      return false;
+  for (int i = 0; i < POW_NONCE_SIZE - 1; ++i) {
+    const int digit = digit_of(nonce[i]);
+    if (digit < 0) return false;
+    d[i] = (uint32_t)digit;
   }
   w[0] = (d[0] << 24) | (d[1] << 18) | (d[2] << 12) | (d[3] << 6) | d[4];
   w[1] = (d[5] << 18) | (d[6] << 12) | (d[7] << 6) | d[8];

@@ -131,6 +131,13 @@ PowRandPlan pow_rand_plan(unsigned diff, uint64_t trial_count, uint32_t cu_count
 // POW_RAND_MAX_WG.  tab holds POW_RAND_TAB_WORDS words.
 #define POW_RAND_TAB_WORDS (POW_RAND_WORDS * 256u + POW_RAND_MAX_WG * POW_RAND_WORDS)
 void pow_rand_tables(uint32_t run, uint32_t* tab);
+// The three polynomials of a call of K8 or K9: step = x^(9 run (nwg 256 - 1)), from the end of a
+// lane's run to its next; first = x^(9 trial_start), to the call's first trial; to_next = x^(9
+// per_launch), from a launch's first trial to the next launch's.
+void pow_rand_jumps(uint32_t run, uint32_t nwg, uint64_t trial_start, uint64_t per_launch, uint32_t step[POW_RAND_WORDS],
+                    uint32_t first[POW_RAND_WORDS], uint32_t to_next[POW_RAND_WORDS]);
+// The digit of a character of block.cpp:61-72's alphabet (a-z, A-Z, 0-9 are 0..61), -1 of any other.
+int digit_of(char c);
 
 // ---- pow_find_seed (K9): the inverse of pow_rand_nonces ----
 // A target's nine base-62 digits as the kernel compares them: w[0] = digits

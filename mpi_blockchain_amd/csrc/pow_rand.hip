@@ -4,33 +4,28 @@
 // glibc's TYPE_3 generator r[i] = r[i-31] + r[i-3] (pow_host.h), in place of
 // the counter's nonces.  The key is the trial index relative to the launch.
 //
-// Layout.  Lane g of the launch's G = 256 x nwg lanes owns runs of T
-// consecutive trials, [p G T + g T, + T) in pass p, ascending, so a lane stops
-// as K4's does: at its first hit, at the end of the launch or once its next
-// trial lies above the lowest solving trial published so far; that word only
-// ever holds a trial that solved, so every trial below the answer is tested
-// whatever the grid is.  Nobody waits for anybody.
+// Layout.  A lane walks its runs of T trials (pow_rand_dev.h) in ascending
+// order, so it stops as K4's does: at its first hit, at the end of the launch
+// or once its next trial lies above the lowest solving trial published so far;
+// that word only ever holds a trial that solved, so every trial below the
+// answer is tested whatever the grid is.  Nobody waits for anybody.
 //
 // The generator.  A lane's state, 31 words, is a circular buffer in LDS laid
 // out [word][lane] (a wave's 64 lanes read 64 consecutive dwords: no bank
 // conflict), 31,744 bytes per workgroup.  A draw is two LDS reads, an add and
-// a store.  The lanes reach their first trial from the launch's state (the
-// host's, at the launch's first trial) through two table polynomials that
-// depend on T alone: workgroup w applies x^(9 T 256 w) cooperatively, one
-// output word per lane, then lane l applies x^(9 T l) to its own copy; from
-// the end of a run to the next, x^(9 T (G - 1)), the launch's `step`.  A lane
-// applies a polynomial c by walking its own generator: y += c[i] x (state
-// after i draws), 31 x 31 multiply-adds with the state and y in registers.
+// a store.  The lanes reach their first trial from the host's state at the
+// launch's, and hop from run to run, by the moves of pow_rand_dev.h.
+#include "pow_rand_dev.h"
 #include "pow_walk_dev.h"
 
 using namespace powwalk;
+using namespace powrand;
 
 static_assert(sizeof(PowRandRec) == 64 && offsetof(PowRandIn, state) == sizeof(PowBatchCtl),
               "the host reads and writes the records as they are");
+static_assert(WG == LANES, "the walk's workgroup is the tables'");
 
 namespace {
-
-constexpr uint32_t NW = POW_RAND_WORDS;
 
 struct RandLds {
   uint32_t st[NW][WG];      // column l: lane l's state, word i of it at row (head + i) % 31
@@ -51,28 +46,16 @@ __device__ __forceinline__ uint32_t draw(uint32_t (&st)[NW][WG], uint32_t& head)
   return v >> 1;
 }
 
-// The lane's state moved by the polynomial coef(0..30).
+// The lane's state moved by the polynomial coef(0..30): its column into registers, and back with the head at row 0.
 template <class Coef>
 __device__ __forceinline__ void apply(uint32_t (&st)[NW][WG], uint32_t& head, Coef coef) {
   const uint32_t tid = threadIdx.x;
-  uint32_t x[NW], y[NW];  // both in registers: the 961 multiply-adds read no LDS
+  uint32_t s[NW];
 #pragma unroll
-  for (uint32_t j = 0; j < NW; ++j) {
-    x[j] = st[wrap(head + j)][tid];
-    y[j] = 0u;
-  }
-#pragma unroll 1
-  for (uint32_t i = 0; i < NW; ++i) {
-    const uint32_t c = coef(i);
+  for (uint32_t j = 0; j < NW; ++j) s[j] = st[wrap(head + j)][tid];
+  powrand::apply(s, coef);
 #pragma unroll
-    for (uint32_t j = 0; j < NW; ++j) y[j] += c * x[j];
-    const uint32_t next = x[0] + x[28];  // the window moves on by one draw
-#pragma unroll
-    for (uint32_t j = 0; j + 1u < NW; ++j) x[j] = x[j + 1u];
-    x[NW - 1u] = next;
-  }
-#pragma unroll
-  for (uint32_t j = 0; j < NW; ++j) st[j][tid] = y[j];
+  for (uint32_t j = 0; j < NW; ++j) st[j][tid] = s[j];
   head = 0u;
 }
 
@@ -100,23 +83,13 @@ __global__ __launch_bounds__(256) void pow_rand_kernel(const PowRandLaunch L, co
          (sh.tm[0] << 24) | ((sh.tm[1] & 0xFFu) << 16) | ((sh.tm[2] & 0xFFu) << 8) | (sh.tm[4] & 0xFFu));
 
   // ---- the workgroup's state: the launch's moved by x^(9 T 256 part) ----
-  if (tid == 0)
-    for (uint32_t k = NW; k < 2u * NW - 1u; ++k) sh.xe[k] = sh.xe[k - NW] + sh.xe[k - 3u];
-  __syncthreads();
-  uint32_t mine = 0u;
-  if (tid < NW) {
-    const uint32_t* const b = tab + NW * WG + part * NW;
-    for (uint32_t i = 0; i < NW; ++i) mine += b[i] * sh.xe[i + tid];
-  }
-  __syncthreads();
-  if (tid < NW) sh.xe[tid] = mine;
-  __syncthreads();  // also: msg0 and kw are expanded
+  group_move(sh.xe, tab + NW * LANES + part * NW);  // its last barrier also: msg0 and kw are expanded
 
   // ---- the lane's: that moved by x^(9 T tid) ----
 #pragma unroll
   for (uint32_t j = 0; j < NW; ++j) sh.st[j][tid] = sh.xe[j];
   uint32_t head = 0u;
-  apply(sh.st, head, [&](uint32_t i) { return tab[i * WG + tid]; });
+  apply(sh.st, head, [&](uint32_t i) { return tab[i * LANES + tid]; });
 
   // ---- the walk ----
   Hit me;
@@ -125,9 +98,8 @@ __global__ __launch_bounds__(256) void pow_rand_kernel(const PowRandLaunch L, co
   for (int k = 0; k < 8; ++k) me.digest[k] = 0u;
   me.trials = 0;
   uint32_t nonce_w[3] = {0u, 0u, 0u};
-  const uint32_t hop_by = L.nwg * WG * L.run - L.run;  // from the end of a run to the lane's next
-  uint32_t rel = (part * WG + tid) * L.run;            // all below 2^27: the launch wrapper's bounds
-  uint32_t in_run = 0u;
+  const uint32_t hop_by = hop_of(L.nwg, L.run);
+  uint32_t rel = first_rel(part, L.run), in_run = 0u;
   bool go = rel < L.count;
   while (go) {
     uint32_t c[9], h[8];

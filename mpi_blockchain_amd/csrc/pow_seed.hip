@@ -2,18 +2,14 @@
 // the REFERENCE draws (pow_rand.hip, pow_host.h), without the hash.  Every
 // (seed, trial) pair of the launch's tile of seeds and slice of trials is
 // compared with up to 64 target nonces, and every match is recorded: the search
-// is exhaustive, nothing stops early and nobody waits for anybody.
+// is exhaustive, nothing stops early and nobody waits for anybody.  The
+// generator's moves and the layout of the runs are pow_rand_dev.h's.
 //
-// Layout.  blockIdx.x = (seed position within the tile, part): each seed has
-// nwg workgroups, and lane g of a seed's G = 256 x nwg lanes owns runs of T
-// consecutive trials, [p G T + g T, + T) in pass p, as in K8.
-//
-// Seeding.  One lane of the workgroup restates pow_rand_seed (pow_host.cpp):
-// the 30 Lehmer steps and the 310 discarded ones, in registers.  The workgroup
-// moves that state to the slice's first trial by the launch's polynomial (the
-// same for every seed), then to its own part by table B, cooperatively, one
-// output word per lane; lane l moves its copy by table A's x^(9 T l), and from
-// the end of a run to the next by the launch's `step`, as in K8.
+// Seeding.  blockIdx.x = (seed position within the tile, part): each seed has
+// nwg workgroups.  One lane of each restates pow_rand_seed (pow_host.cpp): the
+// 30 Lehmer steps and the 310 discarded ones, in registers.  The workgroup moves
+// that state to the slice's first trial by the launch's polynomial (the same
+// for every seed), then on by the tables.
 //
 // The walk.  With no SHA-256 in the lane the 31-word state is 31 VGPRs.  One
 // iteration is 31 trials = 279 draws, fully unrolled: lcm(9, 31) = 279, so the
@@ -25,17 +21,13 @@
 // and the target list walked.  One table alone lets 64 targets through in 1.7 %
 // of a lane's trials, which is two of three trials of a wave of 64, and the wave
 // pays for the list whenever one lane walks it: the second table brings that
-// down to 1.8 % of a wave's trials.  A lane walks whole iterations
-// and never tests the slice's end per trial: the bound is applied where a match
-// is recorded.
-#include <hip/hip_runtime.h>
+// down to 1.8 % of a wave's trials.  A lane walks whole iterations and never
+// tests the slice's end per trial: the bound is applied where a match is recorded.
+#include "pow_rand_dev.h"
 
-#include "pow_ctx.h"
+using namespace powrand;
 
 namespace {
-
-constexpr uint32_t NW = POW_RAND_WORDS;
-constexpr uint32_t WG = 256u;
 
 struct SeedLds {
   uint32_t xe[2 * NW + 2];                 // the workgroup's state, extended to 61 words
@@ -63,46 +55,6 @@ __device__ __forceinline__ void seed_state(uint32_t seed, uint32_t (&x)[NW]) {
   for (uint32_t i = 34; i < 344; ++i) r[i % NW] += r[(i - 3u) % NW];
 #pragma unroll
   for (uint32_t j = 0; j < NW; ++j) x[j] = r[(j + 3u) % NW];
-}
-
-// The workgroup's state xe[0..30] moved by the polynomial c, as K8 moves its
-// own: the 61-word extension, then one output word per lane.  On entry the
-// state is visible to lane 0; on return the new one to every lane.
-__device__ __forceinline__ void group_move(uint32_t (&xe)[2 * NW + 2], const uint32_t* __restrict__ c) {
-  const uint32_t tid = threadIdx.x;
-  if (tid == 0)
-    for (uint32_t k = NW; k < 2u * NW - 1u; ++k) xe[k] = xe[k - NW] + xe[k - 3u];
-  __syncthreads();
-  uint32_t mine = 0u;
-  if (tid < NW)
-    for (uint32_t i = 0; i < NW; ++i) mine += c[i] * xe[i + tid];
-  __syncthreads();
-  if (tid < NW) xe[tid] = mine;
-  __syncthreads();
-}
-
-// The lane's state moved by the polynomial coef(0..30): y += c[i] x (the state
-// after i draws), K8's step with nothing in LDS.
-template <class Coef>
-__device__ __forceinline__ void apply(uint32_t (&s)[NW], Coef coef) {
-  uint32_t x[NW], y[NW];
-#pragma unroll
-  for (uint32_t j = 0; j < NW; ++j) {
-    x[j] = s[j];
-    y[j] = 0u;
-  }
-#pragma unroll 1
-  for (uint32_t i = 0; i < NW; ++i) {
-    const uint32_t c = coef(i);
-#pragma unroll
-    for (uint32_t j = 0; j < NW; ++j) y[j] += c * x[j];
-    const uint32_t next = x[0] + x[28];  // the window moves on by one draw
-#pragma unroll
-    for (uint32_t j = 0; j + 1u < NW; ++j) x[j] = x[j + 1u];
-    x[NW - 1u] = next;
-  }
-#pragma unroll
-  for (uint32_t j = 0; j < NW; ++j) s[j] = y[j];
 }
 
 // A trial that passed both tables: the target list, and a record
@@ -142,18 +94,17 @@ __global__ __launch_bounds__(256) void pow_seed_kernel(const PowSeedLaunch L, co
     for (uint32_t j = 0; j < NW; ++j) sh.xe[j] = s0[j];
   }
   group_move(sh.xe, in->jump);
-  group_move(sh.xe, tab + NW * WG + part * NW);  // table B's x^(9 T 256 part)
+  group_move(sh.xe, tab + NW * LANES + part * NW);  // table B's x^(9 T 256 part)
 
   // ---- the lane's: that moved by table A's x^(9 T tid) ----
   uint32_t x[NW];
 #pragma unroll
   for (uint32_t j = 0; j < NW; ++j) x[j] = sh.xe[j];
-  apply(x, [&](uint32_t i) { return tab[i * WG + tid]; });
+  apply(x, [&](uint32_t i) { return tab[i * LANES + tid]; });
 
   // ---- the walk ----
-  const uint32_t iters = L.run / NW;
-  const uint32_t hop_by = L.nwg * WG * L.run - L.run;  // from the end of a run to the lane's next
-  uint32_t rel = (part * WG + tid) * L.run;            // all below 2^27: the launch wrapper's bounds
+  const uint32_t iters = L.run / NW, hop_by = hop_of(L.nwg, L.run);
+  uint32_t rel = first_rel(part, L.run);
   while (rel < L.count) {
 #pragma unroll 1
     for (uint32_t it = 0; it < iters; ++it) {
@@ -195,6 +146,6 @@ hipError_t pow_launch_seed(hipStream_t stream, const PowSeedLaunch& L, const Pow
       L.count == 0 || L.count > (1u << 26) || L.n_seeds == 0 || (uint64_t)L.n_seeds * L.nwg > (1u << 16) ||
       (uint64_t)L.pos_base + L.n_seeds > POW_SEED_MAX_SEEDS)
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(pow_seed_kernel, dim3(L.n_seeds * L.nwg), dim3(WG), 0, stream, L, in, tab, out);
+  hipLaunchKernelGGL(pow_seed_kernel, dim3(L.n_seeds * L.nwg), dim3(LANES), 0, stream, L, in, tab, out);
   return hipGetLastError();
 }

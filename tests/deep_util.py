@@ -5,7 +5,6 @@ here calls the code under test: every expected value is hashlib's, directly or
 through the host statements block.mine_chain, block.mine_batch and
 block.mine_race over the 100 counters around the stretch's solution (sealing
 does not depend on ctr_start)."""
-import contextlib
 import functools
 import hashlib
 import json
@@ -16,6 +15,7 @@ from oracle.oracle import py_block_to_str, py_nonce_from_counter
 
 import batch_util as bu
 import chain_util as cu
+import helpers
 import race_util as ru
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -122,21 +122,6 @@ ROW_NAMES = ("far", "max_window", "one", "nines", "step3", "step4", "key_over", 
 SWAPPED_ROWS = ("step3", "step4", "key_over", "key_under")  # the race with owners [261, 5] too
 
 
-@contextlib.contextmanager
 def miner_with(**switches):
     """A context of the test library whose pow_init saw exactly these switches."""
-    from mpi_blockchain_amd.miner import GpuMiner
-
-    saved = {k: os.environ.pop(k, None) for k in SWITCHES}
-    os.environ.update({k: str(v) for k, v in switches.items()})
-    try:
-        m = GpuMiner(0, test_hooks=True)
-    finally:
-        for k, v in saved.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-    try:
-        yield m
-    finally:
-        m.close()
+    return helpers.hooked_miner(SWITCHES, **switches)

@@ -1,4 +1,6 @@
-"""Shared helpers for the tests (builds Blocks from golden.json entries)."""
+"""Shared helpers for the tests (builds Blocks from golden.json entries; opens
+contexts of the test library under its switches)."""
+import contextlib
 import ctypes
 import os
 import subprocess
@@ -6,6 +8,28 @@ import tempfile
 
 from mpi_blockchain_amd._lib import Block
 from mpi_blockchain_amd.block import make_block, set_field
+
+
+@contextlib.contextmanager
+def hooked_miner(clear, **switches):
+    """A context of the test library whose pow_init saw exactly the given
+    POW_* switches: the names in `clear` are taken out of the environment while
+    it opens, and the environment is as it was once it has."""
+    from mpi_blockchain_amd.miner import GpuMiner
+
+    saved = {k: os.environ.pop(k, None) for k in (*clear, *switches)}
+    os.environ.update({k: str(v) for k, v in switches.items()})
+    try:
+        m = GpuMiner(0, test_hooks=True)
+    finally:
+        for k, v in saved.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+    try:
+        yield m
+    finally:
+        m.close()
 
 
 def block_from_template(t: dict) -> Block:

@@ -1,36 +1,21 @@
 """What the GPU tests of pow_mine_rand (K8) share: contexts of the test library
 under its three switches, the call through the C ABI with poisoned outputs, and
 the brute force of tests/rand_util.py, computed once per case."""
-import contextlib
 import ctypes
 import functools
-import os
 
+import helpers
 import rand_util
 from mpi_blockchain_amd import _lib
-from mpi_blockchain_amd.miner import GpuMiner
 
 SWITCHES = ("POW_RAND_RUN", "POW_RAND_LANES_LOG2", "POW_RAND_LAUNCH_LOG2")
 SEED = 1700000003  # time + rank
 POISON = b"\xA5" * 552
 
 
-@contextlib.contextmanager
 def miner_with(**switches):
     """A context of the test library whose pow_init saw the given switches."""
-    saved = {k: os.environ.pop(k, None) for k in SWITCHES}
-    os.environ.update({k: str(v) for k, v in switches.items()})
-    try:
-        m = GpuMiner(0, test_hooks=True)
-    finally:
-        for k, v in saved.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-    try:
-        yield m
-    finally:
-        m.close()
+    return helpers.hooked_miner(SWITCHES, **switches)
 
 
 def raw(b) -> bytes:

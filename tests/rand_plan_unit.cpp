@@ -1,7 +1,7 @@
 // The host side of pow_mine_rand (K8) on the CPU: pow_rand_plan, pow_rand_tables
 // and the polynomials the kernel consumes (csrc/pow_host.cpp), linked with
 // pow_host.cpp alone and run under AddressSanitizer + UndefinedBehaviorSanitizer
-// by tests/test_rand_host.py.  Three parts:
+// by tests/test_rand_host.py.  Four parts:
 //   a. the plan over every difficulty, window, chip size and override of the
 //      lists below: what pow_host.h promises, what the kernel's 32-bit trial
 //      index needs, and that the planned run is the least that covers;
@@ -10,7 +10,9 @@
 //   c. the lane walk of pow_rand.hip restated (rel, in_run, hop_by, the step
 //      polynomial): every trial of the launch is visited exactly once, with the
 //      nonce of pow_rand_nonces.  A model, not the kernel: it pins the
-//      host-made polynomials and the arithmetic the kernel copies.
+//      host-made polynomials and the arithmetic the kernel copies;
+//   d. what pow_mine_rand and pow_find_seed share: pow_rand_jumps against
+//      pow_rand_power, and digit_of against the alphabet, every byte value.
 #include <algorithm>
 #include <climits>
 #include <cstdint>
@@ -200,12 +202,44 @@ void lane_walk() {
     }
 }
 
+// ---- d ----
+void jumps_and_digits() {
+  const uint32_t runs[] = {1, 31, 1024}, nwgs[] = {1, 256};
+  const uint64_t starts[] = {0, 1, (1ull << 56) - 1}, per_launch[] = {1, 31ull * 256, 1ull << 26};
+  for (uint32_t run : runs)
+    for (uint32_t nwg : nwgs)
+      for (uint64_t start : starts)
+        for (uint64_t per : per_launch) {
+          uint32_t got[3][POW_RAND_WORDS], want[3][POW_RAND_WORDS];
+          memset(got, 0xA5, sizeof got);
+          pow_rand_jumps(run, nwg, start, per, got[0], got[1], got[2]);
+          pow_rand_power(9ull * run * ((uint64_t)nwg * 256u - 1u), want[0]);
+          pow_rand_power(9ull * start, want[1]);
+          pow_rand_power(9ull * per, want[2]);
+          CHECK(memcmp(got, want, sizeof got) == 0, "jumps run=%u nwg=%u start=%llu per_launch=%llu", run, nwg,
+                (unsigned long long)start, (unsigned long long)per);
+        }
+  // digit_of against digit_char, which pow_nonce_from_counter writes: its last character is digit ctr % 62
+  bool in_alphabet[256] = {false};
+  for (int k = 0; k < 62; ++k) {
+    char nonce[POW_NONCE_SIZE];
+    const bool ok = pow_nonce_from_counter((uint64_t)k, nonce) == POW_OK;
+    CHECK(ok && digit_of(nonce[POW_NONCE_SIZE - 2]) == k, "digit_of('%c') = %d, digit %d", nonce[POW_NONCE_SIZE - 2],
+          digit_of(nonce[POW_NONCE_SIZE - 2]), k);
+    if (ok) in_alphabet[(uint8_t)nonce[POW_NONCE_SIZE - 2]] = true;
+  }
+  CHECK(std::count(in_alphabet, in_alphabet + 256, true) == 62, "62 distinct characters");
+  for (int b = 0; b < 256; ++b)
+    if (!in_alphabet[b]) CHECK(digit_of((char)b) == -1, "digit_of(byte %d) = %d", b, digit_of((char)b));
+}
+
 }  // namespace
 
 int main() {
   plan_sweep();
   tables();
   lane_walk();
+  jumps_and_digits();
   printf("%ld checks, %ld failed\n", checks, failed);
   return failed ? 1 : 0;
 }

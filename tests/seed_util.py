@@ -3,14 +3,14 @@ pow_rand_nonces (pinned to the reference's own gen_random_nonce by
 tests/golden/rand_replay.json: tests/test_rand_host.py and test_seed_host.py),
 contexts of the test library under its three switches and the call through the C
 ABI with a poisoned output."""
-import contextlib
 import ctypes
 import functools
 import json
 import os
 
+import helpers
 from mpi_blockchain_amd import _lib
-from mpi_blockchain_amd.miner import GpuMiner, rand_nonces
+from mpi_blockchain_amd.miner import rand_nonces
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SWITCHES = ("POW_SEED_RUN", "POW_SEED_WG", "POW_SEED_LAUNCH_LOG2")
@@ -54,22 +54,9 @@ def find_seed_ref(nonces, seed_first: int, n_seeds: int, start: int, count: int)
     return out
 
 
-@contextlib.contextmanager
 def miner_with(**switches):
     """A context of the test library whose pow_init saw the given switches."""
-    saved = {k: os.environ.pop(k, None) for k in SWITCHES}
-    os.environ.update({k: str(v) for k, v in switches.items()})
-    try:
-        m = GpuMiner(0, test_hooks=True)
-    finally:
-        for k, v in saved.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-    try:
-        yield m
-    finally:
-        m.close()
+    return helpers.hooked_miner(SWITCHES, **switches)
 
 
 def pack(nonces) -> bytes:

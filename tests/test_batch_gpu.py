@@ -3,7 +3,6 @@
 over all 552 bytes of every block.  The statement never runs the code under
 test; d <= 11 keeps it at a few thousand hashlib calls per template.  K5 is
 forced (POW_BATCH_FUSED_MAX=32, test library) unless a test says otherwise."""
-import contextlib
 import ctypes
 import os
 import random
@@ -16,6 +15,7 @@ from mpi_blockchain_amd.block import field, make_block, mine_batch, nonce_from_c
 from mpi_blockchain_amd.miner import GpuMiner, StopBoard
 
 import batch_util as bu
+import helpers
 
 pytestmark = pytest.mark.gpu
 
@@ -24,22 +24,9 @@ PKG = os.path.join(ROOT, "mpi_blockchain_amd")
 SWITCHES = ("POW_BATCH_FUSED_MAX", "POW_BATCH_TILE", "POW_BATCH_LANES_LOG2")
 
 
-@contextlib.contextmanager
 def miner_with(**switches):
     """A context of the test library whose pow_init saw the given switches."""
-    saved = {k: os.environ.pop(k, None) for k in SWITCHES}
-    os.environ.update({k: str(v) for k, v in switches.items()})
-    try:
-        m = GpuMiner(0, test_hooks=True)
-    finally:
-        for k, v in saved.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-    try:
-        yield m
-    finally:
-        m.close()
+    return helpers.hooked_miner(SWITCHES, **switches)
 
 
 @pytest.fixture(scope="module")

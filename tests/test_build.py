@@ -509,6 +509,26 @@ def timed_section_helpers() -> dict:
     return h
 
 
+def rand_frame_helpers() -> str:
+    """What pow_mine_rand and pow_find_seed share of their host frame, as one
+    text: pow_api.cpp's table upload and the closer that commits it, and
+    pow_host.cpp's three polynomials.  The closer holds the one timed_end( of a
+    launch; the upload waits for nothing."""
+    stage, end = api_function("stage_rand_tables"), api_function("rand_timed_end")
+    host = open(os.path.join(CSRC, "pow_host.cpp")).read()
+    jumps = host[host.index("void pow_rand_jumps("):]
+    jumps = jumps[:jumps.index("\n}\n")]
+    assert not null_stream_calls(stage + end)
+    assert len(re.findall(r"\btimed_end\(", end)) == 1 and "stream_wait_for(" not in stage + end
+    assert "timed_end(" not in stage and "hip" not in jumps.lower()
+    # the cache word: cleared with the upload, set only behind the wait
+    assert re.search(r"rand_tab_run = 0;\s+HIP_OK\(hipMemcpyAsync\(ctx->d_rtab\.p", stage)
+    assert re.search(r"timed_end\([^\n]*\) return rc;\s+ctx->rand_tab_run = run;", end)
+    api = open(os.path.join(CSRC, "pow_api.cpp")).read()
+    assert len(re.findall(r"rand_tab_run = ", api)) == 2
+    return stage + end + jumps
+
+
 def test_no_null_stream_in_library_sources():
     found = {}
     for p in SHIPPED_SOURCES:

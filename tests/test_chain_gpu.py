@@ -2,7 +2,6 @@
 (mpi_blockchain_amd.block.mine_chain, hashlib on the CPU): every comparison is
 over all 552 bytes of every block.  The statement never runs the code under
 test; d <= 12 keeps it at a few thousand hashlib calls per block."""
-import contextlib
 import ctypes
 import os
 import random
@@ -18,6 +17,7 @@ from mpi_blockchain_amd.block import field, make_block, mine_chain, nonce_from_c
 from mpi_blockchain_amd.miner import GpuMiner, StopBoard, refresh_template
 
 import chain_util as cu
+import helpers
 
 pytestmark = pytest.mark.gpu
 
@@ -26,22 +26,9 @@ PKG = os.path.join(ROOT, "mpi_blockchain_amd")
 SWITCHES = ("POW_CHAIN_BATCH", "POW_CHAIN_FUSED_MAX", "POW_CHAIN_LANES_LOG2")
 
 
-@contextlib.contextmanager
 def miner_with(**switches):
     """A context of the test library whose pow_init saw the given switches."""
-    saved = {k: os.environ.pop(k, None) for k in SWITCHES}
-    os.environ.update({k: str(v) for k, v in switches.items()})
-    try:
-        m = GpuMiner(0, test_hooks=True)
-    finally:
-        for k, v in saved.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-    try:
-        yield m
-    finally:
-        m.close()
+    return helpers.hooked_miner(SWITCHES, **switches)
 
 
 @pytest.fixture(scope="module")

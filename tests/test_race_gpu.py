@@ -4,7 +4,6 @@ over all 552 bytes of every block.  The statement never runs the code under
 test; d <= 11 and windows of at most 2^16 keep it at a few thousand hashlib
 calls per height.  K6 is forced (POW_RACE_FUSED_MAX=32, test library) unless a
 test says otherwise."""
-import contextlib
 import ctypes
 import os
 import random
@@ -17,6 +16,7 @@ from mpi_blockchain_amd.block import field, make_block, mine_race, nonce_from_co
 from mpi_blockchain_amd.miner import GpuMiner, StopBoard, refresh_template
 
 import chain_util as cu
+import helpers
 import race_util as ru
 
 pytestmark = pytest.mark.gpu
@@ -26,22 +26,9 @@ PKG = os.path.join(ROOT, "mpi_blockchain_amd")
 SWITCHES = ("POW_RACE_FUSED_MAX", "POW_RACE_BATCH", "POW_RACE_LANES_LOG2", "POW_CHAIN_FUSED_MAX")
 
 
-@contextlib.contextmanager
 def miner_with(**switches):
     """A context of the test library whose pow_init saw the given switches."""
-    saved = {k: os.environ.pop(k, None) for k in SWITCHES}
-    os.environ.update({k: str(v) for k, v in switches.items()})
-    try:
-        m = GpuMiner(0, test_hooks=True)
-    finally:
-        for k, v in saved.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-    try:
-        yield m
-    finally:
-        m.close()
+    return helpers.hooked_miner(SWITCHES, **switches)
 
 
 @pytest.fixture(scope="module")

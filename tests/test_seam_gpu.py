@@ -9,9 +9,7 @@ zero bits, so each side of the seam has an accept and a reject.
 Every expected value is hashlib's (seam_util, the host statements
 block.mine_chain, block.mine_batch, block.mine_race and block.verify_chain) or
 Python's bit_length."""
-import contextlib
 import ctypes
-import os
 
 import numpy as np
 import pytest
@@ -40,22 +38,9 @@ CONTEXTS = {"shipped": None, "k1_only": {"POW_LAT_MAX": 0}, "force_full": {"POW_
             "lat_asm_full": {"POW_LAT_WPS": 4, "POW_FORCE_FULL": 1}}
 
 
-@contextlib.contextmanager
 def miner_with(**switches):
     """A context of the test library whose pow_init saw exactly these switches."""
-    saved = {k: os.environ.pop(k, None) for k in SWITCHES}
-    os.environ.update({k: str(v) for k, v in switches.items()})
-    try:
-        m = GpuMiner(0, test_hooks=True)
-    finally:
-        for k, v in saved.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-    try:
-        yield m
-    finally:
-        m.close()
+    return helpers.hooked_miner(SWITCHES, **switches)
 
 
 @pytest.fixture(scope="module", params=list(CONTEXTS))

@@ -10,7 +10,7 @@ import pytest
 
 from mpi_blockchain_amd import _lib
 
-from test_build import CSRC, ROOT, api_function, null_stream_calls, timed_section_helpers
+from test_build import CSRC, ROOT, api_function, null_stream_calls, rand_frame_helpers, timed_section_helpers
 
 KERNEL = "_Z15pow_seed_kernel"
 SWITCHES = (b"POW_SEED_RUN", b"POW_SEED_WG", b"POW_SEED_LAUNCH_LOG2")
@@ -45,7 +45,7 @@ def test_seed_kernel_has_no_scratch(metadata):
     md = metadata
     assert md["private_segment_fixed_size"] == 0, md
     assert md["vgpr_spill_count"] == 0 and md["sgpr_spill_count"] == 0, md
-    assert md["vgpr_count"] <= 128, md
+    assert md["vgpr_count"] <= 128, md  # where it stood before the generator moved to pow_rand_dev.h, too
     assert md["wavefront_size"] == 64 and md["max_flat_workgroup_size"] == 256, md
 
 
@@ -59,6 +59,7 @@ def test_seed_kernel_state_is_not_in_lds(metadata):
     lds = metadata["group_segment_fixed_size"]
     assert 62 * 8 + 64 * 8 <= lds < 4 * 1024, lds
     assert lds < 31 * 256 * 4
+    assert lds == 1760, lds  # the layout did not move with the generator
 
 
 def test_seed_kernel_is_in_both_libraries():
@@ -79,18 +80,25 @@ def test_no_null_stream_in_seed_sources():
             found[f] = hits
     assert not found, found
     # one plain stream launch behind one bounded wait per launch, through the timed section; no graph
-    body, h = api_function("pow_find_seed"), timed_section_helpers()
+    # (the call's timed_end( is rand_timed_end(, the closer it shares with pow_mine_rand)
+    body, h, shared = api_function("pow_find_seed"), timed_section_helpers(), rand_frame_helpers()
     union = body + h["timed_begin"] + h["timed_end"]
     assert not null_stream_calls(union)
     assert body.count("pow_launch_seed(ctx->stream") == 1 and body.count("timed_begin(") == 1
     assert body.count("timed_end(") == 1 and union.count("stream_wait_for(") == 1
+    assert body.count("rand_timed_end(") == 1 and body.count("stage_rand_tables(") == 1
     kernel = open(os.path.join(CSRC, "pow_seed.hip")).read()
-    assert "hipGraph" not in union and "hipGraph" not in kernel
+    assert "hipGraph" not in union + shared and "hipGraph" not in kernel
     assert kernel.count("hipLaunchKernelGGL(pow_seed_kernel") == 1 and "<<<" not in kernel
+    # the tables go up first, then the launch's input, then the timed section
+    order = [body.index(s) for s in ("stage_rand_tables(", "hipMemcpyAsync(ctx->d_seed.p, H,", "timed_begin(",
+                                     "pow_launch_seed(", "rand_timed_end(")]
+    assert order == sorted(order)
     # the generator, the plan and the packing are the HIP-free ones
     host = open(os.path.join(CSRC, "pow_host.cpp")).read()
     for fn in ("pow_seed_plan(", "pow_seed_pack(", "pow_rand_power(", "pow_rand_mul(", "pow_rand_tables("):
-        assert fn in body and fn in host, fn
+        assert fn in body + shared and fn in host, fn
+    assert "pow_rand_jumps(" in body
     assert "hip" not in re.sub(r"//[^\n]*", "", host[host.index("bool pow_seed_pack"):host.index('extern "C"')]).lower()
     # there is no per-seed host work: the host's seeding is not called
     assert "pow_rand_seed(" not in body
@@ -107,9 +115,13 @@ def test_no_libc_generator_in_the_sources():
 def test_seed_kernel_never_waits_for_another_workgroup():
     """No grid barrier and no loop on a word another workgroup writes: the only
     word the workgroups share is the match counter, and nobody reads it but
-    through the atomic add that reserves a slot."""
+    through the atomic add that reserves a slot.  The generator's header,
+    which the kernel's file includes, is read with it: it has no atomic at all."""
     own = open(os.path.join(CSRC, "pow_seed.hip")).read()
-    code = re.sub(r"//[^\n]*", "", own)
+    gen = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, "pow_rand_dev.h")).read())
+    assert '#include "pow_rand_dev.h"' in own and re.findall(r'#include "([^"]+)"', gen) == ["pow_ctx.h"]
+    assert "atomic" not in gen
+    code = re.sub(r"//[^\n]*", "", own) + gen
     assert "cooperative_groups" not in code and "grid.sync" not in code and "pow_walk_dev.h" not in code
     loops = re.findall(r"\b(?:while|for)\s*\(([^\n]*)\)\s*\{?\s*$", code, flags=re.M)
     assert loops

@@ -8,6 +8,8 @@ import subprocess
 
 import pytest
 
+import helpers
+import rand_gpu_util
 import seed_util
 from seed_util import call, check_against_ref, golden_nonces, miner_with, nonce_at
 from mpi_blockchain_amd import _lib
@@ -214,7 +216,29 @@ def test_stats(shipped):
         assert (s["launches"], s["hashes"]) == (16, 4 * count) and s["kernel_ms"] > 0
 
 
-# ---- 11: the C example ----
+# ---- 11: K8 and K9 by turns on one context: the table buffer they share ----
+def test_tables_are_reloaded_between_mine_rand_and_find_seed():
+    """The two calls keep the tables of their run T in one device buffer behind
+    one cache word.  K8's T is a power of two and K9's 31 x 2^j, never equal:
+    every switch between the calls must load the tables again, or the lanes
+    start from another run's polynomials and draw other nonces."""
+    tmpl = make_block(1, 0, 9, 1700000000)
+    span = 31 * 512 + 64  # two workgroups of 256 lanes x 31 trials: one pass and the start of the next
+    offsets = [0, 31 * 256 - 1, 31 * 256, 31 * 512]
+    with helpers.hooked_miner(rand_gpu_util.SWITCHES + seed_util.SWITCHES, POW_RAND_RUN=4, POW_RAND_LANES_LOG2=8,
+                              POW_SEED_RUN=31, POW_SEED_WG=2) as m:
+        first = rand_gpu_util.check_against_brute(m, tmpl, SEED, 0, 1 << 12, 9)
+        assert first is not None
+        nonces, want = placed(SEED, offsets)
+        assert check_against_ref(m, nonces, SEED, 1, 0, span) == want
+        assert m.stats()["launches"] == 1
+        again = rand_gpu_util.check_against_brute(m, tmpl, SEED, 1 << 12, 1 << 12, 9)
+        assert again is not None and again >= 1 << 12
+        nonces, want = placed(SEED, [5 + t for t in offsets])
+        assert check_against_ref(m, nonces, SEED, 1, 5, span) == want
+
+
+# ---- 12: the C example ----
 def test_c_example(tmp_path):
     exe = str(tmp_path / "find_seed")
     subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
