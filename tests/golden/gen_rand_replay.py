@@ -32,8 +32,9 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 from oracle.oracle import OBlock, RefLib, make_oblock  # noqa: E402
 
 N_BLOCKS = 3
-# 0 counts as 1; the sign bit; all ones; and time(NULL) + mpi_rank (node.cpp:386)
-SEEDS = (0, 1, 0x80000000, 0xFFFFFFFF, 1700000000 + 3)
+# 0 counts as 1; the sign bit; all ones; time(NULL) + mpi_rank (node.cpp:386); and
+# the sign bit's two neighbours, whose first Lehmer step gives 0: r[1..30] are all zero
+SEEDS = (0, 1, 0x80000000, 0xFFFFFFFF, 1700000000 + 3, 0x7FFFFFFF, 0x80000001)
 PAIRS = ((0, "S0"), (1, "S1"), (0x80000000, "S2"), (0xFFFFFFFF, "S0"), (1700000000 + 3, "S2"))
 
 

@@ -15,6 +15,7 @@ from mpi_blockchain_amd.miner import GpuMiner
 
 import pool_util as pu
 import verify_util as vu
+from pool_util import check  # one call against the mirror: all five results and the stats
 
 pytestmark = pytest.mark.gpu
 
@@ -36,29 +37,6 @@ def tree():
 @pytest.fixture(scope="module")
 def chain65():
     return pu.flat_chain(65, 0, seed=31)
-
-
-def launches(n: int) -> int:
-    """The plan's: one K10a per host tile, K10b, K10c, ceil(log2 n) rounds of K10d, K10e."""
-    return 0 if n == 0 else (n + T - 1) // T + 3 + (n - 1).bit_length()
-
-
-def check(miner, pool, difficulty, want=None):
-    """One call over `pool` against the mirror (`want`: its five results,
-    where the caller has them already)."""
-    status, parent, depth, n_bad, best = index_blocks(pool, difficulty) if want is None else want
-    r = miner.index_blocks(pool, difficulty)
-    n = len(pool)
-    assert r.status.dtype == np.uint8 and r.status.tolist() == list(status)
-    assert r.parent.tolist() == list(parent)
-    assert r.depth.tolist() == list(depth)
-    assert r.n_bad.tolist() == list(n_bad)
-    assert r.best == best
-    assert r.ok == (not any(status))
-    s = miner.stats()
-    assert s["hashes"] == n and s["launches"] == launches(n)
-    assert (s["kernel_ms"] > 0) == (n > 0)
-    return r
 
 
 @pytest.mark.parametrize("n", [0, 1, 2, 3, 63, 64, 65])

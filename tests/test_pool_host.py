@@ -132,6 +132,57 @@ def test_mirror_against_verify_chain_on_extracted_chains(tree, what):
         assert (j == POOL_NONE) == bool(status[walk[-1]] & V_LINK)
 
 
+# ---- what the inputs of tests/test_pool_edges_gpu.py hold, from the mirror alone ----
+@pytest.mark.parametrize("case", sorted(pu.TIE_CASES))
+def test_mirror_on_the_tie_pools(case):
+    pool, best = pu.tie_pool(case)
+    index, flagged, _ = pu.TIE_CASES[case]
+    status, parent, depth, n_bad, got = index_blocks(pool, 0)
+    assert len(pool) == 600 and got == best
+    assert status == [V_HASH if k in flagged else 0 for k in range(600)] and n_bad == [s and 1 for s in status]
+    assert parent == [POOL_ROOT] * 600 and [b.index for b in pool] == [index.get(k, 9) for k in range(600)]
+    assert len({pu.name_of(b) for b in pool}) == 600  # no twins: the position alone breaks a tie
+
+
+def test_mirror_on_the_twin_storm():
+    for low_index, other_index in ((1, 257), (257, 1)):
+        pool, children = pu.twin_storm(low_index, other_index)
+        status, parent, depth, n_bad, best = index_blocks(pool, 0)
+        assert len(pool) == 804 and len({pu.name_of(b) for b in pool}) == 5 and pu.twins_in(pool, status) == 799
+        assert [parent[k] for k in children] == [3] * 100 and parent.count(POOL_ROOT) == 704
+        assert {status[k] for k in children} == {0 if low_index == 1 else V_INDEX}
+        status, parent, depth, n_bad, best = index_blocks(pool[::-1], 0)
+        assert [parent[803 - k] for k in children] == [1] * 100
+        assert {status[803 - k] for k in children} == {0 if other_index == 1 else V_INDEX}
+
+
+def test_mirror_on_the_name_sweep():
+    pool, name = pu.name_sweep()
+    assert len(pool) == 16321 and len(name) == 64 and set(name) == set(b"0123456789abcdef")
+    status, parent, depth, n_bad, best = index_blocks(pool, 0)
+    assert parent == [POOL_ROOT] * 2 + [POOL_NONE] * 16319 and status == [0] * 2 + [V_LINK] * 16319
+    assert pool[1].previous_block_hash == b"" and best == 1 and pool[1].index == 2
+
+
+def test_fuzz_pools_hold_every_case():
+    """Each pool has a sound tip and a flagged block; over the 24, every flag,
+    a twin and an orphan occur."""
+    pools_with = {V_HASH: 0, V_WORK: 0, V_LINK: 0, V_INDEX: 0, "twin": 0, "orphan": 0}
+    assert len(pu.FUZZ) == 24 and [d for _, d in pu.FUZZ] == [0, 1, 3] * 8
+    for seed, d in pu.FUZZ:
+        pool = pu.random_pool(seed)
+        status, parent, depth, n_bad, best = index_blocks(pool, d)
+        assert 190 <= len(pool) <= 715 and 0 in n_bad and any(status) and best is not None, (seed, d)
+        for f in (V_HASH, V_WORK, V_LINK, V_INDEX):
+            pools_with[f] += any(s & f for s in status)
+        pools_with["twin"] += pu.twins_in(pool, status) > 0
+        pools_with["orphan"] += POOL_NONE in parent
+        # the sound tips are exactly those whose extracted chain passes verify_chain down to a root
+        assert [b == 0 for b in n_bad] == pu.sound_tips(pool, d), seed
+    assert all(pools_with.values()), pools_with
+    assert pools_with[V_WORK] == 16  # at d = 1 and d = 3, from the blocks' own digests; none at d = 0
+
+
 def test_mirror_index_rule_and_duplicates():
     c = pu.flat_chain(4, 0, seed=21)
     # a wrong index in the high bytes is not hashed: only V_INDEX, on the block and on its child

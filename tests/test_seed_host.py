@@ -7,9 +7,11 @@ import ctypes
 import os
 import subprocess
 
+import rand_util
 import seed_util
 from mpi_blockchain_amd import _lib
 from mpi_blockchain_amd.block import nonce_from_counter
+from mpi_blockchain_amd.miner import rand_nonces
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIMIT = 1 << 56
@@ -91,6 +93,52 @@ def test_packing_round_trips_through_nonce_from_counter():
         rc = L.pow_find_seed(None, nonce_from_counter(ctr), 1, 0, 1, 0, 1, None, 0, None, 0, ctypes.byref(n_found), None)
         assert rc == _lib.POW_EINVAL and b"null" in L.pow_last_error()
     assert n_found.value == 7
+
+
+def test_seeding_through_2_pow_31():
+    """pow_rand_nonces against tests/rand_util.py for the 64 seeds around 2^31,
+    where the Lehmer step's signed division changes branch, and far down the
+    stream of the two whose state is the generator's most degenerate."""
+    for seed in range(0x7FFFFFE0, 0x80000020):
+        assert rand_nonces(seed, 0, 64) == rand_util.nonces(seed, 0, 64), hex(seed)
+    for seed in range(0x7FFFFFFE, 0x80000003):
+        zeros = rand_util.seed_words(seed)[1:31].count(0)
+        assert zeros == (30 if seed in seed_util.DEGENERATE else 0), hex(seed)
+    for seed in seed_util.DEGENERATE:
+        assert rand_util.seed_words(seed)[0] == seed
+        assert rand_nonces(seed, seed_util.DEEP, 64) == rand_util.nonces(seed, seed_util.DEEP, 64), hex(seed)
+        # ... and what the reference's own gen_random_nonce gave after srand(seed)
+        assert seed_util.golden_nonces(seed) == rand_nonces(seed, 0, 64) == rand_util.nonces(seed, 0, 64), hex(seed)
+        assert len(set(seed_util.golden_nonces(seed))) == 64  # degenerate in its seeding, not in what it draws
+
+
+def test_the_inputs_of_the_edge_tests():
+    """What tests/test_seed_edges_gpu.py asks of its inputs, and its yardstick
+    (the brute force over pow_rand_nonces) against the same search over
+    tests/rand_util.py on each of them."""
+    ru, ref = seed_util.find_seed_ru, seed_util.find_seed_ref
+    hits = seed_util.digit_edge_hits()
+    assert len(hits) == 12 and all(hits.values()), hits
+    for (at, pair), (seed, trial, n) in hits.items():
+        assert tuple(seed_util.digits(n)[at:at + 2]) == pair and rand_nonces(seed, trial, 1)[0][:9] == n
+    assert hits[0, (61, 61)] == (1700000003, 1007, b"99Z0FmjmU")
+    targets = [n for _, _, n in hits.values()]
+    want = ru(targets, 1700000003, 3, 0, 4096)
+    assert ref(targets, 1700000003, 3, 0, 4096) == want
+    assert sorted(want) == sorted((s, k, t) for k, (s, t, _) in enumerate(hits.values()))
+    # the near misses: each target but the last differs from N, two of them let a trial of N through both tables
+    stream = seed_util.ru_stream(1700000003, 0, 2048)
+    n, a, b = stream[1007], stream[5], stream[6]
+    targets = seed_util.near_misses(n, a, b)
+    d = [seed_util.digits(t) for t in targets]
+    assert len(targets) == 12 and d[0][:2] == d[11][:2] and d[0][2:4] != d[11][2:4]
+    assert d[1][2:4] == d[11][2:4] and d[1][:2] != d[11][:2]
+    assert [[i for i in range(9) if d[2 + k][i] != d[11][i]] for k in range(9)] == [[k] for k in range(9)]
+    assert ref(targets, 1700000003, 1, 0, 2048) == ru(targets, 1700000003, 1, 0, 2048) == [(1700000003, 11, 1007)]
+    # 64 equal targets under the twin seeds 0 and 1
+    targets = [rand_util.nonces(1, 5, 1)[0]] * 64
+    want = [(s, k, 5) for s in (0, 1) for k in range(64)]
+    assert ref(targets, 0xFFFFFFFE, 4, 0, 64) == ru(targets, 0xFFFFFFFE, 4, 0, 64) == want
 
 
 def test_brute_force_agrees_with_the_reference_s_recorded_nonces():
