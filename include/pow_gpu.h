@@ -327,6 +327,112 @@ int pow_index_blocks(pow_ctx* ctx, const pow_block* pool, size_t n, unsigned dif
                      uint32_t* n_bad  /* n, may be NULL */,
                      size_t* best     /* may be NULL */);
 
+/* A pool that stays on the device and is fed: pow_index_blocks' answers kept
+ * current while blocks arrive, as node_blocks grows one block at a time
+ * (node.cpp:199, 319) or by a migrated run (node.cpp:174-179).  A pow_pool
+ * keeps pow_index_blocks' 98 bytes per block and its table resident; the raw
+ * structs are not kept on the device, the host owns them as before.
+ * The contract.  A block's position is the order of its arrival.  After any
+ * sequence of adds, status, parent, depth, n_bad (pow_pool_read), best
+ * (pow_pool_info) and the value pow_pool_add returned are byte for byte what
+ * pow_index_blocks gives on the concatenation of everything added, in that
+ * order, at the pool's diff_bits.  Every rule of pow_index_blocks above
+ * carries over unchanged: names are computed digests; a POW_V_HASH block is
+ * nobody's parent; of several blocks with one digest the lowest position is
+ * the parent; how previous_block_hash is read; the flags; the fork choice and
+ * its tie rule.  A cycle of names needs a SHA-256 cycle and cannot be built
+ * through this interface; what the pool gives on one is not specified.
+ * How an add runs (N blocks before it, m with it).  The new structs go up and
+ * are audited in pow_verify_chain's tiles of 2^16, as pow_index_blocks does
+ * it.  The new named blocks go into the table; if N + m exceeds half its slots
+ * the table is rebuilt from all N + m blocks with at least 2 (N + m) slots
+ * instead (info: rehashed).  One launch over N + m lanes joins the new blocks
+ * and lets every old block that is an orphan so far (parent POW_POOL_NONE, a
+ * previous_block_hash that can name somebody) look its parent up again;
+ * nothing else about an old block can change, since a new twin has a higher
+ * position and never takes a name over.  ceil(log2 m) rounds rank the new
+ * blocks among themselves; a walk that reaches an old block takes over that
+ * block's depth and n_bad.  The new blocks alone feed the resident fork
+ * choice and flagged count.  The host waits once per tile of the audit, as
+ * pow_index_blocks does, then once for all the rest.  If no old orphan found
+ * its parent (info: adopted == 0, the common case) the add is done.  Otherwise
+ * everything above an adopted orphan is stale, and the whole pool is ranked
+ * again on the device, behind one more bounded wait (info: reranked).  An add
+ * of one block waits twice, three times when it re-ranks.
+ * Cost.  Host work, uploads and downloads of an add are O(m), never O(N):
+ * there is no per-block host loop and no copy of earlier structs.  Launches
+ * (pow_get_stats; hashes = m): ceil(m / 2^16) + 3 + ceil(log2 m), what
+ * pow_index_blocks takes on the m blocks alone, 4 for one block; a re-rank
+ * adds 3 + ceil(log2(N + m)).  The arrays grow by doubling, device to device,
+ * never past POW_POOL_MAX_BLOCKS blocks, which bounds the pool's total.
+ * pow_warmup does not launch this call's kernels.
+ * Device memory: 98 bytes per block of the capacity and 4 per slot, the
+ * context's tile staging buffer (pow_verify_chain's) apart; while an add grows
+ * the arrays or the table, the ones it leaves stand beside the new until it
+ * returns.
+ * Measured (MI355X, profiles/pool_stream/README.md; medians of 9 adds into
+ * shuffled sound pools of N blocks at d = 0, against pow_index_blocks over
+ * the N + 1 blocks and against the reference's way at -O2 on one CPU thread of
+ * the same box, a std::map insert and the sanity_test walk from the new tip):
+ * the add of one block does not grow with N: 98 us at N = 31, 101 us at 200,
+ * 102 us at 4,096, 105 us at 2^16, 106 us at 2^20 - 1 (4 launches, kernels
+ * 39 to 41 us: four launch boundaries), against 0.138, 0.156, 0.220, 0.908
+ * and 12.5 ms for pow_index_blocks.  The add is slower than the reference's
+ * map below a few hundred blocks: 98 us against 18 us at 31 blocks, even at
+ * 200 (101 against 110 us); then 2.4 ms at 4,096, 48 ms at 2^16 and 1.28 s at
+ * 2^20 for the reference, whose walk hashes the whole chain again.  An add
+ * that re-ranks: 0.17 ms at 31 blocks (13 launches), 0.20 ms at 4,096, 0.23 ms
+ * at 2^16, 1.19 ms at 2^20 (27 launches, kernels 1.10 ms).  A run of 5 blocks:
+ * 0.11 ms at every size (7 launches).  Device memory at 2^20 blocks: 111.1 MB.
+ * Walks.  Walking a chain (send_blockchain, log_chain) stays on the host: read
+ * parent and follow it.
+ * Lifetime and threads.  A pool is driven by its context's one thread.
+ * Several pools may live on one context; pow_index_blocks and the verify calls
+ * may be used between adds (they share the tile staging buffer and do not
+ * disturb a pool).  Every pool is closed before pow_destroy: pow_destroy of a
+ * context with open pools frees nothing, keeps the context usable and leaves
+ * its reason in pow_last_error; close the pools and call it again.  A context bound
+ * to a stop board refuses pow_pool_open, _add, _read and _find (POW_EINVAL).
+ *
+ * pow_pool_open: an empty pool at diff_bits.  reserve is a hint: the blocks
+ * the arrays are sized for at once; 0 = 64 blocks.  POW_EINVAL, in this order
+ * before the context is touched: diff_bits > 256; reserve >
+ * POW_POOL_MAX_BLOCKS; a null ctx or out.
+ * pow_pool_add: returns 1 if no block of the whole pool is flagged, 0
+ * otherwise; *info (may be NULL) as pow_pool_get_info.  m = 0 changes nothing.
+ * POW_EINVAL, in this order before the context is touched and with nothing
+ * written or added: a null pool; null blocks with m > 0; an add that would
+ * pass POW_POOL_MAX_BLOCKS.  An add that fails with POW_EHIP leaves the pool
+ * unusable: every later call on it but pow_pool_close returns POW_EHIP at
+ * once, as on a wedged context.
+ * pow_pool_get_info: the pool after its last add; no GPU work.
+ * pow_pool_read: blocks first .. first + count - 1 of the four per-block
+ * results (each may be NULL).  POW_EINVAL: a null pool; a range past size.
+ * pow_pool_find: node_blocks.find (node.cpp:83, 105) for k names of 64
+ * characters each (no NUL between them).  64 characters of 0-9a-f give the
+ * named block of that digest, the lowest position among twins, or
+ * POW_POOL_NONE; anything else gives POW_POOL_NONE, and so does the stored
+ * text of a POW_V_HASH block.  One launch.  POW_EINVAL: a null pool; null names
+ * or pos with k > 0; k > POW_POOL_MAX_BLOCKS. */
+typedef struct pow_pool pow_pool;
+typedef struct pow_pool_info {
+  uint32_t size;        /* blocks held */
+  uint32_t n_flagged;   /* blocks with a non-zero status */
+  uint32_t best;        /* fork choice: a position, POW_POOL_NONE if no block has n_bad == 0 */
+  uint32_t best_index;  /* its index field (0 if none) */
+  uint32_t adopted;     /* last add: earlier blocks that were POW_POOL_NONE and whose parent came with it */
+  uint32_t reranked;    /* last add: 1 if it re-ranked the whole pool */
+  uint32_t rehashed;    /* last add: 1 if it rebuilt the table */
+  uint32_t capacity, slots;
+} pow_pool_info;
+int pow_pool_open(pow_ctx* ctx, unsigned diff_bits, size_t reserve, pow_pool** out);
+void pow_pool_close(pow_pool* p);
+int pow_pool_add(pow_pool* p, const pow_block* blocks, size_t m, pow_pool_info* info /* may be NULL */);
+int pow_pool_get_info(const pow_pool* p, pow_pool_info* info);
+int pow_pool_read(pow_pool* p, size_t first, size_t count, uint8_t* status, uint32_t* parent, uint32_t* depth,
+                  uint32_t* n_bad);
+int pow_pool_find(pow_pool* p, const char* names /* k x 64 */, size_t k, uint32_t* pos /* k */);
+
 /* Mining round: replaces node.cpp:302-308 (nonce -> hash -> test) for every
  * counter in [ctr_start, ctr_start + ctr_count).  The header fields and the
  * 256-byte previous_block_hash are taken from `tmpl` as they are (the caller

@@ -20,6 +20,9 @@ a pool in any order       :func:`index_blocks` and :func:`chain_from` (host stat
                            ``pow_index_blocks``: the block tree of ``node_blocks``, every
                            chain in it audited, and the fork choice:
                            :meth:`mpi_blockchain_amd.miner.GpuMiner.index_blocks`)
+a pool that is fed        :class:`BlockPool` (host statement of ``pow_pool``: the same answers kept
+                           current while blocks arrive:
+                           :meth:`mpi_blockchain_amd.miner.GpuMiner.open_pool`)
 the same, many chains     :func:`verify_chains` and :func:`best_chain` (host statement of
                            ``pow_verify_chains``' verdicts and fork choice:
                            :meth:`mpi_blockchain_amd.miner.GpuMiner.verify_chains`)
@@ -53,7 +56,7 @@ MAX_BLOCKS = 200
 ALPHABET = "abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789"
 
 __all__ = ["Block", "make_block", "block_to_str", "solves_problem", "nonce_from_counter",
-           "gen_random_nonce", "field", "set_field", "verify_chain", "verify_chains", "best_chain", "index_blocks", "chain_from", "POOL_ROOT", "POOL_NONE", "mine_chain", "mine_batch", "V_HASH", "V_WORK", "V_LINK", "V_INDEX", "DEFAULT_DIFFICULTY", "BLOCKS_TO_MINE",
+           "gen_random_nonce", "field", "set_field", "verify_chain", "verify_chains", "best_chain", "index_blocks", "BlockPool", "chain_from", "POOL_ROOT", "POOL_NONE", "mine_chain", "mine_batch", "V_HASH", "V_WORK", "V_LINK", "V_INDEX", "DEFAULT_DIFFICULTY", "BLOCKS_TO_MINE",
            "VALIDATION_MINUTES", "VALIDATION_BLOCKS", "HASH_SIZE", "NONCE_SIZE", "MSG_BYTES"]
 
 
@@ -232,6 +235,106 @@ def index_blocks(pool, difficulty: int = DEFAULT_DIFFICULTY):
         if n_bad[i] == 0 and (best is None or pool[i].index > pool[best].index):
             best = i
     return status, parent, depth, n_bad, best
+
+
+class BlockPool:
+    """A pool that is fed: the host statement of ``pow_pool`` (``pow_pool_open``,
+    ``pow_pool_add``, ``pow_pool_find``), incremental in its own right with a
+    dict of names and a dict of waiting orphans.  After any sequence of
+    :meth:`add` calls ``status``, ``parent``, ``depth``, ``n_bad``, ``best`` and
+    ``ok`` are what :func:`index_blocks` gives on everything added so far, in
+    the order of arrival.  ``adopted`` counts the last add's earlier blocks that
+    were ``POOL_NONE`` and whose parent came with it."""
+
+    def __init__(self, difficulty: int = DEFAULT_DIFFICULTY):
+        if not 0 <= difficulty <= 256:
+            raise ValueError(f"difficulty {difficulty} not in 0..256")
+        self.difficulty = difficulty
+        self.index, self.status, self.parent, self.depth, self.n_bad = [], [], [], [], []
+        self.best, self.adopted, self.n_flagged = None, 0, 0
+        self._names, self._waiting, self._children = {}, {}, {}
+
+    def __len__(self) -> int:
+        return len(self.status)
+
+    @property
+    def ok(self) -> bool:
+        return self.n_flagged == 0
+
+    def results(self):
+        """``(status, parent, depth, n_bad, best)``, as :func:`index_blocks` returns them."""
+        return self.status, self.parent, self.depth, self.n_bad, self.best
+
+    def find(self, name: bytes) -> int:
+        """The named block of that text (the lowest position among twins), or ``POOL_NONE``."""
+        return self._names.get(bytes(name), POOL_NONE)
+
+    def _join(self, i: int, p: int) -> None:
+        """Block i's parent is p: the link and index flags against it."""
+        s = self.status[i] & (V_HASH | V_WORK)
+        if p == POOL_NONE:
+            s |= V_LINK
+        elif p != POOL_ROOT:
+            if (self.index[i] - 1) & 0xFFFFFFFF != self.index[p]:
+                s |= V_INDEX
+            self._children.setdefault(p, []).append(i)
+        self.n_flagged += bool(s) - bool(self.status[i])
+        self.status[i], self.parent[i] = s, p
+
+    def _rank(self, i: int) -> None:
+        """depth and n_bad of block i, of what it stands on if that is open,
+        and of everything that stands on it; a sound block feeds ``best``."""
+        todo = [i]
+        while todo:
+            j = todo.pop()
+            p = self.parent[j]
+            if p < len(self) and self.depth[p] is None:  # a new block under a new block: that one first
+                todo += [j, p]
+                continue
+            d, f = (self.depth[p], self.n_bad[p]) if p < len(self) else (0, 0)
+            self.depth[j], self.n_bad[j] = d + 1, f + bool(self.status[j])
+            if self.n_bad[j] == 0 and (self.best is None or self.index[j] > self.index[self.best]
+                                       or (self.index[j] == self.index[self.best] and j < self.best)):
+                self.best = j
+            todo += [c for c in self._children.get(j, ()) if self.depth[c] != self.depth[j] + 1
+                     or self.n_bad[c] != self.n_bad[j] + bool(self.status[c])]
+
+    def add(self, blocks) -> bool:
+        base, new_names = len(self), []
+        for i, b in enumerate(blocks, base):
+            digest = hashlib.sha256(block_to_str(b)).digest()
+            stored = field(b, "block_hash")
+            flags = 0
+            if stored[:64] != digest.hex().encode() or stored[64] != 0:
+                flags |= V_HASH
+            elif self._names.setdefault(digest.hex().encode(), i) == i:
+                new_names.append(digest.hex().encode())
+            if 256 - int.from_bytes(digest, "big").bit_length() < self.difficulty:
+                flags |= V_WORK
+            self.index.append(b.index)
+            self.status.append(flags)
+            self.n_flagged += bool(flags)
+            self.parent.append(None)
+            self.depth.append(None)
+            self.n_bad.append(None)
+        for i, b in enumerate(blocks, base):
+            prev = _c_string(field(b, "previous_block_hash"))
+            p = POOL_ROOT if prev == b"" else self._names.get(prev, POOL_NONE)
+            if p == POOL_NONE:
+                self._waiting.setdefault(prev, []).append(i)
+            self._join(i, p)
+        old = []
+        for name in new_names:
+            for i in self._waiting.pop(name, ()):  # all of them old: the new blocks were joined with every name in place
+                self._join(i, self._names[name])
+                old.append(i)
+        self.adopted = len(old)
+        for i in range(base, len(self)):
+            if self.depth[i] is None:
+                self._rank(i)
+        for i in old:
+            self._rank(i)
+        return self.ok
 
 
 def chain_from(pool, parent, i: int):

@@ -20,8 +20,8 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libpow_gpu.so")
 # In link order; every library links its sources in this order (the shipped one without TEST_ONLY).
 SOURCES = ["pow_board.cpp", "pow_kernels.hip", "pow_sort.hip", "valu_peak.hip", "pow_api.cpp", "pow_group.cpp", "pow_host.cpp",
-           "pow_verify.hip", "pow_verify_batch.hip", "pow_chain.hip", "pow_batch.hip", "pow_race.hip", "pow_rand.hip", "pow_seed.hip", "pow_pool.hip", "pow_hooks.cpp", "pow_aql.cpp", "pow_test_kernels.hip"]
-HEADERS = ["pow_template.h", "sha256_dev.h", "pow_aql.h", "pow_host.h", "pow_ctx.h", "pow_walk_dev.h", "pow_rand_dev.h", "pow_audit_dev.h"]
+           "pow_verify.hip", "pow_verify_batch.hip", "pow_chain.hip", "pow_batch.hip", "pow_race.hip", "pow_rand.hip", "pow_seed.hip", "pow_pool.hip", "pow_pool_live.hip", "pow_hooks.cpp", "pow_aql.cpp", "pow_test_kernels.hip"]
+HEADERS = ["pow_template.h", "sha256_dev.h", "pow_aql.h", "pow_host.h", "pow_ctx.h", "pow_walk_dev.h", "pow_rand_dev.h", "pow_audit_dev.h", "pow_pool_dev.h"]
 INCLUDES = [os.path.join(ROOT, "include", h) for h in ("pow_gpu.h", "pow_tools.h")]
 ARCH = "gfx950"
 
@@ -43,7 +43,7 @@ def _inputs() -> list[str]:
 # POW_FAULT_INJECT, POW_LAT_MAX, POW_LAT_WPS, POW_GRID_PER_CU, POW_CHAIN_BATCH,
 # POW_CHAIN_FUSED_MAX, POW_CHAIN_LANES_LOG2, POW_BATCH_FUSED_MAX, POW_BATCH_TILE,
 # POW_BATCH_LANES_LOG2, POW_RACE_FUSED_MAX, POW_RACE_BATCH, POW_RACE_LANES_LOG2, POW_RAND_RUN,
-# POW_RAND_LANES_LOG2, POW_RAND_LAUNCH_LOG2, POW_SEED_RUN, POW_SEED_WG, POW_SEED_LAUNCH_LOG2, POW_POOL_SLOTS_LOG2, ...), the RCCL
+# POW_RAND_LANES_LOG2, POW_RAND_LAUNCH_LOG2, POW_SEED_RUN, POW_SEED_WG, POW_SEED_LAUNCH_LOG2, POW_POOL_SLOTS_LOG2, POW_POOL_FIRST_CAP, ...), the RCCL
 # library override (POW_TEST_RCCL_LIB, tests/stub_rccl) and direct AQL
 # dispatch (pow_aql.cpp: round 4's K1'/K2' launch path, opt-in with POW_AQL=1),
 # with the watchdog tests' stall kernel.  The shipped libpow_gpu.so has none of

@@ -414,6 +414,10 @@ int pow_init(int device, pow_ctx** out) {
 
 void pow_destroy(pow_ctx* ctx) {
   if (!ctx) return;
+  if (ctx->open_pools) {  // a pool's calls go through its context: keep it, and say so
+    (void)fail(POW_EINVAL, "pow_destroy: %u pools still open; the context is kept (close them, then destroy)", ctx->open_pools);
+    return;
+  }
   (void)hipSetDevice(ctx->device);
   // A context whose launch has not completed (after a watchdog error) is left
   // allocated rather than freed under a kernel that may still write it.  Each
@@ -767,6 +771,248 @@ int pow_index_blocks(pow_ctx* ctx, const pow_block* pool, size_t n, unsigned dif
   if (ctl->err) return fail(POW_EHIP, "pool table overflow (%zu blocks, %u slots)", n, D.slots);
   if (best && ctl->best) *best = (size_t)(uint32_t)~(uint32_t)ctl->best;
   return ctl->n_flagged == 0 ? 1 : 0;
+}
+
+// ---- pow_pool (K11): K10's arrays and table resident, fed in batches ----
+
+}  // extern "C"
+
+// pow_pool (include/pow_gpu.h): K10's per-block arrays and its table, resident.
+// Driven by its context's thread; its buffers are its own (pow_pool_close frees
+// them through release_buffers, which has to name every holder), the tile
+// staging buffer is the context's.
+struct pow_pool {
+  pow_ctx* ctx = nullptr;
+  unsigned diff = 0;
+  uint32_t size = 0;           // blocks held
+  uint32_t slots = 0;          // of the table
+  uint32_t fin = 0;            // which of depth[], bad[] hold the final values
+  bool dead = false;           // an add failed half way: every later call is POW_EHIP
+  PowPoolLivePlan plan{};      // the arrays' offsets at the present capacity
+  DevBuf<uint32_t> d_arr;      // the arrays (plan.words)
+  DevBuf<uint32_t> d_table;    // the table (slots)
+  DevBuf<uint32_t> d_old_arr, d_old_table;  // what an add that grew them left behind, until its wait has passed
+  DevBuf<uint32_t> d_find;     // pow_pool_find: 16 words per name up, then one per name down
+  HostBuf<PowPoolLiveCtl> h_ctl;  // the pinned twin of the control words
+  pow_pool_info info{};
+  void release_buffers() {
+    d_arr.release(), d_table.release(), d_old_arr.release(), d_old_table.release(), d_find.release(), h_ctl.release();
+  }
+};
+
+extern "C" {
+
+// What every pool call that reaches the GPU opens with, behind its argument
+// checks: a pool whose add failed, or whose context is wedged, fails at once.
+static int pool_ready(const pow_pool* p, const char* what) {
+  if (p->dead || p->ctx->wedged) return fail(POW_EHIP, "%s: the pool is unusable after a failed call", what);
+  if (p->ctx->board) return fail(POW_EINVAL, "%s does not run on a context bound to a stop board", what);
+  return set_dev(p->ctx);
+}
+
+static PowPoolDev pool_dev(const pow_pool* p, uint32_t n) {
+  return pow_pool_live_dev(p->d_arr.p, p->plan, p->d_table.p, n, p->slots);
+}
+
+static void pool_fill_info(pow_pool* p, const PowPoolLiveCtl& ctl, uint32_t adopted, bool reranked, bool rehashed) {
+  const uint32_t best = ctl.k10.best ? (uint32_t)~(uint32_t)ctl.k10.best : POW_POOL_NONE;
+  p->info = pow_pool_info{p->size, ctl.k10.n_flagged, best, ctl.k10.best ? (uint32_t)(ctl.k10.best >> 32) : 0u,
+                          adopted, reranked ? 1u : 0u, rehashed ? 1u : 0u, p->plan.cap, p->slots};
+}
+
+// The pool's first buffers, their reset and one bounded wait.
+static int pool_alloc(pow_pool* p, uint32_t cap, uint32_t slots) {
+  pow_ctx* const ctx = p->ctx;
+  p->plan = pow_pool_live_plan(cap);
+  p->slots = slots;
+  RESERVE(p->d_arr, p->plan.words);
+  RESERVE(p->d_table, slots);
+  RESERVE(p->h_ctl, 1);
+  HIP_OK(hipMemsetAsync(p->d_arr.p + p->plan.ctl, 0, sizeof(PowPoolLiveCtl), ctx->stream));
+  HIP_OK(hipMemsetAsync(p->d_table.p, 0xFF, (size_t)slots * sizeof(uint32_t), ctx->stream));
+  return stream_wait_for(ctx, "pool reset", 0);
+}
+
+// Room for `need` blocks: arrays of twice the capacity (pow_pool_live_grow),
+// filled device to device with what the pool's blocks have.  The arrays left
+// behind stay allocated until the add's wait has passed (d_old_arr).
+static int pool_grow(pow_pool* p, uint32_t need) {
+  pow_ctx* const ctx = p->ctx;
+  const PowPoolLivePlan from = p->plan, to = pow_pool_live_plan(pow_pool_live_grow(from.cap, need));
+  p->d_old_arr = p->d_arr;
+  p->d_arr = DevBuf<uint32_t>{};
+  RESERVE(p->d_arr, to.words);
+  const uint32_t* const src = p->d_old_arr.p;
+  uint32_t* const dst = p->d_arr.p;
+  const size_t n = p->size, bytes = (n + 3) / 4;
+  const struct { uint32_t from, to; size_t words; } arrays[] = {
+      {from.ctl, to.ctl, POW_POOL_LIVE_CTL_WORDS}, {from.dig, to.dig, 8 * n}, {from.prev, to.prev, 8 * n},
+      {from.index, to.index, n}, {from.parent, to.parent, n}, {from.depth[p->fin], to.depth[p->fin], n},
+      {from.bad[p->fin], to.bad[p->fin], n}, {from.status, to.status, bytes}, {from.kind, to.kind, bytes}};
+  for (const auto& a : arrays)
+    if (a.words)
+      HIP_OK(hipMemcpyAsync(dst + a.to, src + a.from, a.words * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+  p->plan = to;
+  return POW_OK;
+}
+
+int pow_pool_open(pow_ctx* ctx, unsigned diff_bits, size_t reserve, pow_pool** out) {
+  if (diff_bits > 256) return fail(POW_EINVAL, "diff_bits %u > 256", diff_bits);
+  if (reserve > POW_POOL_MAX_BLOCKS)
+    return fail(POW_EINVAL, "reserve too large (%zu blocks > %u)", reserve, POW_POOL_MAX_BLOCKS);
+  if (!ctx || !out) return fail(POW_EINVAL, "null");
+  if (ctx->wedged) return fail(POW_EHIP, "pow_pool_open: the context must not be reused");
+  if (ctx->board) return fail(POW_EINVAL, "pow_pool_open does not run on a context bound to a stop board");
+  if (int rc = set_dev(ctx)) return rc;
+  pow_pool* const p = new pow_pool;
+  p->ctx = ctx;
+  p->diff = diff_bits;
+  const uint32_t cap = pow_pool_live_first_cap(reserve, ctx->pool_first_cap);
+  if (int rc = pool_alloc(p, cap, pow_pool_live_first_slots(cap, ctx->pool_slots_log2))) {
+    if (!ctx->wedged) p->release_buffers();
+    delete p;
+    return rc;
+  }
+  pool_fill_info(p, PowPoolLiveCtl{}, 0, false, false);
+  ++ctx->open_pools;
+  *out = p;
+  return POW_OK;
+}
+
+void pow_pool_close(pow_pool* p) {
+  if (!p) return;
+  pow_ctx* const ctx = p->ctx;
+  (void)hipSetDevice(ctx->device);
+  // As pow_destroy: what a kernel of a wedged context may still write stays allocated.
+  if (!ctx->wedged) p->release_buffers();
+  --ctx->open_pools;
+  delete p;
+}
+
+// K10a over the new structs tile by tile at the pool's end, then one timed
+// section: the table (K11b, or a reset and K10b over everything when it has to
+// grow), K11c, the rounds of K11d and K11e, and the control words down.  Only
+// if an old orphan's parent came with the batch, a second one: K11s, the
+// control words' reset and K10c to K10e over the whole pool.
+int pow_pool_add(pow_pool* p, const pow_block* blocks, size_t m, pow_pool_info* info) {
+  if (!p) return fail(POW_EINVAL, "null pool");
+  if (!blocks && m) return fail(POW_EINVAL, "null blocks");
+  if (m > POW_POOL_MAX_BLOCKS - p->size)
+    return fail(POW_EINVAL, "pool too large (%u + %zu blocks > %u)", p->size, m, POW_POOL_MAX_BLOCKS);
+  if (int rc = pool_ready(p, "pow_pool_add")) return rc;
+  pow_ctx* const ctx = p->ctx;
+  ctx->stats = pow_stats{};
+  if (m == 0) {
+    if (info) *info = p->info;
+    return p->info.n_flagged == 0 ? 1 : 0;
+  }
+  p->dead = true;  // until the add has gone through
+  const uint32_t base = p->size, n = base + (uint32_t)m;
+  if (int rc = ensure_verify_tile(ctx, std::min(m, kVerifyTile))) return rc;
+  if (n > p->plan.cap)
+    if (int rc = pool_grow(p, n)) return rc;
+  const uint32_t slots = pow_pool_live_slots(p->slots, n);
+  const bool rehashed = slots != p->slots;
+  if (slots > p->d_table.cap) {
+    p->d_old_table = p->d_table;
+    p->d_table = DevBuf<uint32_t>{};
+    RESERVE(p->d_table, slots);
+  }
+  p->slots = slots;
+  const PowPoolDev D = pool_dev(p, n);
+  if (int rc = verify_tiles(
+          ctx, blocks, m, "pool audit kernel", [](const VerifyTile&) -> int { return POW_OK; },
+          [&](const VerifyTile& t) -> int {
+            HIP_OK(pow_launch_pool_audit(ctx->stream, (const uint32_t*)ctx->d_vblk.p, (uint32_t)t.tn,
+                                         base + (uint32_t)t.t0, p->diff, D));
+            HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+            return POW_OK;
+          },
+          [](const VerifyTile&) {}))
+    return rc;
+  PowPoolLiveCtl* const d_ctl = (PowPoolLiveCtl*)D.ctl;
+  PowPoolLiveCtl* const ctl = p->h_ctl.p;
+  const uint32_t rounds = pow_pool_rounds((uint32_t)m);
+  if (int rc = timed_begin(ctx)) return rc;
+  HIP_OK(hipMemsetAsync(&d_ctl->adopted, 0, 2 * sizeof(uint32_t), ctx->stream));
+  if (rehashed) {
+    HIP_OK(hipMemsetAsync(D.table, 0xFF, (size_t)D.slots * sizeof(uint32_t), ctx->stream));
+    HIP_OK(pow_launch_pool_insert(ctx->stream, D));  // K10b: every named block of the pool
+  } else {
+    HIP_OK(pow_launch_pool_live_insert(ctx->stream, D, base));
+  }
+  HIP_OK(pow_launch_pool_live_join(ctx->stream, D, base));
+  for (uint32_t r = 0; r < rounds; ++r) HIP_OK(pow_launch_pool_live_round(ctx->stream, D, base, r));
+  HIP_OK(pow_launch_pool_live_finish(ctx->stream, D, base, rounds & 1u, p->fin));
+  HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+  HIP_OK(hipMemcpyAsync(ctl, d_ctl, sizeof(PowPoolLiveCtl), hipMemcpyDeviceToHost, ctx->stream));
+  // + 100 ns per block and launch that runs over the whole pool or the batch
+  if (int rc = timed_end(ctx, "pool add kernels", 100ull * (n + m * (rounds + 2ull)), 3u + rounds, &ctx->stats))
+    return rc;
+  if (ctl->k10.err) return fail(POW_EHIP, "pool table overflow (%u blocks, %u slots)", n, D.slots);
+  const uint32_t adopted = ctl->adopted;
+  if (adopted) {  // the subtree over every adopted orphan is stale: rank the whole pool again, on the device
+    const uint32_t all = pow_pool_rounds(n);
+    if (int rc = timed_begin(ctx)) return rc;
+    HIP_OK(pow_launch_pool_live_strip(ctx->stream, D));
+    HIP_OK(hipMemsetAsync(d_ctl, 0, sizeof(PowPoolLiveCtl), ctx->stream));
+    HIP_OK(pow_launch_pool_join(ctx->stream, D));
+    for (uint32_t r = 0; r < all; ++r) HIP_OK(pow_launch_pool_round(ctx->stream, D, r));
+    HIP_OK(pow_launch_pool_finish(ctx->stream, D, all & 1u));
+    HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_OK(hipMemcpyAsync(ctl, d_ctl, sizeof(PowPoolLiveCtl), hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = timed_end(ctx, "pool re-rank kernels", 100ull * n * (all + 3ull), 3u + all, &ctx->stats)) return rc;
+    p->fin = all & 1u;
+  }
+  p->d_old_arr.release(), p->d_old_table.release();  // the waits have passed: nothing reads them
+  p->size = n;
+  pool_fill_info(p, *ctl, adopted, adopted != 0, rehashed);
+  p->dead = false;
+  if (info) *info = p->info;
+  return p->info.n_flagged == 0 ? 1 : 0;
+}
+
+int pow_pool_get_info(const pow_pool* p, pow_pool_info* info) {
+  if (!p || !info) return fail(POW_EINVAL, "null");
+  if (p->dead || p->ctx->wedged) return fail(POW_EHIP, "pow_pool_get_info: the pool is unusable after a failed call");
+  *info = p->info;
+  return POW_OK;
+}
+
+int pow_pool_read(pow_pool* p, size_t first, size_t count, uint8_t* status, uint32_t* parent, uint32_t* depth,
+                  uint32_t* n_bad) {
+  if (!p) return fail(POW_EINVAL, "null pool");
+  if (first > p->size || count > p->size - first)
+    return fail(POW_EINVAL, "blocks %zu + %zu past the pool's %u", first, count, p->size);
+  if (int rc = pool_ready(p, "pow_pool_read")) return rc;
+  pow_ctx* const ctx = p->ctx;
+  if (count == 0 || !(status || parent || depth || n_bad)) return POW_OK;
+  const PowPoolDev D = pool_dev(p, p->size);
+  const size_t words = count * sizeof(uint32_t);
+  if (status) HIP_OK(hipMemcpyAsync(status, D.status + first, count, hipMemcpyDeviceToHost, ctx->stream));
+  if (parent) HIP_OK(hipMemcpyAsync(parent, D.parent + first, words, hipMemcpyDeviceToHost, ctx->stream));
+  if (depth) HIP_OK(hipMemcpyAsync(depth, D.depth[p->fin] + first, words, hipMemcpyDeviceToHost, ctx->stream));
+  if (n_bad) HIP_OK(hipMemcpyAsync(n_bad, D.bad[p->fin] + first, words, hipMemcpyDeviceToHost, ctx->stream));
+  return stream_wait_for(ctx, "pool read", 100ull * count);
+}
+
+int pow_pool_find(pow_pool* p, const char* names, size_t k, uint32_t* pos) {
+  if (!p) return fail(POW_EINVAL, "null pool");
+  if ((!names || !pos) && k) return fail(POW_EINVAL, "null");
+  if (k > POW_POOL_MAX_BLOCKS) return fail(POW_EINVAL, "too many names (%zu > %u)", k, POW_POOL_MAX_BLOCKS);
+  if (int rc = pool_ready(p, "pow_pool_find")) return rc;
+  pow_ctx* const ctx = p->ctx;
+  ctx->stats = pow_stats{};
+  if (k == 0) return POW_OK;
+  RESERVE(p->d_find, 17 * k);
+  uint32_t* const d_names = p->d_find.p;
+  uint32_t* const d_pos = p->d_find.p + 16 * k;
+  HIP_OK(hipMemcpyAsync(d_names, names, 64 * k, hipMemcpyHostToDevice, ctx->stream));
+  if (int rc = timed_begin(ctx)) return rc;
+  HIP_OK(pow_launch_pool_live_find(ctx->stream, pool_dev(p, p->size), d_names, (uint32_t)k, d_pos));
+  HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+  HIP_OK(hipMemcpyAsync(pos, d_pos, k * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  return timed_end(ctx, "pool find kernel", 100ull * k, 1u, &ctx->stats);
 }
 
 int pow_sweep_device(pow_ctx* ctx, const pow_block* tmpl, uint64_t ctr_start, uint64_t ctr_count,

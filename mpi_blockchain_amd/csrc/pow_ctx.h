@@ -281,6 +281,27 @@ inline PowPoolDev pow_pool_dev(uint32_t* base, const PowPoolPlan& p, uint32_t n)
                     base + p.table, n, p.slots};
 }
 
+// K11 (pow_pool_live.hip), the kernels of pow_pool_add and pow_pool_find.  The
+// pool's control words stay on the device from add to add: K10's first (K10b
+// and K10e take them as they are), then the orphans of the last add whose
+// parent came with it, which the host resets before every add.
+struct PowPoolLiveCtl {
+  PowPoolCtl k10;        // err; n_flagged and best over the whole pool, fed by every add
+  unsigned int adopted;  // K11c: old blocks that were POW_POOL_NONE and have a parent now (atomic add)
+  unsigned int pad;
+};
+static_assert(sizeof(PowPoolLiveCtl) == 4 * POW_POOL_LIVE_CTL_WORDS && offsetof(PowPoolLiveCtl, k10) == 0,
+              "the plan's control words; K10's launchers take the head");
+// A pool's arrays at its capacity's offsets (pow_pool_live_plan) with its
+// table, which is an allocation of its own; n = the blocks it holds.
+inline PowPoolDev pow_pool_live_dev(uint32_t* base, const PowPoolLivePlan& p, uint32_t* table, uint32_t n,
+                                    uint32_t slots) {
+  return PowPoolDev{(PowPoolCtl*)(base + p.ctl), base + p.dig, base + p.prev, base + p.index, base + p.parent,
+                    {base + p.next[0], base + p.next[1]}, {base + p.depth[0], base + p.depth[1]},
+                    {base + p.bad[0], base + p.bad[1]}, (uint8_t*)(base + p.status), (uint8_t*)(base + p.kind),
+                    table, n, slots};
+}
+
 struct pow_ctx {
   int device = 0;
   int cu_count = 0;
@@ -391,7 +412,10 @@ struct pow_ctx {
   unsigned seed_run = 0;          // pow_find_seed: K9's run T (0 = the plan)
   unsigned seed_wg = 0;           // K9's workgroups per seed (0 = the plan)
   unsigned seed_launch_log2 = POW_SEED_LAUNCH_LOG2;  // (seed, trial) pairs per K9 launch = 2^this
-  unsigned pool_slots_log2 = 0;   // pow_index_blocks: the table's slots = 2^this, at least n + 1 (0 = the plan)
+  unsigned pool_slots_log2 = 0;   // pow_index_blocks: the table's slots = 2^this, at least n + 1 (0 = the plan);
+                                  // pow_pool_open: the pool's first table
+  unsigned pool_first_cap = 0;    // pow_pool_open with reserve 0: the first capacity in blocks (0 = the plan)
+  unsigned open_pools = 0;        // pow_pool handles not yet closed: pow_destroy keeps the context while there are any
   // K1' and K2' launches as AQL packets (pow_aql.cpp) instead of
   // hipLaunchKernel: test library only, opt-in there; null = the HIP launch
   // path, the only one the shipped library has.
@@ -435,6 +459,14 @@ hipError_t pow_launch_pool_insert(hipStream_t stream, const PowPoolDev& D);
 hipError_t pow_launch_pool_join(hipStream_t stream, const PowPoolDev& D);
 hipError_t pow_launch_pool_round(hipStream_t stream, const PowPoolDev& D, uint32_t r);
 hipError_t pow_launch_pool_finish(hipStream_t stream, const PowPoolDev& D, uint32_t which);
+hipError_t pow_launch_pool_live_insert(hipStream_t stream, const PowPoolDev& D, uint32_t base);
+hipError_t pow_launch_pool_live_join(hipStream_t stream, const PowPoolDev& D, uint32_t base);
+hipError_t pow_launch_pool_live_round(hipStream_t stream, const PowPoolDev& D, uint32_t base, uint32_t from);
+hipError_t pow_launch_pool_live_finish(hipStream_t stream, const PowPoolDev& D, uint32_t base, uint32_t which,
+                                       uint32_t fin);
+hipError_t pow_launch_pool_live_strip(hipStream_t stream, const PowPoolDev& D);
+hipError_t pow_launch_pool_live_find(hipStream_t stream, const PowPoolDev& D, const uint32_t* names, uint32_t k,
+                                     uint32_t* pos);
 hipError_t pow_sort_u32(void* temp, size_t* temp_bytes, uint32_t* keys, uint32_t* alt, uint32_t n,
                         uint32_t** sorted, hipStream_t stream);
 hipError_t pow_launch_search_lat(bool full, bool any, bool asm_groups, unsigned grid, hipStream_t stream,

@@ -59,6 +59,9 @@ void configure(pow_ctx* ctx) {
   if (const char* sn = getenv("POW_SEED_LAUNCH_LOG2")) ctx->seed_launch_log2 = (unsigned)std::min((unsigned long)POW_SEED_LAUNCH_LOG2, strtoul(sn, nullptr, 0));
   // pow_index_blocks: the table's slots (2^n, never below the pool's blocks + 1); the result must not depend on it
   if (const char* ps = getenv("POW_POOL_SLOTS_LOG2")) ctx->pool_slots_log2 = (unsigned)std::min(21ul, strtoul(ps, nullptr, 0));
+  // pow_pool_open: that switch also gives a pool's first table (2^n slots; every add keeps at least two slots per
+  // block), and this one its first capacity in blocks when reserve is 0; the results must not depend on either
+  if (const char* pc = getenv("POW_POOL_FIRST_CAP")) ctx->pool_first_cap = (unsigned)std::min((unsigned long)POW_POOL_MAX_BLOCKS, strtoul(pc, nullptr, 0));
   if (const char* g = getenv("POW_GRID_PER_CU")) {  // launch-geometry experiments
     const int per = atoi(g);
     if (per > 0 && per <= 64) ctx->grid_full = (unsigned)ctx->cu_count * (unsigned)per;

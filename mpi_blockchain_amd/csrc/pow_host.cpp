@@ -463,8 +463,7 @@ PowPoolPlan pow_pool_plan(uint32_t n, unsigned slots_log2) {
   while (slots < 2ull * n) slots *= 2;
   if (slots_log2) slots = std::max(least, 1u << std::min(slots_log2, 21u));
   p.slots = slots;
-  p.rounds = 0;
-  while ((1ull << p.rounds) < n) ++p.rounds;
+  p.rounds = pow_pool_rounds(n);
   const uint32_t bytes = (n + 3u) / 4u;  // n bytes in whole words
   uint32_t at = 0;
   auto take = [&](uint32_t words) {
@@ -485,6 +484,64 @@ PowPoolPlan pow_pool_plan(uint32_t n, unsigned slots_log2) {
   p.table = take(slots);
   p.words = at;
   return p;
+}
+
+PowPoolLivePlan pow_pool_live_plan(uint32_t cap) {
+  PowPoolLivePlan p;
+  p.cap = cap;
+  const uint32_t bytes = (cap + 3u) / 4u;  // cap bytes in whole words
+  uint32_t at = 0;
+  auto take = [&](uint32_t words) {
+    const uint32_t here = at;
+    at += words;
+    return here;
+  };
+  p.ctl = take(8);  // POW_POOL_LIVE_CTL_WORDS, and dig stays on 16 bytes
+  p.dig = take(8u * cap);
+  p.prev = take(8u * cap);
+  p.index = take(cap);
+  p.parent = take(cap);
+  for (int k = 0; k < 2; ++k) p.next[k] = take(cap);
+  for (int k = 0; k < 2; ++k) p.depth[k] = take(cap);
+  for (int k = 0; k < 2; ++k) p.bad[k] = take(cap);
+  p.status = take(bytes);
+  p.kind = take(bytes);
+  p.words = at;
+  return p;
+}
+
+uint32_t pow_pool_live_first_cap(size_t reserve, unsigned first_cap) {
+  const size_t want = reserve ? reserve : first_cap ? first_cap : POW_POOL_LIVE_FIRST_CAP;
+  return (uint32_t)std::min<size_t>(want, POW_POOL_MAX_BLOCKS);
+}
+
+uint32_t pow_pool_live_grow(uint32_t cap, uint32_t need) {
+  uint64_t c = std::max(1u, cap);
+  while (c < need) c *= 2;
+  return (uint32_t)std::min<uint64_t>(c, POW_POOL_MAX_BLOCKS);
+}
+
+uint32_t pow_pool_live_first_slots(uint32_t cap, unsigned slots_log2) {
+  if (slots_log2) return 1u << std::min(slots_log2, 21u);
+  return pow_pool_live_slots(2, cap);
+}
+
+uint32_t pow_pool_live_slots(uint32_t slots, uint32_t size) {
+  if (size <= slots / 2u) return slots;
+  uint32_t s = 2;
+  while (s < 2ull * size) s *= 2;
+  return s;
+}
+
+uint32_t pow_pool_rounds(uint32_t n) {
+  uint32_t r = 0;
+  while ((1ull << r) < n) ++r;
+  return r;
+}
+
+uint32_t pow_pool_live_launches(uint32_t m, uint32_t size, bool rerank) {
+  const uint32_t tiles = (m + (1u << 16) - 1u) >> 16;
+  return tiles + 3u + pow_pool_rounds(m) + (rerank ? 3u + pow_pool_rounds(size) : 0u);
 }
 
 extern "C" {

@@ -192,4 +192,42 @@ struct PowPoolPlan {
 };
 PowPoolPlan pow_pool_plan(uint32_t n, unsigned slots_log2);
 
+// ---- pow_pool (K11): the pool that stays on the device ----
+// The plan of a pool's arrays at a capacity of cap blocks (1..
+// POW_POOL_MAX_BLOCKS): K10's arrays at cap entries each, in 32-bit words from
+// the start of the pool's buffer; the table is an allocation of its own.  Pure.
+// It holds that no two arrays overlap, dig and prev lie on 16 bytes, ctl on 8,
+// status and kind on whole words, and words holds them all: 8 + 24 cap +
+// 2 ceil(cap / 4), that is 98 bytes per block as pow_index_blocks has them.
+#define POW_POOL_LIVE_CTL_WORDS 6u   // PowPoolLiveCtl (pow_ctx.h); the plan rounds them up to 8
+#define POW_POOL_LIVE_FIRST_CAP 64u  // pow_pool_open with reserve 0: 1,024 blocks take four doublings
+struct PowPoolLivePlan {
+  uint32_t cap;       // blocks the arrays hold
+  uint32_t ctl;       // PowPoolLiveCtl
+  uint32_t dig, prev, index, parent, next[2], depth[2], bad[2];  // as PowPoolPlan's, cap entries each
+  uint32_t status, kind;  // cap bytes each
+  uint64_t words;
+};
+PowPoolLivePlan pow_pool_live_plan(uint32_t cap);
+// The first capacity: reserve, or with reserve 0 POW_POOL_LIVE_FIRST_CAP
+// (first_cap: the test library's override of that, 0 = none); 1..POW_POOL_MAX_BLOCKS.
+uint32_t pow_pool_live_first_cap(size_t reserve, unsigned first_cap);
+// The capacity for `need` blocks (cap < need <= POW_POOL_MAX_BLOCKS): cap
+// doubled until it holds them, never past POW_POOL_MAX_BLOCKS.
+uint32_t pow_pool_live_grow(uint32_t cap, uint32_t need);
+// The first table: the lowest power of two that is at least 2 cap, or the test
+// library's 2^slots_log2 (2..2^21; 0 = none).
+uint32_t pow_pool_live_first_slots(uint32_t cap, unsigned slots_log2);
+// The table for `size` blocks after an add: `slots` if size <= slots / 2,
+// otherwise (a rebuild) the lowest power of two that is at least 2 size.  So
+// slots >= 2 size after every add, and a probe always meets an empty slot.
+uint32_t pow_pool_live_slots(uint32_t slots, uint32_t size);
+// ceil(log2 n), 0 for n <= 1: the rounds that end every walk of n blocks; pow_pool_plan's rounds.
+uint32_t pow_pool_rounds(uint32_t n);
+// The kernel launches of an add of m blocks (m >= 1) that leaves `size` blocks:
+// one K10a per host tile of 2^16, the insert (K11b, or K10b on a rebuild), K11c,
+// ceil(log2 m) rounds of K11d and K11e: what pow_index_blocks takes on the m
+// blocks alone.  A re-rank adds K11s, K10c, ceil(log2 size) rounds of K10d and K10e.
+uint32_t pow_pool_live_launches(uint32_t m, uint32_t size, bool rerank);
+
 #pragma GCC visibility pop

@@ -8,11 +8,13 @@ from __future__ import annotations
 
 import ctypes
 import time
+import weakref
 from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import HASH_SIZE, NONCE_SIZE, SEED_MAX_SEEDS, SEED_MAX_TARGETS, Block, PowStats, SeedMatchRec, check, load
+from ._lib import (HASH_SIZE, NONCE_SIZE, POOL_NONE, SEED_MAX_SEEDS, SEED_MAX_TARGETS, Block, PoolInfo, PowStats,
+                   SeedMatchRec, check, load)
 from .block import DEFAULT_DIFFICULTY, field, nonce_from_counter
 
 
@@ -140,6 +142,83 @@ def refresh_template(last: Block, rank: int, difficulty: int = DEFAULT_DIFFICULT
     return b
 
 
+class GpuPool:
+    """A ``pow_pool`` of a :class:`GpuMiner` (:meth:`GpuMiner.open_pool`): the
+    block tree of everything added so far, kept on the GPU.  A context manager;
+    driven by the miner's thread."""
+
+    def __init__(self, miner: "GpuMiner", difficulty: int, reserve: int = 0):
+        self.miner, self.L = miner, miner.L
+        self.handle = ctypes.c_void_p()
+        check(self.L.pow_pool_open(miner.ctx, difficulty, reserve, ctypes.byref(self.handle)), self.L)
+        miner._pools.add(self)  # the miner closes what is still open before its context goes
+
+    def close(self) -> None:
+        if self.handle:
+            self.L.pow_pool_close(self.handle)
+            self.handle = ctypes.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __len__(self) -> int:
+        return self.info()["size"]
+
+    @staticmethod
+    def _info(raw: PoolInfo) -> dict:
+        d = {name: getattr(raw, name) for name, _ in PoolInfo._fields_}
+        d["best"] = None if raw.best == POOL_NONE else raw.best
+        return d
+
+    def add(self, blocks) -> dict:
+        """pow_pool_add: a list of Blocks or a ctypes ``Block * m`` array.
+        Returns the pool's info after the add, with ``ok``: no block of the
+        whole pool is flagged."""
+        m = len(blocks)
+        arr = blocks if isinstance(blocks, ctypes.Array) else (Block * max(m, 1))(*blocks)
+        raw = PoolInfo()
+        rc = check(self.L.pow_pool_add(self.handle, arr, m, ctypes.byref(raw)), self.L)
+        return {**self._info(raw), "ok": rc == 1}
+
+    def info(self) -> dict:
+        raw = PoolInfo()
+        check(self.L.pow_pool_get_info(self.handle, ctypes.byref(raw)), self.L)
+        return self._info(raw)
+
+    def read(self, first: int = 0, count: int | None = None) -> IndexBlocksResult:
+        """pow_pool_read: the four per-block results of `count` blocks from
+        `first` (all of them by default), with the pool's ``best`` and ``ok``."""
+        info = self.info()
+        n = info["size"] - first if count is None else count
+        status = np.zeros(max(n, 0), dtype=np.uint8)
+        parent, depth, bad = (np.zeros(max(n, 0), dtype=np.uint32) for _ in range(3))
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        check(self.L.pow_pool_read(self.handle, first, n, status.ctypes.data_as(ctypes.c_void_p),
+                                   parent.ctypes.data_as(u32p), depth.ctypes.data_as(u32p),
+                                   bad.ctypes.data_as(u32p)), self.L)
+        return IndexBlocksResult(info["n_flagged"] == 0, info["best"], status, parent, depth, bad)
+
+    def find(self, names) -> list[int]:
+        """pow_pool_find: per name (64 bytes each) the named block's position
+        or ``block.POOL_NONE``."""
+        names = [bytes(x) for x in names]
+        if any(len(x) != 64 for x in names):
+            raise ValueError("a name is 64 characters")
+        k = len(names)
+        pos = (ctypes.c_uint32 * max(k, 1))()
+        check(self.L.pow_pool_find(self.handle, b"".join(names), k, pos), self.L)
+        return list(pos)[:k]
+
+
 class GpuMiner:
     def __init__(self, device: int = 0, test_hooks: bool = False):
         """test_hooks=True: a context of libpow_gpu_test.so, which reads the
@@ -150,6 +229,7 @@ class GpuMiner:
         check(self.L.pow_init(device, ctypes.byref(self.ctx)), self.L)
         self.device = device
         self._cancel = ctypes.c_uint32(0)
+        self._pools = weakref.WeakSet()  # open GpuPools: pow_destroy keeps a context that has any
 
     def warmup(self) -> None:
         """Load every kernel now (HIP loads code objects at first launch)."""
@@ -158,6 +238,8 @@ class GpuMiner:
     # ---- lifecycle ----
     def close(self) -> None:
         if self.ctx:
+            for pool in list(self._pools):
+                pool.close()
             self.L.pow_destroy(self.ctx)
             self.ctx = ctypes.c_void_p()
 
@@ -234,6 +316,12 @@ class GpuMiner:
                                            bad.ctypes.data_as(u32p), ctypes.byref(best)), self.L)
         return IndexBlocksResult(rc == 1, None if best.value == ctypes.c_size_t(-1).value else best.value,
                                  status, parent, depth, bad)
+
+    def open_pool(self, difficulty: int = DEFAULT_DIFFICULTY, reserve: int = 0) -> "GpuPool":
+        """pow_pool_open: an empty pool that stays on the GPU and is fed in
+        batches (:class:`GpuPool`; close it before the miner).  The host
+        statement is :class:`mpi_blockchain_amd.block.BlockPool`."""
+        return GpuPool(self, difficulty, reserve)
 
     # ---- chain audit (check_first + check_chain + solves_problem for every block) ----
     def verify_chain(self, blocks, difficulty: int = DEFAULT_DIFFICULTY) -> VerifyResult:

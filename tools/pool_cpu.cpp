@@ -168,6 +168,52 @@ size_t pool_ref_audit(const pow_block* pool, size_t n, unsigned diff, size_t* n_
   return sound;
 }
 
+// ---- tools/pool_add_bench.py: a pool that is fed ----
+
+// m blocks in a chain on `parent` (owner tells them from the pool's own).
+void pool_extend(const pow_block* parent, pow_block* out, size_t m, uint32_t owner) {
+  for (size_t k = 0; k < m; ++k) seal_child(out[k], k ? &out[k - 1] : parent, parent->index + 1 + (uint32_t)k, owner);
+}
+
+// The reference's node_blocks, kept between arrivals.
+void* pool_ref_new(const pow_block* pool, size_t n) {
+  auto* blocks = new std::map<std::string, pow_block>;
+  for (size_t i = 0; i < n; ++i) blocks->insert({text(pool[i].block_hash), pool[i]});
+  return blocks;
+}
+
+void pool_ref_free(void* handle) { delete (std::map<std::string, pow_block>*)handle; }
+
+// What an arrival costs the reference, in our words: the m blocks into
+// node_blocks (node.cpp:199, 319), then the sanity_test walk from the last of
+// them (node.cpp:100-148) with block_to_hash, the work test, the link and the
+// index per block.  Returns 1 if the walk is sound down to a root; *blocks_walked
+// counts it.  The blocks are taken out again behind the caller's clock
+// (pool_ref_drop), so that every repetition meets the same pool.
+int pool_ref_add(void* handle, const pow_block* add, size_t m, unsigned diff, uint64_t* blocks_walked) {
+  auto& node_blocks = *(std::map<std::string, pow_block>*)handle;
+  for (size_t i = 0; i < m; ++i) node_blocks.insert({text(add[i].block_hash), add[i]});
+  const pow_block* cur = &node_blocks.find(text(add[m - 1].block_hash))->second;
+  uint64_t count = 0;
+  bool ok = true;
+  while (ok) {
+    char hex[65];
+    ++count;
+    ok = block_to_hash(*cur, hex) >= diff && text(cur->block_hash) == hex;
+    if (!ok || cur->previous_block_hash[0] == 0) break;
+    const auto it = node_blocks.find(text(cur->previous_block_hash));
+    ok = it != node_blocks.end() && cur->index - 1u == it->second.index;
+    if (ok) cur = &it->second;
+  }
+  *blocks_walked = count;
+  return ok ? 1 : 0;
+}
+
+void pool_ref_drop(void* handle, const pow_block* add, size_t m) {
+  auto& node_blocks = *(std::map<std::string, pow_block>*)handle;
+  for (size_t i = 0; i < m; ++i) node_blocks.erase(text(add[i].block_hash));
+}
+
 // Returns the blocks written (at most cap; more were needed if it returns cap + 1).
 size_t pool_extract(const pow_block* pool, size_t n, pow_block* out, size_t cap, uint32_t* lengths, size_t* n_chains) {
   std::map<std::string, pow_block> blocks;
