@@ -364,7 +364,8 @@ int pow_index_blocks(pow_ctx* ctx, const pow_block* pool, size_t n, unsigned dif
  * (pow_get_stats; hashes = m): ceil(m / 2^16) + 3 + ceil(log2 m), what
  * pow_index_blocks takes on the m blocks alone, 4 for one block; a re-rank
  * adds 3 + ceil(log2(N + m)).  The arrays grow by doubling, device to device,
- * never past POW_POOL_MAX_BLOCKS blocks, which bounds the pool's total.
+ * never past POW_POOL_MAX_BLOCKS blocks, which bounds the blocks a pool holds at
+ * a time; only pow_pool_prune makes them fewer.
  * pow_warmup does not launch this call's kernels.
  * Device memory: 98 bytes per block of the capacity and 4 per slot, the
  * context's tile staging buffer (pow_verify_chain's) apart; while an add grows
@@ -384,15 +385,16 @@ int pow_index_blocks(pow_ctx* ctx, const pow_block* pool, size_t n, unsigned dif
  * that re-ranks: 0.17 ms at 31 blocks (13 launches), 0.20 ms at 4,096, 0.23 ms
  * at 2^16, 1.19 ms at 2^20 (27 launches, kernels 1.10 ms).  A run of 5 blocks:
  * 0.11 ms at every size (7 launches).  Device memory at 2^20 blocks: 111.1 MB.
- * Walks.  Walking a chain (send_blockchain, log_chain) stays on the host: read
- * parent and follow it.
+ * Walks.  Walking a chain in order (send_blockchain, log_chain) stays on the
+ * host: read parent and follow it.  Which blocks lie under a tip, and dropping
+ * the forks that lost, run on the device: pow_pool_mark, pow_pool_prune below.
  * Lifetime and threads.  A pool is driven by its context's one thread.
  * Several pools may live on one context; pow_index_blocks and the verify calls
  * may be used between adds (they share the tile staging buffer and do not
  * disturb a pool).  Every pool is closed before pow_destroy: pow_destroy of a
  * context with open pools frees nothing, keeps the context usable and leaves
  * its reason in pow_last_error; close the pools and call it again.  A context bound
- * to a stop board refuses pow_pool_open, _add, _read and _find (POW_EINVAL).
+ * to a stop board refuses pow_pool_open, _add, _read, _find, _mark and _prune (POW_EINVAL).
  *
  * pow_pool_open: an empty pool at diff_bits.  reserve is a hint: the blocks
  * the arrays are sized for at once; 0 = 64 blocks.  POW_EINVAL, in this order
@@ -432,6 +434,91 @@ int pow_pool_get_info(const pow_pool* p, pow_pool_info* info);
 int pow_pool_read(pow_pool* p, size_t first, size_t count, uint8_t* status, uint32_t* parent, uint32_t* depth,
                   uint32_t* n_bad);
 int pow_pool_find(pow_pool* p, const char* names /* k x 64 */, size_t k, uint32_t* pos /* k */);
+
+/* "Which blocks lie on the chains under these tips?", and "forget every fork
+ * that lost": look_for_block and find_block over a migrated chain
+ * (node.cpp:131-148) without a host walk, and the way for a pool to shrink.
+ * The reference never migrates to a fork more than VALIDATION_BLOCKS behind the
+ * tip (verificar_y_migrar_cadena) and yet keeps every loser for ever.  Both are
+ * one computation on what the pool holds already (parent, depth, n_bad, the
+ * digests): mark every ancestor of a set of seed blocks, then, for the prune,
+ * compact the resident arrays onto the marked blocks.  Nothing is hashed again
+ * and no struct goes up.
+ * Seeds.  Every position in tips[] (duplicates allowed).  With
+ * POW_KEEP_BY_INDEX also every block with index >= min_index, in plain uint32_t
+ * comparison; without that flag min_index is ignored.  With POW_KEEP_SOUND_ONLY
+ * as well an index seed must also have n_bad == 0; explicit tips are seeds
+ * whatever their flags.  The marked set is every seed and every block on the
+ * walk from a seed along parent, to the walk's end (a root or POW_POOL_NONE).
+ * pow_pool_mark: on[i] (size bytes, may be NULL) is 1 for a marked block and 0
+ * otherwise, *n_on (may be NULL) the count of marked blocks; the pool's answers
+ * do not change.  Returns POW_OK.
+ * pow_pool_prune: the pool afterwards holds exactly the marked blocks, in
+ * their old order.  map[i] (the size BEFORE the call, may be NULL) is block i's
+ * new position, or POW_POOL_NONE if it was dropped; the caller compacts its own
+ * struct array with it.  Returns 1 if no block that is left is flagged, 0
+ * otherwise; *info (may be NULL) as pow_pool_get_info.
+ * The prune's contract.  After a prune status, parent, depth, n_bad, best,
+ * n_flagged and pow_pool_find are byte for byte what pow_index_blocks gives on
+ * the surviving structs in that order, at the pool's diff_bits; and after any
+ * later adds, on the survivors followed by everything added since.  Why: the
+ * marked set is closed under parent, so every survivor keeps its whole walk,
+ * its depth and n_bad stand and only positions are renamed.  A parent is the
+ * lowest twin of its name, and order is kept, so it stays the lowest.  A
+ * dropped lower twin of a kept block names nobody that is kept (a child of that
+ * name would have marked it).  A block that later names a dropped block is an
+ * orphan (POW_V_LINK), as it would be in that pow_index_blocks call.  A block
+ * on a cycle of names stays unspecified, as above.
+ * Info after a prune that dropped something: size, n_flagged, best,
+ * best_index, capacity and slots describe the pool as it now is; adopted 0,
+ * reranked 0, rehashed 1.  Nothing marked: the pool is empty, best
+ * POW_POOL_NONE.  Everything marked: nothing is touched, map is the identity,
+ * adopted, reranked and rehashed are 0.  On an empty pool neither call does
+ * GPU work.
+ * How they run.  One bounded wait: the tips go up, every block starts a walk
+ * at its parent and the seeds are marked (K12a), ceil(log2 size) rounds of
+ * pointer jumping carry the marks down every walk (K12b), the marks are
+ * counted per 256 blocks and scanned (K12c, K12d); the marks and the total
+ * come down.  A prune that keeps some blocks and drops some then allocates
+ * arrays at the lowest power of two that holds the survivors and is at least
+ * pow_pool_open's first capacity, and a table to match (slots >= 2 size still
+ * holds), and behind one more bounded wait gathers the survivors' entries into
+ * them (K12e), renames the parents and redoes the fork choice and the flagged
+ * count (K12f) and fills the table (K10b).  It is the one call that gives
+ * device memory back; the arrays it leaves stand beside the new until it
+ * returns.  The scratch is arrays the pool has anyway.
+ * Cost.  Launches (pow_get_stats; hashes = 0): 3 + ceil(log2 size) for a mark,
+ * 6 + ceil(log2 size) for a prune that drops and keeps.  No host loop runs
+ * over the pool's blocks, only the check of the tips.  pow_warmup does not
+ * launch these kernels.
+ * Measured (MI355X, profiles/pool_prune/README.md; medians of 9 calls on
+ * shuffled sound pools in the published shape at d = 0, three rivals per
+ * height, the winning tip as the one seed, so two thirds of N blocks go;
+ * against pow_pool_close, pow_pool_open and one pow_pool_add of the survivors
+ * in the same process, what the library took before): mark / prune / that
+ * path: 89 / 153 / 366 us at N = 31 (8 and 11 launches), 99 / 172 / 394 us at
+ * 199, 110 / 191 / 437 us at 4,096, 0.14 / 0.45 / 0.91 ms at 2^16, 0.36 /
+ * 1.00 / 7.3 ms at 2^20 - 3 (23 and 26 launches, kernels 0.22 and 0.34 ms).
+ * The prune was expected to be the slower one below some hundreds of blocks,
+ * being 6 + ceil(log2 N) launch boundaries; against that whole path it is not,
+ * at any size measured.  Against the pow_pool_add of the survivors alone, into
+ * a pool that is already open, it has not been measured; by the add's own
+ * figures above (about 0.1 ms for a small batch) that add would be the faster
+ * one for pools of some hundreds of blocks.  Device memory at 2^20 - 3 blocks:
+ * 111.1 MB before, 55.6 MB after (capacity 2^20 to 2^19).  A pool opened with
+ * a reserve below pow_pool_open's first capacity grows to it (31 to 64).
+ * POW_EINVAL, in this order before the context is touched and with nothing
+ * written: a null pool; flag bits other than the two; n_tips >
+ * POW_POOL_MAX_TIPS; null tips with n_tips > 0; a tip at or past size.  Then as
+ * every pool call: POW_EHIP on a pool that is unusable, POW_EINVAL on a context
+ * bound to a stop board.  A prune that fails with POW_EHIP leaves the pool
+ * unusable, as a failed add does. */
+enum { POW_KEEP_BY_INDEX = 1, POW_KEEP_SOUND_ONLY = 2 };
+#define POW_POOL_MAX_TIPS (1u << 16)
+int pow_pool_mark(pow_pool* p, const uint32_t* tips, size_t n_tips, uint32_t min_index, unsigned flags,
+                  uint8_t* on /* size bytes, may be NULL */, size_t* n_on /* may be NULL */);
+int pow_pool_prune(pow_pool* p, const uint32_t* tips, size_t n_tips, uint32_t min_index, unsigned flags,
+                   uint32_t* map /* the size BEFORE the call, may be NULL */, pow_pool_info* info /* may be NULL */);
 
 /* Mining round: replaces node.cpp:302-308 (nonce -> hash -> test) for every
  * counter in [ctr_start, ctr_start + ctr_count).  The header fields and the

@@ -11,7 +11,7 @@ the reference's names on the host side:
 * :mod:`mpi_blockchain_amd.shard`  — nonce space sharded over GPUs, RCCL min
 """
 from ._lib import Block, PowError, load  # noqa: F401
-from .block import V_HASH, V_INDEX, V_LINK, V_WORK, BlockPool, best_chain, chain_from, index_blocks, mine_batch, mine_chain, verify_chain, verify_chains  # noqa: F401
+from .block import V_HASH, V_INDEX, V_LINK, V_WORK, BlockPool, best_chain, chain_from, index_blocks, mine_batch, mine_chain, prune_structs, verify_chain, verify_chains  # noqa: F401
 from .miner import audit_rand_provenance, rand_nonces, replay_proof_of_work  # noqa: F401
 
 __version__ = "0.1.0"

@@ -85,12 +85,13 @@ class GroupSearchInfo(ctypes.Structure):
 
 
 class PoolInfo(ctypes.Structure):
-    """pow_pool_info (include/pow_gpu.h): a pow_pool after its last add."""
+    """pow_pool_info (include/pow_gpu.h): a pow_pool after its last add or prune."""
 
     _fields_ = [(n, ctypes.c_uint32) for n in ("size", "n_flagged", "best", "best_index", "adopted", "reranked",
                                                "rehashed", "capacity", "slots")]
 
 
+POW_KEEP_BY_INDEX, POW_KEEP_SOUND_ONLY, POOL_MAX_TIPS = 1, 2, 1 << 16  # pow_pool_mark, pow_pool_prune
 POW_VALU_MIX, POW_VALU_FULL, POW_VALU_HALF = 0, 1, 2
 POW_LAUNCH_HIP, POW_LAUNCH_DIRECT = 0, 1
 
@@ -161,6 +162,10 @@ def load(test_hooks: bool = False) -> ctypes.CDLL:
                            ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
         "pow_pool_find": ([ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)],
                           ctypes.c_int),
+        "pow_pool_mark": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t, ctypes.c_uint32,
+                           ctypes.c_uint, ctypes.c_void_p, c_sizep], ctypes.c_int),
+        "pow_pool_prune": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t, ctypes.c_uint32,
+                            ctypes.c_uint, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(PoolInfo)], ctypes.c_int),
         "pow_mine_chain": ([ctypes.c_void_p, P, ctypes.c_size_t, ctypes.c_uint, ctypes.c_uint32, c_u64p,
                             ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, P,
                             c_sizep, c_u64p], ctypes.c_int),
@@ -221,7 +226,7 @@ def load(test_hooks: bool = False) -> ctypes.CDLL:
 EXPORTS = ("pow_device_count", "pow_init", "pow_warmup", "pow_destroy", "pow_last_error", "pow_get_stats", "pow_launch_path",
            "pow_device_info", "pow_device_pci_bus_id",
            "pow_nonce_from_counter", "pow_block_to_bytes", "pow_solves_problem", "pow_hash_blocks",
-           "pow_hash_block", "pow_verify_chain", "pow_verify_chains", "pow_index_blocks", "pow_pool_open", "pow_pool_close", "pow_pool_add", "pow_pool_get_info", "pow_pool_read", "pow_pool_find", "pow_mine_chain", "pow_mine_batch", "pow_mine_race", "pow_mine_rand", "pow_rand_nonces", "pow_find_seed", "pow_mine", "pow_mine_any", "pow_cancel", "pow_sweep", "pow_sweep_device", "pow_dev_alloc", "pow_dev_free",
+           "pow_hash_block", "pow_verify_chain", "pow_verify_chains", "pow_index_blocks", "pow_pool_open", "pow_pool_close", "pow_pool_add", "pow_pool_get_info", "pow_pool_read", "pow_pool_find", "pow_pool_mark", "pow_pool_prune", "pow_mine_chain", "pow_mine_batch", "pow_mine_race", "pow_mine_rand", "pow_rand_nonces", "pow_find_seed", "pow_mine", "pow_mine_any", "pow_cancel", "pow_sweep", "pow_sweep_device", "pow_dev_alloc", "pow_dev_free",
            "pow_dev_read", "pow_valu_peak", "pow_valu_rate", "pow_valu_rate_ctx", "pow_group_partition", "pow_group_unique_id", "pow_group_init",
            "pow_group_init_within",
            "pow_group_init_custom", "pow_group_destroy", "pow_group_info", "pow_group_rccl_path", "pow_group_last_search",

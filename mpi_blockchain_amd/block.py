@@ -56,7 +56,7 @@ MAX_BLOCKS = 200
 ALPHABET = "abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789"
 
 __all__ = ["Block", "make_block", "block_to_str", "solves_problem", "nonce_from_counter",
-           "gen_random_nonce", "field", "set_field", "verify_chain", "verify_chains", "best_chain", "index_blocks", "BlockPool", "chain_from", "POOL_ROOT", "POOL_NONE", "mine_chain", "mine_batch", "V_HASH", "V_WORK", "V_LINK", "V_INDEX", "DEFAULT_DIFFICULTY", "BLOCKS_TO_MINE",
+           "gen_random_nonce", "field", "set_field", "verify_chain", "verify_chains", "best_chain", "index_blocks", "BlockPool", "prune_structs", "chain_from", "POOL_ROOT", "POOL_NONE", "mine_chain", "mine_batch", "V_HASH", "V_WORK", "V_LINK", "V_INDEX", "DEFAULT_DIFFICULTY", "BLOCKS_TO_MINE",
            "VALIDATION_MINUTES", "VALIDATION_BLOCKS", "HASH_SIZE", "NONCE_SIZE", "MSG_BYTES"]
 
 
@@ -239,7 +239,7 @@ def index_blocks(pool, difficulty: int = DEFAULT_DIFFICULTY):
 
 class BlockPool:
     """A pool that is fed: the host statement of ``pow_pool`` (``pow_pool_open``,
-    ``pow_pool_add``, ``pow_pool_find``), incremental in its own right with a
+    ``pow_pool_add``, ``pow_pool_find``, ``pow_pool_mark``, ``pow_pool_prune``), incremental in its own right with a
     dict of names and a dict of waiting orphans.  After any sequence of
     :meth:`add` calls ``status``, ``parent``, ``depth``, ``n_bad``, ``best`` and
     ``ok`` are what :func:`index_blocks` gives on everything added so far, in
@@ -253,6 +253,7 @@ class BlockPool:
         self.index, self.status, self.parent, self.depth, self.n_bad = [], [], [], [], []
         self.best, self.adopted, self.n_flagged = None, 0, 0
         self._names, self._waiting, self._children = {}, {}, {}
+        self._name = []  # per block: its name, None for a V_HASH block (prune hands a dropped twin's name on)
 
     def __len__(self) -> int:
         return len(self.status)
@@ -309,6 +310,7 @@ class BlockPool:
                 flags |= V_HASH
             elif self._names.setdefault(digest.hex().encode(), i) == i:
                 new_names.append(digest.hex().encode())
+            self._name.append(None if flags & V_HASH else digest.hex().encode())
             if 256 - int.from_bytes(digest, "big").bit_length() < self.difficulty:
                 flags |= V_WORK
             self.index.append(b.index)
@@ -335,6 +337,68 @@ class BlockPool:
         for i in old:
             self._rank(i)
         return self.ok
+
+    def mark(self, tips=(), min_index: int | None = None, sound_only: bool = False) -> list[int]:
+        """The host statement of ``pow_pool_mark``: per block 1 if it is a
+        seed or lies on the walk from a seed along ``parent``, else 0.  The
+        seeds are the positions in `tips` and, unless `min_index` is None,
+        every block with ``index >= min_index`` (`sound_only`: and ``n_bad ==
+        0``; the tips are seeds whatever their flags)."""
+        n = len(self)
+        tips = [int(t) for t in tips]
+        if any(not 0 <= t < n for t in tips):
+            raise ValueError("a tip past the pool")
+        seeds = list(tips)
+        if min_index is not None:
+            seeds += [i for i in range(n) if self.index[i] >= min_index and not (sound_only and self.n_bad[i])]
+        on = [0] * n
+        for i in seeds:
+            while i < n and not on[i]:  # a marked block's walk is marked already
+                on[i] = 1
+                i = self.parent[i]
+        return on
+
+    def prune(self, tips=(), min_index: int | None = None, sound_only: bool = False) -> list[int]:
+        """The host statement of ``pow_pool_prune``: the pool keeps exactly
+        what :meth:`mark` marks, in its order, and every later :meth:`add` goes
+        on from there.  Returns the map: per block of the pool before the call
+        its new position, or ``POOL_NONE`` if it was dropped.  The marked set
+        is closed under ``parent``, so status, depth and n_bad stand; parents,
+        names, waiting orphans and children move to the new positions, and a
+        name whose lowest twin was dropped goes to the lowest twin kept."""
+        on = self.mark(tips, min_index, sound_only)
+        new, kept = [], 0
+        for m in on:
+            new.append(kept if m else POOL_NONE)
+            kept += m
+        self.adopted = 0
+        if kept == len(on):
+            return new
+        keep = [i for i, m in enumerate(on) if m]
+        self.parent = [new[p] if p < len(on) else p for p in (self.parent[i] for i in keep)]
+        self.index, self.status, self.depth, self.n_bad, self._name = (
+            [a[i] for i in keep] for a in (self.index, self.status, self.depth, self.n_bad, self._name))
+        self._names = {}
+        for j, name in enumerate(self._name):
+            if name is not None:
+                self._names.setdefault(name, j)
+        self._waiting = {prev: [new[i] for i in who if on[i]] for prev, who in self._waiting.items()}
+        self._waiting = {prev: who for prev, who in self._waiting.items() if who}
+        self._children = {new[p]: [new[c] for c in cs if on[c]] for p, cs in self._children.items() if on[p]}
+        self.n_flagged = sum(1 for s in self.status if s)
+        self.best = None
+        for j in range(kept):
+            if self.n_bad[j] == 0 and (self.best is None or self.index[j] > self.index[self.best]):
+                self.best = j
+        return new
+
+
+def prune_structs(blocks, new):
+    """The survivors of a prune in their order: the blocks whose entry in
+    `new` (``BlockPool.prune``'s or ``GpuPool.prune``'s map) is a position."""
+    if len(blocks) != len(new):
+        raise ValueError("one map entry per block")
+    return [b for b, j in zip(blocks, new) if j != POOL_NONE]
 
 
 def chain_from(pool, parent, i: int):

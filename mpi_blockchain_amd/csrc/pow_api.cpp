@@ -1015,6 +1015,124 @@ int pow_pool_find(pow_pool* p, const char* names, size_t k, uint32_t* pos) {
   return timed_end(ctx, "pool find kernel", 100ull * k, 1u, &ctx->stats);
 }
 
+// ---- pow_pool_mark, pow_pool_prune (K12) ----
+
+// The argument checks of both calls, in the header's order.  The one host loop
+// of either call: over the tips, never over the pool's blocks.
+static int pool_mark_args(const pow_pool* p, const uint32_t* tips, size_t n_tips, unsigned flags) {
+  if (!p) return fail(POW_EINVAL, "null pool");
+  if (flags & ~(unsigned)(POW_KEEP_BY_INDEX | POW_KEEP_SOUND_ONLY)) return fail(POW_EINVAL, "unknown flags 0x%x", flags);
+  if (n_tips > POW_POOL_MAX_TIPS) return fail(POW_EINVAL, "too many tips (%zu > %u)", n_tips, POW_POOL_MAX_TIPS);
+  if (!tips && n_tips) return fail(POW_EINVAL, "null tips");
+  for (size_t k = 0; k < n_tips; ++k)
+    if (tips[k] >= p->size) return fail(POW_EINVAL, "tip %zu (block %u) past the pool's %u", k, tips[k], p->size);
+  return POW_OK;
+}
+
+// One timed section over a pool that holds blocks: the tips up (d_find), the
+// marks' reset, K12a, the rounds of K12b, K12c and K12d, then the control words
+// and, if asked for, the marks down.  The marks lie in depth[1 - fin], every
+// block's own position in bad[1 - fin], the partials' scan in next[1].
+static int pool_mark_run(pow_pool* p, const uint32_t* tips, uint32_t n_tips, uint32_t min_index, unsigned flags,
+                         uint8_t* on, uint32_t* marked) {
+  pow_ctx* const ctx = p->ctx;
+  const uint32_t n = p->size, rounds = pow_pool_rounds(n);
+  const PowPoolDev D = pool_dev(p, n);
+  RESERVE(p->d_find, std::max<size_t>(n_tips, 1));
+  if (n_tips) HIP_OK(hipMemcpyAsync(p->d_find.p, tips, n_tips * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+  PowPoolLiveCtl* const ctl = p->h_ctl.p;
+  if (int rc = timed_begin(ctx)) return rc;
+  HIP_OK(hipMemsetAsync(D.depth[p->fin ^ 1u], 0, (size_t)((n + 3u) / 4u) * sizeof(uint32_t), ctx->stream));
+  HIP_OK(pow_launch_pool_prune_seed(ctx->stream, D, p->fin, p->d_find.p, n_tips, min_index, flags));
+  for (uint32_t r = 0; r < rounds; ++r) HIP_OK(pow_launch_pool_prune_round(ctx->stream, D, p->fin, r));
+  HIP_OK(pow_launch_pool_prune_count(ctx->stream, D, p->fin));
+  HIP_OK(pow_launch_pool_prune_scan(ctx->stream, D));
+  HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+  HIP_OK(hipMemcpyAsync(ctl, D.ctl, sizeof(PowPoolLiveCtl), hipMemcpyDeviceToHost, ctx->stream));
+  if (on) HIP_OK(hipMemcpyAsync(on, D.depth[p->fin ^ 1u], n, hipMemcpyDeviceToHost, ctx->stream));
+  // + 100 ns per block and launch
+  if (int rc = timed_end(ctx, "pool mark kernels", 100ull * n * (rounds + 3ull), 3u + rounds, &ctx->stats)) return rc;
+  *marked = ctl->marked;
+  return POW_OK;
+}
+
+int pow_pool_mark(pow_pool* p, const uint32_t* tips, size_t n_tips, uint32_t min_index, unsigned flags, uint8_t* on,
+                  size_t* n_on) {
+  if (int rc = pool_mark_args(p, tips, n_tips, flags)) return rc;
+  if (int rc = pool_ready(p, "pow_pool_mark")) return rc;
+  p->ctx->stats = pow_stats{};
+  uint32_t marked = 0;
+  if (p->size)
+    if (int rc = pool_mark_run(p, tips, (uint32_t)n_tips, min_index, flags, on, &marked)) return rc;
+  if (n_on) *n_on = marked;
+  return POW_OK;
+}
+
+// The mark's section, then by its total: everything marked, and only the
+// positions K12a wrote come down as the map; otherwise new arrays and a table
+// fitted to what is left (pow_pool_prune_cap, _slots), and a second timed
+// section: their reset, K12e, K12f, K10b over the survivors, the control words
+// and the map down.  The arrays and the table left behind stay allocated until
+// that section's wait has passed, as pool_grow leaves them.
+int pow_pool_prune(pow_pool* p, const uint32_t* tips, size_t n_tips, uint32_t min_index, unsigned flags, uint32_t* map,
+                   pow_pool_info* info) {
+  if (int rc = pool_mark_args(p, tips, n_tips, flags)) return rc;
+  if (int rc = pool_ready(p, "pow_pool_prune")) return rc;
+  pow_ctx* const ctx = p->ctx;
+  ctx->stats = pow_stats{};
+  const uint32_t n = p->size;
+  uint32_t kept = 0;
+  if (n) {
+    p->dead = true;  // until the prune has gone through
+    if (int rc = pool_mark_run(p, tips, (uint32_t)n_tips, min_index, flags, nullptr, &kept)) return rc;
+  }
+  if (kept >= n) {  // nothing to drop: the pool stays as it is
+    if (map && n) {
+      const PowPoolDev F = pool_dev(p, n);
+      HIP_OK(hipMemcpyAsync(map, F.bad[p->fin ^ 1u], (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+      if (int rc = stream_wait_for(ctx, "pool map", 100ull * n)) return rc;
+    }
+    p->info.adopted = p->info.reranked = p->info.rehashed = 0;
+  } else {
+    const PowPoolDev F = pool_dev(p, n);  // the arrays the prune leaves behind
+    const uint32_t cap = pow_pool_prune_cap(kept, pow_pool_live_first_cap(0, ctx->pool_first_cap));
+    const uint32_t slots = pow_pool_prune_slots(cap, kept, ctx->pool_slots_log2);
+    const PowPoolLivePlan to = pow_pool_live_plan(cap);
+    p->d_old_arr = p->d_arr;
+    p->d_arr = DevBuf<uint32_t>{};
+    RESERVE(p->d_arr, to.words);
+    p->d_old_table = p->d_table;
+    p->d_table = DevBuf<uint32_t>{};
+    RESERVE(p->d_table, slots);
+    const PowPoolDev T = pow_pool_live_dev(p->d_arr.p, to, p->d_table.p, kept, slots);
+    PowPoolLiveCtl* const ctl = p->h_ctl.p;
+    if (int rc = timed_begin(ctx)) return rc;
+    HIP_OK(hipMemsetAsync(T.ctl, 0, sizeof(PowPoolLiveCtl), ctx->stream));
+    HIP_OK(hipMemsetAsync(T.table, 0xFF, (size_t)slots * sizeof(uint32_t), ctx->stream));
+    if (kept) {
+      HIP_OK(pow_launch_pool_prune_gather(ctx->stream, F, T, cap, p->fin));
+      HIP_OK(pow_launch_pool_prune_remap(ctx->stream, F, T, p->fin));
+      HIP_OK(pow_launch_pool_insert(ctx->stream, T));  // K10b: every named survivor
+    } else if (map) {  // nothing marked: every block was dropped
+      HIP_OK(hipMemsetD32Async((hipDeviceptr_t)F.next[0], (int)POW_POOL_NONE, n, ctx->stream));
+    }
+    HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+    HIP_OK(hipMemcpyAsync(ctl, T.ctl, sizeof(PowPoolLiveCtl), hipMemcpyDeviceToHost, ctx->stream));
+    if (map) HIP_OK(hipMemcpyAsync(map, F.next[0], (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    // + 100 ns per block and launch
+    if (int rc = timed_end(ctx, "pool prune kernels", 100ull * (n + 2ull * kept), kept ? 3u : 0u, &ctx->stats)) return rc;
+    if (ctl->k10.err) return fail(POW_EHIP, "pool table overflow (%u blocks, %u slots)", kept, slots);
+    p->d_old_arr.release(), p->d_old_table.release();  // the wait has passed: nothing reads them
+    p->plan = to;
+    p->slots = slots;
+    p->size = kept;
+    pool_fill_info(p, *ctl, 0, false, true);
+  }
+  p->dead = false;
+  if (info) *info = p->info;
+  return p->info.n_flagged == 0 ? 1 : 0;
+}
+
 int pow_sweep_device(pow_ctx* ctx, const pow_block* tmpl, uint64_t ctr_start, uint64_t ctr_count,
                      unsigned diff_bits, uint32_t* dev_out, size_t cap, size_t* n_found,
                      uint64_t* min_ctr) {

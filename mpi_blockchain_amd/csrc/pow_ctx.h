@@ -288,7 +288,7 @@ inline PowPoolDev pow_pool_dev(uint32_t* base, const PowPoolPlan& p, uint32_t n)
 struct PowPoolLiveCtl {
   PowPoolCtl k10;        // err; n_flagged and best over the whole pool, fed by every add
   unsigned int adopted;  // K11c: old blocks that were POW_POOL_NONE and have a parent now (atomic add)
-  unsigned int pad;
+  unsigned int marked;   // K12d: the blocks the last pow_pool_mark or pow_pool_prune marked; every add resets it
 };
 static_assert(sizeof(PowPoolLiveCtl) == 4 * POW_POOL_LIVE_CTL_WORDS && offsetof(PowPoolLiveCtl, k10) == 0,
               "the plan's control words; K10's launchers take the head");
@@ -467,6 +467,16 @@ hipError_t pow_launch_pool_live_finish(hipStream_t stream, const PowPoolDev& D, 
 hipError_t pow_launch_pool_live_strip(hipStream_t stream, const PowPoolDev& D);
 hipError_t pow_launch_pool_live_find(hipStream_t stream, const PowPoolDev& D, const uint32_t* names, uint32_t k,
                                      uint32_t* pos);
+// K12 (pow_pool_prune.hip), the kernels of pow_pool_mark and pow_pool_prune.  D, F: the pool's arrays; T: the
+// arrays a prune gathers into; fin: which of depth[], bad[] hold the final values (the others are scratch).
+hipError_t pow_launch_pool_prune_seed(hipStream_t stream, const PowPoolDev& D, uint32_t fin, const uint32_t* tips,
+                                      uint32_t n_tips, uint32_t min_index, uint32_t flags);
+hipError_t pow_launch_pool_prune_round(hipStream_t stream, const PowPoolDev& D, uint32_t fin, uint32_t r);
+hipError_t pow_launch_pool_prune_count(hipStream_t stream, const PowPoolDev& D, uint32_t fin);
+hipError_t pow_launch_pool_prune_scan(hipStream_t stream, const PowPoolDev& D);
+hipError_t pow_launch_pool_prune_gather(hipStream_t stream, const PowPoolDev& F, const PowPoolDev& T, uint32_t cap,
+                                        uint32_t fin);
+hipError_t pow_launch_pool_prune_remap(hipStream_t stream, const PowPoolDev& F, const PowPoolDev& T, uint32_t fin);
 hipError_t pow_sort_u32(void* temp, size_t* temp_bytes, uint32_t* keys, uint32_t* alt, uint32_t n,
                         uint32_t** sorted, hipStream_t stream);
 hipError_t pow_launch_search_lat(bool full, bool any, bool asm_groups, unsigned grid, hipStream_t stream,

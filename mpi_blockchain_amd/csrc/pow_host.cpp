@@ -544,6 +544,20 @@ uint32_t pow_pool_live_launches(uint32_t m, uint32_t size, bool rerank) {
   return tiles + 3u + pow_pool_rounds(m) + (rerank ? 3u + pow_pool_rounds(size) : 0u);
 }
 
+uint32_t pow_pool_prune_cap(uint32_t kept, uint32_t first_cap) {
+  const uint32_t need = std::min(std::max(std::max(kept, first_cap), 1u), POW_POOL_MAX_BLOCKS);
+  return 1u << pow_pool_rounds(need);
+}
+
+uint32_t pow_pool_prune_slots(uint32_t cap, uint32_t kept, unsigned slots_log2) {
+  return pow_pool_live_slots(pow_pool_live_first_slots(cap, slots_log2), kept);
+}
+
+uint32_t pow_pool_prune_launches(uint32_t size, uint32_t kept, bool prune) {
+  if (size == 0) return 0;
+  return 3u + pow_pool_rounds(size) + (prune && kept != 0 && kept < size ? 3u : 0u);
+}
+
 extern "C" {
 
 const char* pow_last_error(void) { return g_err.c_str(); }

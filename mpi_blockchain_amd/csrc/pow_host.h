@@ -230,4 +230,18 @@ uint32_t pow_pool_rounds(uint32_t n);
 // blocks alone.  A re-rank adds K11s, K10c, ceil(log2 size) rounds of K10d and K10e.
 uint32_t pow_pool_live_launches(uint32_t m, uint32_t size, bool rerank);
 
+// ---- pow_pool_mark, pow_pool_prune (K12) ----
+// The capacity a prune leaves for `kept` blocks (0..POW_POOL_MAX_BLOCKS): the lowest
+// power of two that holds them and is at least first_cap, what pow_pool_open takes
+// with reserve 0 (pow_pool_live_first_cap(0, ...)); at least 1, never past
+// POW_POOL_MAX_BLOCKS.  The table beside it is pow_pool_live_slots(
+// pow_pool_live_first_slots(cap, slots_log2), kept): slots >= 2 kept, as after an add.
+uint32_t pow_pool_prune_cap(uint32_t kept, uint32_t first_cap);
+uint32_t pow_pool_prune_slots(uint32_t cap, uint32_t kept, unsigned slots_log2);
+// The kernel launches of a mark (prune = false) or a prune of a pool of `size`
+// blocks of which `kept` are marked: K12a, ceil(log2 size) rounds of K12b, K12c
+// and K12d; a prune that drops some blocks and keeps some adds K12e, K12f and
+// K10b.  An empty pool: 0.
+uint32_t pow_pool_prune_launches(uint32_t size, uint32_t kept, bool prune);
+
 #pragma GCC visibility pop

@@ -13,8 +13,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import (HASH_SIZE, NONCE_SIZE, POOL_NONE, SEED_MAX_SEEDS, SEED_MAX_TARGETS, Block, PoolInfo, PowStats,
-                   SeedMatchRec, check, load)
+from ._lib import (HASH_SIZE, NONCE_SIZE, POOL_NONE, POW_KEEP_BY_INDEX, POW_KEEP_SOUND_ONLY, SEED_MAX_SEEDS,
+                   SEED_MAX_TARGETS, Block, PoolInfo, PowStats, SeedMatchRec, check, load)
 from .block import DEFAULT_DIFFICULTY, field, nonce_from_counter
 
 
@@ -217,6 +217,40 @@ class GpuPool:
         pos = (ctypes.c_uint32 * max(k, 1))()
         check(self.L.pow_pool_find(self.handle, b"".join(names), k, pos), self.L)
         return list(pos)[:k]
+
+    @staticmethod
+    def _seeds(tips, min_index, sound_only):
+        """(tips as a ctypes array, their count, min_index, flags) of pow_pool_mark and pow_pool_prune."""
+        tips = [int(t) for t in tips]
+        arr = (ctypes.c_uint32 * max(len(tips), 1))(*tips)
+        flags = 0 if min_index is None else POW_KEEP_BY_INDEX | (POW_KEEP_SOUND_ONLY if sound_only else 0)
+        return arr, len(tips), 0 if min_index is None else min_index, flags
+
+    def mark(self, tips=(), min_index: int | None = None, sound_only: bool = False) -> np.ndarray:
+        """pow_pool_mark: per block 1 if it is a seed or lies on the walk from
+        one along ``parent``, as a ``numpy.uint8`` array.  The seeds: every
+        position in `tips`, and with `min_index` every block of that index or
+        more (`sound_only`: only those with ``n_bad == 0``); ``None`` means no
+        index seeds.  The host statement is :meth:`block.BlockPool.mark`."""
+        arr, k, lo, flags = self._seeds(tips, min_index, sound_only)
+        on = np.zeros(len(self), dtype=np.uint8)
+        n_on = ctypes.c_size_t()
+        check(self.L.pow_pool_mark(self.handle, arr, k, lo, flags, on.ctypes.data_as(ctypes.c_void_p),
+                                   ctypes.byref(n_on)), self.L)
+        assert n_on.value == int(on.sum())
+        return on
+
+    def prune(self, tips=(), min_index: int | None = None, sound_only: bool = False):
+        """pow_pool_prune: the pool keeps exactly what :meth:`mark` marks, in
+        its order.  Returns ``(map, info)``: per block of the pool before the
+        call its new position or ``block.POOL_NONE`` (``numpy.uint32``), and
+        the pool's info with ``ok`` as :meth:`add` gives it."""
+        arr, k, lo, flags = self._seeds(tips, min_index, sound_only)
+        new = np.zeros(len(self), dtype=np.uint32)
+        raw = PoolInfo()
+        rc = check(self.L.pow_pool_prune(self.handle, arr, k, lo, flags,
+                                         new.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(raw)), self.L)
+        return new, {**self._info(raw), "ok": rc == 1}
 
 
 class GpuMiner:

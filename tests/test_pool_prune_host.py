@@ -1,0 +1,251 @@
+"""pow_pool_mark and pow_pool_prune on the host (CPU only): the Python mirror
+(block.BlockPool.mark and .prune, the GPU tests' yardstick) against a plain
+walk from every seed and against block.index_blocks over the surviving
+structs, also after more adds; the export list and the null-pool check of
+both C calls; and the host plan in tests/pool_prune_plan_unit.cpp, a process
+of its own under sanitizers."""
+import ctypes
+import os
+import random
+import subprocess
+
+import pytest
+
+from mpi_blockchain_amd import _lib
+from mpi_blockchain_amd.block import POOL_NONE, V_LINK, BlockPool, index_blocks, prune_structs
+
+import pool_util as pu
+from test_abi import header_functions
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ("pow_pool_mark", "pow_pool_prune")
+
+
+def plain_mark(mirror: BlockPool, tips, min_index, sound_only):
+    """The issue's words: every seed, and every block on the walk from a seed
+    along parent to the walk's end."""
+    n = len(mirror)
+    seeds = set(tips)
+    if min_index is not None:
+        seeds |= {i for i in range(n) if mirror.index[i] >= min_index and (not sound_only or mirror.n_bad[i] == 0)}
+    on = [0] * n
+    for i in seeds:
+        steps = 0
+        while i < n:
+            on[i] = 1
+            i = mirror.parent[i]
+            steps += 1
+            assert steps <= n  # names are digests: no walk comes back to itself
+    return on
+
+
+def against_index_blocks(mirror: BlockPool, structs, dropped_names=()):
+    """The mirror's whole state against index_blocks over `structs`, and find
+    of every struct's name and of every dropped name."""
+    status, parent, depth, n_bad, best = index_blocks(structs, mirror.difficulty)
+    assert (mirror.status, mirror.parent, mirror.depth, mirror.n_bad, mirror.best) == (status, parent, depth, n_bad, best)
+    assert mirror.n_flagged == sum(1 for s in status if s) and mirror.ok == (not any(status))
+    assert len(mirror) == len(structs) and mirror.index == [b.index for b in structs]
+    names = {}
+    for i, b in enumerate(structs):
+        if not status[i] & 1:
+            names.setdefault(pu.name_of(b), i)
+    for b in structs:
+        assert mirror.find(pu.name_of(b)) == names.get(pu.name_of(b), POOL_NONE)
+    for name in dropped_names:
+        assert mirror.find(name) == names.get(name, POOL_NONE)
+
+
+def seeds_for(mirror: BlockPool, seed: int):
+    """A few ways to choose seeds in a pool: (tips, min_index, sound_only)."""
+    rng = random.Random(seed)
+    n = len(mirror)
+    top = max(mirror.index)
+    best = [] if mirror.best is None else [mirror.best]
+    return [(best, None, False),
+            (rng.sample(range(n), min(n, 4)) + best + best, None, False),  # a duplicate among them
+            ([], max(0, top - 5), False),
+            ([], max(0, top - 5), True),
+            (rng.sample(range(n), min(n, 3)), max(0, top - 2), True),
+            ([], None, False),          # nothing
+            ([], 0, False),             # everything
+            ([], 0xFFFFFFFF, True),     # hardly anything
+            ([n - 1], 7, True)]
+
+
+def prune_and_compare(blocks, difficulty, seeds, more=()):
+    """Feed `blocks` in two adds, check mark against the plain walk, prune,
+    compare with index_blocks over the survivors; then `more` added to both."""
+    mirror = BlockPool(difficulty)
+    mirror.add(blocks[:len(blocks) // 3])
+    mirror.add(blocks[len(blocks) // 3:])
+    tips, min_index, sound_only = seeds
+    on = mirror.mark(tips, min_index, sound_only)
+    assert on == plain_mark(mirror, tips, min_index, sound_only)
+    before = list(mirror.results()[:4])
+    assert mirror.mark(tips, min_index, sound_only) == on and list(mirror.results()[:4]) == before  # mark changes nothing
+    new = mirror.prune(tips, min_index, sound_only)
+    assert len(new) == len(blocks) and [j for j in new if j != POOL_NONE] == list(range(sum(on)))
+    assert [int(j != POOL_NONE) for j in new] == on and mirror.adopted == 0
+    structs = prune_structs(blocks, new)
+    dropped = [pu.name_of(b) for b, j in zip(blocks, new) if j == POOL_NONE]
+    against_index_blocks(mirror, structs, dropped)
+    for batch in more:
+        mirror.add(batch)
+        structs = structs + list(batch)
+        against_index_blocks(mirror, structs, dropped)
+    return mirror, new, structs
+
+
+@pytest.fixture(scope="module")
+def tree():
+    return pu.tree(seed=3)
+
+
+@pytest.mark.parametrize("order", ["mined", "shuffled", "reversed"])
+def test_prune_of_the_tree(tree, order):
+    blocks = {"mined": list(tree), "reversed": tree[::-1], "shuffled": pu.shuffled(tree, 5)[0]}[order]
+    probe = BlockPool(pu.D)
+    probe.add(blocks)
+    extra = pu.mine_chain(blocks[probe.best], 2, pu.D, owner=9, created_at=[1_700_009_000, 1_700_009_001])[::-1]
+    for k, seeds in enumerate(seeds_for(probe, 11)):
+        mirror, new, structs = prune_and_compare(blocks, pu.D, seeds, more=[[extra[0]], [extra[1]]])
+        if new[probe.best] != POOL_NONE:  # the tip survived: the new blocks stand on it
+            assert mirror.parent[-2:] == [new[probe.best], len(mirror) - 2] and mirror.best == len(mirror) - 1
+        else:  # its parent was dropped: an orphan, as index_blocks has it
+            assert mirror.parent[-2] == POOL_NONE and mirror.status[-2] & V_LINK
+
+
+@pytest.mark.parametrize("seed,difficulty", pu.FUZZ)
+def test_prune_of_a_fuzz_pool(seed, difficulty):
+    blocks = pu.random_pool(seed)
+    probe = BlockPool(difficulty)
+    probe.add(blocks)
+    seeds = seeds_for(probe, seed)
+    more = pu.random_pool(seed + 1000)[:60]  # unrelated blocks, some of them twins of each other
+    prune_and_compare(blocks, difficulty, seeds[seed % len(seeds)], more=[more[:25], more[25:]])
+    prune_and_compare(blocks, difficulty, seeds[(seed + 3) % len(seeds)])
+
+
+@pytest.mark.parametrize("low_index,other_index", [(1, 257), (257, 1)])
+def test_prune_of_a_twin_storm(low_index, other_index):
+    storm, children = pu.twin_storm(low_index, other_index)
+    # a higher twin is a seed while the lowest (position 3) is not: the name passes to the lowest twin kept
+    mirror, new, structs = prune_and_compare(storm, 0, ([500, 700], None, False))
+    assert len(mirror) == 2 and new[3] == POOL_NONE and mirror.find(pu.name_of(storm[3])) == 0
+    # a child is a seed: the lowest twin is kept as its parent, the other twins go
+    mirror, new, structs = prune_and_compare(storm, 0, ([children[50]], None, False))
+    assert len(mirror) == 2 and new[3] == 0 and mirror.parent == [0xFFFFFFFF, 0]
+    # both: the kept higher twin stays behind the lowest
+    mirror, new, structs = prune_and_compare(storm, 0, ([children[50], 5], None, False), more=[[storm[children[0]]]])
+    assert len(mirror) == 4 and mirror.parent == [0xFFFFFFFF, 0xFFFFFFFF, 0, 0]
+    # by index, sound only.  (1, 257): the 700 twins and the 100 children are seeds, and the lowest twin is the
+    # children's parent.  (257, 1): the lowest twin alone; the children's index does not fit it, so they are not sound.
+    mirror, new, structs = prune_and_compare(storm, 0, ([], 2, True))
+    assert new[3] == 0 and len(mirror) == (801 if low_index == 1 else 1)
+
+
+def test_a_surviving_orphan_is_adopted_after_the_prune(tree):
+    """The trunk without its root and its first block: the kept chain hangs on
+    a parent that arrives after the prune, and the add re-ranks it."""
+    blocks = tree[2:13] + tree[33:]  # trunk[1:] on a missing trunk[0], and the second root's chain
+    mirror, new, structs = prune_and_compare(blocks, pu.D, ([10], None, False))
+    assert len(mirror) == 11 and mirror.parent[0] == POOL_NONE and not mirror.ok
+    mirror.add([tree[1]])
+    assert mirror.adopted == 1 and mirror.parent[0] == 11 and mirror.parent[11] == POOL_NONE
+    mirror.add([tree[0]])
+    assert mirror.adopted == 1 and mirror.ok and mirror.depth[10] == 13 and mirror.best == 10
+    against_index_blocks(mirror, structs + [tree[1], tree[0]])
+    # a child of a dropped block is an orphan
+    mirror.add([tree[35]])
+    assert mirror.parent[-1] == POOL_NONE and mirror.status[-1] == V_LINK and mirror.adopted == 0
+
+
+def test_prune_again_after_adds(tree):
+    blocks, _ = pu.shuffled(tree, 9)
+    mirror = BlockPool(pu.D)
+    structs = []
+    for lo in range(0, 40, 10):
+        mirror.add(blocks[lo:lo + 10])
+        structs += blocks[lo:lo + 10]
+        top = max(mirror.index)
+        new = mirror.prune([], max(0, top - 3), False)
+        structs = prune_structs(structs, new)
+        against_index_blocks(mirror, structs)
+    assert 0 < len(mirror) < 40
+
+
+def test_the_mirror_refuses_a_tip_past_the_pool(tree):
+    mirror = BlockPool(pu.D)
+    mirror.add(tree[:5])
+    for call in (mirror.mark, mirror.prune):
+        with pytest.raises(ValueError):
+            call([5])
+        with pytest.raises(ValueError):
+            call([-1])
+    assert len(mirror) == 5
+    with pytest.raises(ValueError):
+        prune_structs(tree[:5], [0, 1])
+    empty = BlockPool(pu.D)
+    assert empty.mark() == [] and empty.prune([], 0) == [] and empty.best is None
+
+
+def test_the_names_are_exported():
+    assert set(NAMES) <= set(_lib.EXPORTS) and set(_lib.EXPORTS) == header_functions()
+    for lib in (_lib.load(), _lib.load(test_hooks=True)):
+        for name in NAMES:
+            assert getattr(lib, name)
+    header = open(os.path.join(ROOT, "include", "pow_gpu.h")).read()
+    assert "enum { POW_KEEP_BY_INDEX = 1, POW_KEEP_SOUND_ONLY = 2 };" in header
+    assert "#define POW_POOL_MAX_TIPS (1u << 16)" in header
+    assert (_lib.POW_KEEP_BY_INDEX, _lib.POW_KEEP_SOUND_ONLY, _lib.POOL_MAX_TIPS) == (1, 2, 1 << 16)
+    assert ctypes.sizeof(_lib.PoolInfo) == 36  # the struct keeps its layout
+
+
+def test_a_null_pool_is_the_first_fault():
+    """Each call has every LATER fault too (unknown flags, too many tips, null
+    tips) and the message names the first.  Nothing is written and no context
+    is touched (there is none).  The later checks need a pool:
+    tests/test_pool_prune_gpu.py."""
+    L = _lib.load()
+    err = lambda: (L.pow_last_error() or b"").decode()  # noqa: E731
+    info = _lib.PoolInfo(*[0xA5A5A5A5] * 9)
+    words = (ctypes.c_uint32 * 4)(*[0xA5A5A5A5] * 4)
+    n_on = ctypes.c_size_t(77)
+    for flags, n_tips, tips in ((0xFF, 1 << 40, None), (0, (1 << 16) + 1, None), (3, 1, None), (3, 4, words)):
+        assert L.pow_pool_mark(None, tips, n_tips, 0, flags, words, ctypes.byref(n_on)) == _lib.POW_EINVAL
+        assert "null pool" in err()
+        assert L.pow_pool_prune(None, tips, n_tips, 0, flags, words, ctypes.byref(info)) == _lib.POW_EINVAL
+        assert "null pool" in err()
+    assert list(words) == [0xA5A5A5A5] * 4 and info.size == info.slots == 0xA5A5A5A5 and n_on.value == 77
+
+
+def test_the_checks_stand_in_the_stated_order():
+    """Both calls open with one helper, whose checks are in the header's
+    order, then pool_ready, then the statistics' reset."""
+    from test_build import api_function
+
+    args = api_function("pool_mark_args")
+    order = [args.index(s) for s in ("!p)", "POW_KEEP_BY_INDEX | POW_KEEP_SOUND_ONLY", "n_tips > POW_POOL_MAX_TIPS",
+                                     "!tips && n_tips", "tips[k] >= p->size")]
+    assert order == sorted(order) and "hip" not in args and "ctx" not in args
+    for name in NAMES:
+        body = api_function(name)
+        order = [body.index(s) for s in ("pool_mark_args(", "pool_ready(", "stats = pow_stats{}", "pool_mark_run(")]
+        assert order == sorted(order), name
+
+
+def test_plan_under_sanitizers(tmp_path):
+    """tests/pool_prune_plan_unit.cpp links pow_host.cpp alone and runs as a
+    process of its own under ASan + UBSan: nothing is loaded into Python."""
+    csrc = os.path.join(ROOT, "mpi_blockchain_amd", "csrc")
+    exe = str(tmp_path / "pool_prune_plan_unit")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=undefined", "-I", os.path.join(ROOT, "include"), "-I", csrc,
+                    os.path.join(ROOT, "tests", "pool_prune_plan_unit.cpp"), os.path.join(csrc, "pow_host.cpp"),
+                    "-o", exe], check=True, cwd=str(tmp_path))
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    print(r.stdout, r.stderr)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    assert " checks, 0 failed" in r.stdout, r.stdout
+    assert int(r.stdout.split(" checks, 0 failed")[0].split()[-1]) > 20_000  # the sweeps ran
