@@ -385,9 +385,11 @@ int pow_index_blocks(pow_ctx* ctx, const pow_block* pool, size_t n, unsigned dif
  * that re-ranks: 0.17 ms at 31 blocks (13 launches), 0.20 ms at 4,096, 0.23 ms
  * at 2^16, 1.19 ms at 2^20 (27 launches, kernels 1.10 ms).  A run of 5 blocks:
  * 0.11 ms at every size (7 launches).  Device memory at 2^20 blocks: 111.1 MB.
- * Walks.  Walking a chain in order (send_blockchain, log_chain) stays on the
- * host: read parent and follow it.  Which blocks lie under a tip, and dropping
- * the forks that lost, run on the device: pow_pool_mark, pow_pool_prune below.
+ * Walks.  Walking a chain in order (send_blockchain, log_chain), a block's
+ * ancestor and the fork point of two chains run on the device:
+ * pow_pool_chain, pow_pool_ancestors, pow_pool_fork_points below.  So do
+ * which blocks lie under a tip, and dropping the forks that lost:
+ * pow_pool_mark, pow_pool_prune below.
  * Lifetime and threads.  A pool is driven by its context's one thread.
  * Several pools may live on one context; pow_index_blocks and the verify calls
  * may be used between adds (they share the tile staging buffer and do not
@@ -519,6 +521,100 @@ int pow_pool_mark(pow_pool* p, const uint32_t* tips, size_t n_tips, uint32_t min
                   uint8_t* on /* size bytes, may be NULL */, size_t* n_on /* may be NULL */);
 int pow_pool_prune(pow_pool* p, const uint32_t* tips, size_t n_tips, uint32_t min_index, unsigned flags,
                    uint32_t* map /* the size BEFORE the call, may be NULL */, pow_pool_info* info /* may be NULL */);
+
+/* "Where do the old best chain and the new one part?", "is this block on my
+ * chain?", "give me the blocks under this one, in order": look_for_block and
+ * find_block (node.cpp:131-148), the migration rule of
+ * verificar_y_migrar_cadena (node.cpp:150-191) and the walks of
+ * send_blockchain and log_chain (node.cpp:40-58, 334-359), answered on the
+ * device from the pool's own parent and depth, as pow_pool_read returns them.
+ * Nothing is hashed, no struct goes up and no host walk runs.
+ * pow_pool_ancestors: out[q] is the block steps[q] steps along parent from
+ * pos[q]; 0 steps give pos[q] itself.  If steps[q] >= depth[pos[q]], out[q] is
+ * the walk's end, the parent value of the walk's last block: POW_POOL_ROOT or
+ * POW_POOL_NONE.  Any uint32_t is a valid step count.
+ * pow_pool_fork_points: at[q] is the first block on the walk from a[q] that
+ * also lies on the walk from b[q]: a[q] itself when it is on b[q]'s walk (so
+ * a == b gives a), POW_POOL_NONE when the walks share no block (different
+ * roots, two orphan ends: an end is not a block).  back_a[q], back_b[q] (each
+ * may be NULL) are the steps from a[q] and b[q] to at[q], or with no shared
+ * block depth[a[q]] and depth[b[q]], the whole of both walks.  back_a == 0 is
+ * look_for_block; with a = a received chain's tip and b = the node's own tip,
+ * back_a is what find_block returns (its index == 1 clause stays with the
+ * caller).  A twin is a block like any other, with its own parent: the fork
+ * point of a block and its twin is their common parent.
+ * pow_pool_chain: *len = min(max_len, depth[tip]); out[j] is the block j steps
+ * under tip for j < *len, POW_POOL_NONE for *len <= j < min(max_len, size);
+ * nothing past that is touched.  One query launch, lane j answering (tip, j).
+ * A cycle of names: what the calls return is unspecified, as everywhere in
+ * the pool, but they return and read nothing outside the arrays: every loop has
+ * a constant bound and every position read is compared with size before use.
+ * How they run.  A binary-lifting table on the device.  Level 0 is the pool's
+ * parent array; row j >= 1 holds for every block the block 2^j steps under it,
+ * or the walk's end marker.  A pool of n blocks has max(ceil(log2 n) - 1, 0)
+ * rows.  The table is allocated by the first query call that needs it, at the
+ * pool's capacity at that moment: 4 x capacity x rows(capacity) bytes, 79.7 MB
+ * at a capacity of 2^20 (19 rows), beside the pool's 111.1 MB.  A pool that is
+ * never queried pays nothing.  It is brought up to date lazily, inside the next
+ * query call; pow_pool_add and pow_pool_prune launch nothing for it.  Up to
+ * date: no table launch.  Stale (never built, an add that re-ranked, a prune
+ * that dropped blocks, a capacity that outgrew the table's: then it is
+ * allocated again at the pool's capacity, not copied): one launch per row over
+ * all blocks.  Otherwise, for the m new blocks, the rows that exist: one launch
+ * of one workgroup when m <= 256, else one launch per row over m lanes; then
+ * one launch over all blocks for every row that is new because size passed a
+ * power of two.  A prune that drops something frees the table; an add that
+ * re-ranks keeps the allocation.
+ * Cost.  One bounded wait per call: the arguments up, the table's launches, one
+ * query launch, the results down.  Launches (pow_get_stats; hashes = 0): the
+ * table's plus one, so 2 for a query after a one-block add at every pool size,
+ * 3 when the size has just passed a power of two, 1 when nothing was added.  A
+ * lane does at most about 3 ceil(log2 size) dependent 4-byte reads.  The one
+ * host loop is the check of the positions, over the queries and never over the
+ * pool's blocks.  pow_warmup does not launch these kernels.  k == 0 (and
+ * max_len == 0) returns POW_OK with no GPU work and no table work.
+ * Measured (MI355X, profiles/pool_lift/README.md; medians of 9 calls on
+ * shuffled pools at d = 0: a trunk of half the blocks and eight chains forking
+ * from its tip; a and b two of those tips, N / 16 steps from their fork point;
+ * against pow_pool_read of parent and depth for the whole pool and a plain
+ * walk on the host, which is what a caller did before, and against that walk
+ * alone on arrays the host already holds): one pair with the table up to date
+ * takes 31 us at N = 31, 30 us at 4,096, 32 us at 2^16 and at 2^20 - 16 (1
+ * launch, kernel 7 to 10 us); after a one-block add 44, 43, 40 and 45 us (2
+ * launches); 4,096 pairs 56 to 63 us; pow_pool_chain of 5 blocks 27 us at every
+ * size, of the whole walk 27 us (17 blocks) to 0.29 ms (589,815 blocks, which
+ * the host walk takes 5.8 ms for).  The first query of a filled pool, with the
+ * table's allocation and every row: 84 us at 31 blocks (5 launches), 0.10 ms at
+ * 4,096, 0.13 ms at 2^16, 0.32 ms at 2^20 - 16 (20 launches, kernels 0.19 ms).
+ * Read and walk: 44, 41, 69 us and 2.9 ms.  So the query after an add ties with
+ * reading the pool down up to a few thousand blocks (43 against 41 us at
+ * 4,096), is 1.7x faster at 2^16 and 65x at 2^20 - 16.  Against a host that
+ * keeps its own copy of the tree and walks it (3 us up to 4,096 blocks, 14 us
+ * at 2^16, 0.65 ms at 2^20 - 16) the device query is slower up to 2^16 and
+ * 20x faster at 2^20 - 16: one pair is one launch and one bounded wait.  What
+ * that copy costs to keep current is not in its figure.  A block-major layout
+ * of the table was not tried.
+ * POW_EINVAL, in this order before the context is touched and with nothing
+ * written: a null pool; a null required array with k > 0 (for the chain call:
+ * null len, or null out with min(max_len, size) > 0); k > POW_POOL_MAX_BLOCKS;
+ * a position at or past size.  Then as every pool call: POW_EHIP on a pool
+ * that is unusable, POW_EINVAL on a context bound to a stop board.  The queries
+ * return POW_OK.
+ * pow_pool_lift_get_info: the table as the next query call will find it; no
+ * GPU work.  POW_EINVAL: a null pool or out. */
+int pow_pool_ancestors(pow_pool* p, const uint32_t* pos, const uint32_t* steps, size_t k, uint32_t* out /* k */);
+int pow_pool_fork_points(pow_pool* p, const uint32_t* a, const uint32_t* b, size_t k, uint32_t* at /* k */,
+                         uint32_t* back_a /* k, may be NULL */, uint32_t* back_b /* k, may be NULL */);
+int pow_pool_chain(pow_pool* p, uint32_t tip, size_t max_len, uint32_t* out /* min(max_len, size) */, size_t* len);
+typedef struct pow_pool_lift_info {
+  uint32_t covered;   /* blocks the table covers (0: none, or stale) */
+  uint32_t rows;      /* rows in use */
+  uint32_t capacity;  /* blocks a row has room for (0: not allocated) */
+  uint32_t rebuilt;   /* last query call: 1 if it made the table from nothing */
+  uint32_t extended;  /* last query call: blocks it extended the table by */
+  uint64_t bytes;     /* device memory the table holds */
+} pow_pool_lift_info;
+int pow_pool_lift_get_info(const pow_pool* p, pow_pool_lift_info* out);
 
 /* Mining round: replaces node.cpp:302-308 (nonce -> hash -> test) for every
  * counter in [ctr_start, ctr_start + ctr_count).  The header fields and the

@@ -239,7 +239,7 @@ def index_blocks(pool, difficulty: int = DEFAULT_DIFFICULTY):
 
 class BlockPool:
     """A pool that is fed: the host statement of ``pow_pool`` (``pow_pool_open``,
-    ``pow_pool_add``, ``pow_pool_find``, ``pow_pool_mark``, ``pow_pool_prune``), incremental in its own right with a
+    ``pow_pool_add``, ``pow_pool_find``, ``pow_pool_mark``, ``pow_pool_prune``, the ancestry queries), incremental in its own right with a
     dict of names and a dict of waiting orphans.  After any sequence of
     :meth:`add` calls ``status``, ``parent``, ``depth``, ``n_bad``, ``best`` and
     ``ok`` are what :func:`index_blocks` gives on everything added so far, in
@@ -391,6 +391,47 @@ class BlockPool:
             if self.n_bad[j] == 0 and (self.best is None or self.index[j] > self.index[self.best]):
                 self.best = j
         return new
+
+    def _at(self, *pos) -> None:
+        if any(not 0 <= int(i) < len(self) for i in pos):
+            raise ValueError("a position past the pool")
+
+    def ancestor(self, pos: int, steps: int) -> int:
+        """The host statement of ``pow_pool_ancestors``, as a plain walk: the
+        block `steps` steps along ``parent`` from `pos`, or the walk's end
+        (``POOL_ROOT`` or ``POOL_NONE``) if the walk is shorter."""
+        self._at(pos)
+        i = int(pos)
+        for _ in range(min(int(steps), self.depth[i])):
+            i = self.parent[i]
+        return i
+
+    def fork_point(self, a: int, b: int):
+        """The host statement of ``pow_pool_fork_points``: ``(at, back_a,
+        back_b)``.  `at` is the first block on the walk from `a` that also lies
+        on the walk from `b`, or ``POOL_NONE``; the backs are the steps from `a`
+        and `b` to it, or with no shared block the two depths."""
+        self._at(a, b)
+        steps_b, i, s = {}, int(b), 0
+        while i < len(self):
+            steps_b[i] = s
+            i, s = self.parent[i], s + 1
+        i, s = int(a), 0
+        while i < len(self):
+            if i in steps_b:
+                return i, s, steps_b[i]
+            i, s = self.parent[i], s + 1
+        return POOL_NONE, self.depth[int(a)], self.depth[int(b)]
+
+    def chain(self, tip: int, max_len: int | None = None) -> list[int]:
+        """The host statement of ``pow_pool_chain``: `tip`, its parent and so
+        on, at most `max_len` positions (all of the walk by default)."""
+        self._at(tip)
+        walk, i = [], int(tip)
+        while i < len(self) and (max_len is None or len(walk) < max_len):
+            walk.append(i)
+            i = self.parent[i]
+        return walk
 
 
 def prune_structs(blocks, new):

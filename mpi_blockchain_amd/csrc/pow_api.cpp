@@ -777,6 +777,22 @@ int pow_index_blocks(pow_ctx* ctx, const pow_block* pool, size_t n, unsigned dif
 
 }  // extern "C"
 
+// The binary-lifting table of a pool's ancestry queries (K13), made at the
+// first query that needs it: rows(capacity) rows of `capacity` words.  It covers
+// the pool's first `covered` blocks as the pool stood at generation `gen`.
+struct PowPoolLift {
+  DevBuf<uint32_t> d_up;
+  HostBuf<uint32_t> h_io;  // a query call's arguments and results, pinned: one copy up and one down
+  uint32_t covered = 0, capacity = 0;  // capacity 0: not allocated
+  uint32_t gen = 0;
+  uint32_t rebuilt = 0, extended = 0;  // of the last query call
+  void release_table() {
+    d_up.release();
+    covered = capacity = 0;
+  }
+  void release() { release_table(), h_io.release(); }
+};
+
 // pow_pool (include/pow_gpu.h): K10's per-block arrays and its table, resident.
 // Driven by its context's thread; its buffers are its own (pow_pool_close frees
 // them through release_buffers, which has to name every holder), the tile
@@ -787,6 +803,7 @@ struct pow_pool {
   uint32_t size = 0;           // blocks held
   uint32_t slots = 0;          // of the table
   uint32_t fin = 0;            // which of depth[], bad[] hold the final values
+  uint32_t gen = 0;            // bumped when an old block's walk or position may have changed: a re-rank, a prune that drops
   bool dead = false;           // an add failed half way: every later call is POW_EHIP
   PowPoolLivePlan plan{};      // the arrays' offsets at the present capacity
   DevBuf<uint32_t> d_arr;      // the arrays (plan.words)
@@ -795,8 +812,10 @@ struct pow_pool {
   DevBuf<uint32_t> d_find;     // pow_pool_find: 16 words per name up, then one per name down
   HostBuf<PowPoolLiveCtl> h_ctl;  // the pinned twin of the control words
   pow_pool_info info{};
+  PowPoolLift lift;            // K13's table: lazily made and extended by the query calls
   void release_buffers() {
     d_arr.release(), d_table.release(), d_old_arr.release(), d_old_table.release(), d_find.release(), h_ctl.release();
+    lift.release();
   }
 };
 
@@ -818,6 +837,7 @@ static void pool_fill_info(pow_pool* p, const PowPoolLiveCtl& ctl, uint32_t adop
   const uint32_t best = ctl.k10.best ? (uint32_t)~(uint32_t)ctl.k10.best : POW_POOL_NONE;
   p->info = pow_pool_info{p->size, ctl.k10.n_flagged, best, ctl.k10.best ? (uint32_t)(ctl.k10.best >> 32) : 0u,
                           adopted, reranked ? 1u : 0u, rehashed ? 1u : 0u, p->plan.cap, p->slots};
+  if (reranked) ++p->gen;  // K13's table is stale
 }
 
 // The pool's first buffers, their reset and one bounded wait.
@@ -1123,6 +1143,7 @@ int pow_pool_prune(pow_pool* p, const uint32_t* tips, size_t n_tips, uint32_t mi
     if (int rc = timed_end(ctx, "pool prune kernels", 100ull * (n + 2ull * kept), kept ? 3u : 0u, &ctx->stats)) return rc;
     if (ctl->k10.err) return fail(POW_EHIP, "pool table overflow (%u blocks, %u slots)", kept, slots);
     p->d_old_arr.release(), p->d_old_table.release();  // the wait has passed: nothing reads them
+    p->lift.release_table(), ++p->gen;  // K13's table goes with the blocks it covered
     p->plan = to;
     p->slots = slots;
     p->size = kept;
@@ -1131,6 +1152,149 @@ int pow_pool_prune(pow_pool* p, const uint32_t* tips, size_t n_tips, uint32_t mi
   p->dead = false;
   if (info) *info = p->info;
   return p->info.n_flagged == 0 ? 1 : 0;
+}
+
+// ---- pow_pool_ancestors, pow_pool_fork_points, pow_pool_chain (K13) ----
+
+// The argument checks of the two batched calls, in the header's order.  The
+// one host loop of a query call: over the queries, never over the pool's blocks.
+static int pool_lift_args(const pow_pool* p, const uint32_t* a, const uint32_t* b, const uint32_t* out, size_t k,
+                          bool both) {
+  if (!p) return fail(POW_EINVAL, "null pool");
+  if ((!a || !b || !out) && k) return fail(POW_EINVAL, "null");
+  if (k > POW_POOL_MAX_BLOCKS) return fail(POW_EINVAL, "too many queries (%zu > %u)", k, POW_POOL_MAX_BLOCKS);
+  for (size_t q = 0; q < k; ++q)
+    if (a[q] >= p->size || (both && b[q] >= p->size))
+      return fail(POW_EINVAL, "query %zu names a block past the pool's %u", q, p->size);
+  return POW_OK;
+}
+
+// The table brought up to date with the pool, inside the caller's timed
+// section: made from nothing if `stale`, otherwise extended over the blocks
+// behind the first `covered` (pow_pool_lift_launches states the launches).
+// *work: the lanes of those launches, for the watchdog.
+static int pool_lift_update(pow_pool* p, uint32_t covered, bool stale, uint32_t* launches, uint64_t* work) {
+  pow_ctx* const ctx = p->ctx;
+  PowPoolLift& t = p->lift;
+  const uint32_t n = p->size, m = n - covered;
+  const uint32_t have = stale ? 0u : pow_pool_lift_rows(covered), rows = pow_pool_lift_rows(n);
+  const uint32_t* const parent = pool_dev(p, n).parent;
+  *launches = pow_pool_lift_launches(covered, n, stale);
+  *work = 0;
+  if (m && have) {
+    if (m <= POW_POOL_LIFT_SMALL) {
+      HIP_OK(pow_launch_pool_lift_small(ctx->stream, parent, t.d_up.p, t.capacity, have, covered, n));
+      *work += m * (uint64_t)have;
+    } else {
+      for (uint32_t j = 1; j <= have; ++j)
+        HIP_OK(pow_launch_pool_lift_row(ctx->stream, parent, t.d_up.p, t.capacity, j, covered, m, n));
+      *work += m * (uint64_t)have;
+    }
+  }
+  for (uint32_t j = have + 1u; j <= rows; ++j)
+    HIP_OK(pow_launch_pool_lift_row(ctx->stream, parent, t.d_up.p, t.capacity, j, 0, n, n));
+  *work += (uint64_t)n * (rows - have);
+  t.rebuilt = stale ? 1u : 0u;
+  t.extended = stale ? 0u : m;
+  return POW_OK;
+}
+
+// One timed section over a pool that holds blocks, for k >= 1 queries: the
+// arguments up in one copy (d_find: in0, in1, then the results; h_io is its
+// pinned twin), the table's launches, the query launch, the results down in one
+// copy.  The caller's arrays are written once the wait has passed.  fork: K13d over the pairs (in0, in1).
+// Otherwise K13c, over (in0, in1) = (pos, steps) or, with in0 == nullptr, over
+// the chain of `tip`: k answers and the length word behind them (len).
+static int pool_lift_run(pow_pool* p, const char* what, bool fork, const uint32_t* in0, const uint32_t* in1, uint32_t k,
+                         uint32_t tip, uint32_t* out0, uint32_t* out1, uint32_t* out2, uint32_t* len) {
+  pow_ctx* const ctx = p->ctx;
+  PowPoolLift& t = p->lift;
+  const uint32_t n = p->size;
+  const size_t kb = (size_t)k * sizeof(uint32_t);
+  const bool stale = t.covered == 0 || t.capacity == 0 || t.gen != p->gen || t.covered > n || p->plan.cap > t.capacity;
+  if (t.capacity < p->plan.cap) {  // the first query, or the pool has outgrown it: not copied, made again
+    t.release_table();
+    RESERVE(t.d_up, (size_t)p->plan.cap * pow_pool_lift_rows(p->plan.cap));
+    t.capacity = p->plan.cap;
+  }
+  const uint32_t covered = stale ? 0u : t.covered;
+  t.covered = 0;  // until the launches are through
+  RESERVE(p->d_find, 5 * (size_t)k + 1);
+  RESERVE(t.h_io, 5 * (size_t)k + 1);
+  uint32_t* const d_in0 = p->d_find.p;
+  uint32_t* const d_in1 = d_in0 + k;
+  uint32_t* const d_out = d_in1 + k;
+  uint32_t* const h_out = t.h_io.p + 2 * (size_t)k;
+  const size_t n_out = fork ? 3 * (size_t)k : (size_t)k + (len ? 1u : 0u);
+  if (in0) {
+    memcpy(t.h_io.p, in0, kb);
+    memcpy(t.h_io.p + k, in1, kb);
+    HIP_OK(hipMemcpyAsync(d_in0, t.h_io.p, 2 * kb, hipMemcpyHostToDevice, ctx->stream));
+  }
+  const PowPoolDev D = pool_dev(p, n);
+  const PowLiftView v{D.parent, D.depth[p->fin], t.d_up.p, t.capacity, n, pow_pool_rounds(n)};
+  uint32_t launches = 0;
+  uint64_t work = 0;
+  if (int rc = timed_begin(ctx)) return rc;
+  if (int rc = pool_lift_update(p, covered, stale, &launches, &work)) return rc;
+  if (fork)
+    HIP_OK(pow_launch_pool_lift_fork(ctx->stream, v, k, d_in0, d_in1, d_out, d_out + k, d_out + 2 * (size_t)k));
+  else
+    HIP_OK(pow_launch_pool_lift_ancestor(ctx->stream, v, k, in0 ? d_in0 : nullptr, d_in1, tip, d_out));
+  HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+  HIP_OK(hipMemcpyAsync(h_out, d_out, n_out * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  // + 100 ns per block and launch
+  if (int rc = timed_end(ctx, what, 100ull * (work + k), launches + 1u, &ctx->stats)) return rc;
+  memcpy(out0, h_out, kb);
+  if (out1) memcpy(out1, h_out + k, kb);
+  if (out2) memcpy(out2, h_out + 2 * (size_t)k, kb);
+  if (len) *len = h_out[k];
+  t.covered = n;
+  t.gen = p->gen;
+  return POW_OK;
+}
+
+int pow_pool_ancestors(pow_pool* p, const uint32_t* pos, const uint32_t* steps, size_t k, uint32_t* out) {
+  if (int rc = pool_lift_args(p, pos, steps, out, k, false)) return rc;
+  if (int rc = pool_ready(p, "pow_pool_ancestors")) return rc;
+  p->ctx->stats = pow_stats{};
+  if (k == 0) return POW_OK;
+  return pool_lift_run(p, "pool ancestor kernels", false, pos, steps, (uint32_t)k, 0, out, nullptr, nullptr, nullptr);
+}
+
+int pow_pool_fork_points(pow_pool* p, const uint32_t* a, const uint32_t* b, size_t k, uint32_t* at, uint32_t* back_a,
+                         uint32_t* back_b) {
+  if (int rc = pool_lift_args(p, a, b, at, k, true)) return rc;
+  if (int rc = pool_ready(p, "pow_pool_fork_points")) return rc;
+  p->ctx->stats = pow_stats{};
+  if (k == 0) return POW_OK;
+  return pool_lift_run(p, "pool fork point kernels", true, a, b, (uint32_t)k, 0, at, back_a, back_b, nullptr);
+}
+
+int pow_pool_chain(pow_pool* p, uint32_t tip, size_t max_len, uint32_t* out, size_t* len) {
+  if (!p) return fail(POW_EINVAL, "null pool");
+  const uint32_t k = (uint32_t)std::min<size_t>(max_len, p->size);
+  if (!len || (!out && k)) return fail(POW_EINVAL, "null");
+  if (tip >= p->size) return fail(POW_EINVAL, "tip (block %u) past the pool's %u", tip, p->size);
+  if (int rc = pool_ready(p, "pow_pool_chain")) return rc;
+  p->ctx->stats = pow_stats{};
+  *len = 0;
+  if (k == 0) return POW_OK;
+  uint32_t got = 0;
+  if (int rc = pool_lift_run(p, "pool chain kernels", false, nullptr, nullptr, k, tip, out, nullptr, nullptr, &got))
+    return rc;
+  *len = got;
+  return POW_OK;
+}
+
+int pow_pool_lift_get_info(const pow_pool* p, pow_pool_lift_info* out) {
+  if (!p || !out) return fail(POW_EINVAL, "null");
+  const PowPoolLift& t = p->lift;
+  const bool fresh = t.capacity && t.gen == p->gen && t.covered <= p->size && p->plan.cap <= t.capacity;
+  const uint32_t covered = fresh ? t.covered : 0u;
+  *out = pow_pool_lift_info{covered, pow_pool_lift_rows(covered), t.capacity, t.rebuilt, t.extended,
+                            pow_pool_lift_bytes(t.capacity)};
+  return POW_OK;
 }
 
 int pow_sweep_device(pow_ctx* ctx, const pow_block* tmpl, uint64_t ctr_start, uint64_t ctr_count,

@@ -8,6 +8,7 @@
 #include <string>
 
 #include "pow_host.h"
+#include "pow_lift_dev.h"
 
 #define HIP_OK(expr)                                                                       \
   do {                                                                                     \
@@ -477,6 +478,16 @@ hipError_t pow_launch_pool_prune_scan(hipStream_t stream, const PowPoolDev& D);
 hipError_t pow_launch_pool_prune_gather(hipStream_t stream, const PowPoolDev& F, const PowPoolDev& T, uint32_t cap,
                                         uint32_t fin);
 hipError_t pow_launch_pool_prune_remap(hipStream_t stream, const PowPoolDev& F, const PowPoolDev& T, uint32_t fin);
+// K13 (pow_pool_lift.hip), the table and the kernels of pow_pool_ancestors, pow_pool_fork_points and pow_pool_chain.
+// up: the table's rows, cap words each, row j at up + (j - 1) cap; parent is its level 0.
+hipError_t pow_launch_pool_lift_row(hipStream_t stream, const uint32_t* parent, uint32_t* up, uint32_t cap, uint32_t j,
+                                    uint32_t first, uint32_t count, uint32_t size);
+hipError_t pow_launch_pool_lift_small(hipStream_t stream, const uint32_t* parent, uint32_t* up, uint32_t cap,
+                                      uint32_t rows, uint32_t first, uint32_t size);
+hipError_t pow_launch_pool_lift_ancestor(hipStream_t stream, const PowLiftView& v, uint32_t k, const uint32_t* pos,
+                                         const uint32_t* steps, uint32_t tip, uint32_t* out);
+hipError_t pow_launch_pool_lift_fork(hipStream_t stream, const PowLiftView& v, uint32_t k, const uint32_t* a,
+                                     const uint32_t* b, uint32_t* at, uint32_t* back_a, uint32_t* back_b);
 hipError_t pow_sort_u32(void* temp, size_t* temp_bytes, uint32_t* keys, uint32_t* alt, uint32_t n,
                         uint32_t** sorted, hipStream_t stream);
 hipError_t pow_launch_search_lat(bool full, bool any, bool asm_groups, unsigned grid, hipStream_t stream,

@@ -558,6 +558,20 @@ uint32_t pow_pool_prune_launches(uint32_t size, uint32_t kept, bool prune) {
   return 3u + pow_pool_rounds(size) + (prune && kept != 0 && kept < size ? 3u : 0u);
 }
 
+uint32_t pow_pool_lift_rows(uint32_t n) {
+  const uint32_t r = pow_pool_rounds(n);
+  return r ? r - 1u : 0u;
+}
+
+uint64_t pow_pool_lift_bytes(uint32_t cap) { return 4ull * cap * pow_pool_lift_rows(cap); }
+
+uint32_t pow_pool_lift_launches(uint32_t covered, uint32_t size, bool stale) {
+  if (stale) return pow_pool_lift_rows(size);
+  if (covered >= size) return 0;
+  const uint32_t m = size - covered, have = pow_pool_lift_rows(covered);
+  return (have ? (m <= POW_POOL_LIFT_SMALL ? 1u : have) : 0u) + (pow_pool_lift_rows(size) - have);
+}
+
 extern "C" {
 
 const char* pow_last_error(void) { return g_err.c_str(); }

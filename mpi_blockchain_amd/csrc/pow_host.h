@@ -244,4 +244,18 @@ uint32_t pow_pool_prune_slots(uint32_t cap, uint32_t kept, unsigned slots_log2);
 // K10b.  An empty pool: 0.
 uint32_t pow_pool_prune_launches(uint32_t size, uint32_t kept, bool prune);
 
+// ---- pow_pool_ancestors, pow_pool_fork_points, pow_pool_chain (K13) ----
+// The binary-lifting table of a pool of n blocks: its level 0 is the pool's
+// parent array, and it has max(pow_pool_rounds(n) - 1, 0) rows of its own.
+uint32_t pow_pool_lift_rows(uint32_t n);
+// The device memory of a table made at a capacity of cap blocks: 4 cap rows(cap) bytes.
+uint64_t pow_pool_lift_bytes(uint32_t cap);
+// The launches that bring a table that covers `covered` blocks up to a pool of
+// `size` (covered <= size).  stale: it is made from nothing, one launch per
+// row.  Otherwise, for the m = size - covered new blocks, the rows that exist:
+// one launch of one workgroup when m <= POW_POOL_LIFT_SMALL, else one per row;
+// then one launch for every row that is new because size passed a power of two.
+#define POW_POOL_LIFT_SMALL 256u
+uint32_t pow_pool_lift_launches(uint32_t covered, uint32_t size, bool stale);
+
 #pragma GCC visibility pop

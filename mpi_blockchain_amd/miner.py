@@ -14,7 +14,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._lib import (HASH_SIZE, NONCE_SIZE, POOL_NONE, POW_KEEP_BY_INDEX, POW_KEEP_SOUND_ONLY, SEED_MAX_SEEDS,
-                   SEED_MAX_TARGETS, Block, PoolInfo, PowStats, SeedMatchRec, check, load)
+                   SEED_MAX_TARGETS, Block, PoolInfo, PoolLiftInfo, PowStats, SeedMatchRec, check, load)
 from .block import DEFAULT_DIFFICULTY, field, nonce_from_counter
 
 
@@ -251,6 +251,56 @@ class GpuPool:
         rc = check(self.L.pow_pool_prune(self.handle, arr, k, lo, flags,
                                          new.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(raw)), self.L)
         return new, {**self._info(raw), "ok": rc == 1}
+
+    @staticmethod
+    def _u32(values) -> np.ndarray:
+        return np.ascontiguousarray(np.asarray(values, dtype=np.uint64).astype(np.uint32).reshape(-1))
+
+    def ancestors(self, pos, steps) -> np.ndarray:
+        """pow_pool_ancestors: per query the block ``steps[q]`` steps along
+        ``parent`` from ``pos[q]``, or the walk's end (``block.POOL_ROOT``,
+        ``block.POOL_NONE``), as ``numpy.uint32``.  The host statement is
+        :meth:`block.BlockPool.ancestor`."""
+        pos, steps = self._u32(pos), self._u32(steps)
+        if len(pos) != len(steps):
+            raise ValueError("one step count per position")
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        out = np.zeros(len(pos), dtype=np.uint32)
+        check(self.L.pow_pool_ancestors(self.handle, pos.ctypes.data_as(u32p), steps.ctypes.data_as(u32p), len(pos),
+                                        out.ctypes.data_as(u32p)), self.L)
+        return out
+
+    def fork_points(self, a, b):
+        """pow_pool_fork_points: ``(at, back_a, back_b)`` as ``numpy.uint32``
+        arrays; ``at[q]`` is the first block on the walk from ``a[q]`` that
+        also lies on the walk from ``b[q]``, or ``block.POOL_NONE``.  The host
+        statement is :meth:`block.BlockPool.fork_point`."""
+        a, b = self._u32(a), self._u32(b)
+        if len(a) != len(b):
+            raise ValueError("the queries are pairs")
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        at, back_a, back_b = (np.zeros(len(a), dtype=np.uint32) for _ in range(3))
+        check(self.L.pow_pool_fork_points(self.handle, a.ctypes.data_as(u32p), b.ctypes.data_as(u32p), len(a),
+                                          at.ctypes.data_as(u32p), back_a.ctypes.data_as(u32p),
+                                          back_b.ctypes.data_as(u32p)), self.L)
+        return at, back_a, back_b
+
+    def chain(self, tip: int, max_len: int | None = None) -> np.ndarray:
+        """pow_pool_chain: `tip`, its parent and so on in order, at most
+        `max_len` positions (the whole walk by default), as ``numpy.uint32``.
+        The host statement is :meth:`block.BlockPool.chain`."""
+        room = len(self) if max_len is None else int(max_len)
+        out = np.zeros(min(room, len(self)), dtype=np.uint32)
+        n = ctypes.c_size_t()
+        check(self.L.pow_pool_chain(self.handle, int(tip), room, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                    ctypes.byref(n)), self.L)
+        return out[:n.value]
+
+    def lift_info(self) -> dict:
+        """pow_pool_lift_get_info: the queries' table as the next query will find it."""
+        raw = PoolLiftInfo()
+        check(self.L.pow_pool_lift_get_info(self.handle, ctypes.byref(raw)), self.L)
+        return {name: getattr(raw, name) for name, _ in PoolLiftInfo._fields_}
 
 
 class GpuMiner:

@@ -16,6 +16,9 @@
 //   pool_extract     today's way's host part: the same map and tips, and every
 //                    tip's chain copied out tip first, back to back, ready for
 //                    one pow_verify_chains call.
+//   pool_walk_fork,  tools/pool_lift_bench.py's baselines: the fork point of two
+//   pool_walk_chain  blocks and the chain under a tip by plain walks along a
+//                    host copy of parent[] and depth[].
 //
 // SHA-256 is written out here (FIPS 180-4) so that the library needs nothing
 // but the C++ runtime.
@@ -212,6 +215,31 @@ int pool_ref_add(void* handle, const pow_block* add, size_t m, unsigned diff, ui
 void pool_ref_drop(void* handle, const pow_block* add, size_t m) {
   auto& node_blocks = *(std::map<std::string, pow_block>*)handle;
   for (size_t i = 0; i < m; ++i) node_blocks.erase(text(add[i].block_hash));
+}
+
+// ---- tools/pool_lift_bench.py: the walks a host does along a copy of parent[] ----
+
+// The fork point of a and b by plain walks, as a node without the device's
+// table finds it: the deeper side steps down to the other's depth, then both
+// step together until they meet.  parent, depth: n entries as pow_pool_read
+// gives them.  Returns the block (0xFFFFFFFE: none) and the steps on either side.
+uint32_t pool_walk_fork(const uint32_t* parent, const uint32_t* depth, size_t n, uint32_t a, uint32_t b, uint32_t* back_a,
+                        uint32_t* back_b) {
+  uint32_t x = a, y = b, sa = 0, sb = 0, da = depth[a], db = depth[b];
+  for (; da > db && x < n; --da, ++sa) x = parent[x];
+  for (; db > da && y < n; --db, ++sb) y = parent[y];
+  while (x < n && y < n && x != y) x = parent[x], y = parent[y], ++sa, ++sb;
+  const bool met = x < n && x == y;
+  *back_a = met ? sa : depth[a];
+  *back_b = met ? sb : depth[b];
+  return met ? x : 0xFFFFFFFEu;
+}
+
+// The walk from tip, at most max_len blocks, tip first; returns its length.
+size_t pool_walk_chain(const uint32_t* parent, size_t n, uint32_t tip, size_t max_len, uint32_t* out) {
+  size_t len = 0;
+  for (uint32_t x = tip; x < n && len < max_len; x = parent[x]) out[len++] = x;
+  return len;
 }
 
 // Returns the blocks written (at most cap; more were needed if it returns cap + 1).
