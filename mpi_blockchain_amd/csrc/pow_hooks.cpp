@@ -3,8 +3,9 @@
 // libpow_gpu.so.  The test and tuning switches read from the environment at
 // pow_init, the direct-dispatch launch path (pow_aql.cpp, POW_AQL=1), the stall
 // kernel of the watchdog tests, the stand-in RCCL of the shard tests and
-// the exports the shipped library does not have: pow_test_leading_zero_bits and
-// pow_test_pool_rank.
+// the exports the shipped library does not have: pow_test_leading_zero_bits,
+// pow_test_pool_rank, pow_test_pool_prune and pow_test_pool_lift (K10d/K10e, K12
+// and K13 on trees of the caller's making, up to POW_POOL_MAX_BLOCKS nodes).
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -239,5 +240,280 @@ extern "C" int pow_test_pool_rank(pow_ctx* ctx, const uint32_t* next, size_t n, 
   const int waited = pow_ctx_stream_wait(ctx, "pow_test_pool_rank", 100ull * n * (plan.rounds + 1u));
   if (rc == POW_OK) rc = waited;
   if (waited == POW_OK || !ctx->wedged) (void)hipFree(base);  // after a watchdog the launches may still write
+  return rc;
+}
+
+// What pow_test_pool_prune takes and gives: arrays of n entries unless said.
+// An output that is null is not written.
+struct pow_test_prune_io {
+  // in: a forest of the caller's making, as K10 and K11 would have left it
+  const uint32_t* parent;  // a position below n, POW_POOL_ROOT or POW_POOL_NONE
+  const uint32_t* index;
+  const uint32_t* n_bad;
+  const uint8_t* status;
+  const uint32_t* depth;
+  const uint32_t* digest;  // 8 n words; null: zeros
+  const uint32_t* prev;    // 8 n words; null: zeros
+  const uint32_t* tips;    // n_tips positions below n
+  size_t n_tips;
+  uint32_t min_index, flags;  // POW_KEEP_BY_INDEX, POW_KEEP_SOUND_ONLY
+  uint32_t fin;            // 0 or 1: which of depth[], bad[] hold the final values; the others are the scratch
+  // out
+  uint8_t* marks;          // K12a and K12b
+  uint32_t* kept;          // one word: K12d's total
+  uint32_t* map;           // K12e's newpos, or K12a's own positions when nothing is dropped
+  // the first `kept` entries of each (room for n): what K12e and K12f left, or the input when nothing is dropped
+  uint32_t* parent_out;
+  uint32_t* index_out;
+  uint32_t* depth_out;
+  uint32_t* n_bad_out;
+  uint8_t* status_out;
+  uint32_t* digest_out;    // 8 words a block
+  uint32_t* prev_out;      // 8 words a block
+  unsigned long long* best;  // one word: the new control words' key (K12f), 0 when nothing is dropped
+  uint32_t* n_flagged;     // one word: K12f's count, 0 when nothing is dropped
+};
+static_assert(sizeof(pow_test_prune_io) == 23 * 8, "tests/pool_deep_util.py PruneIO");
+
+// K12 (pow_pool_prune.hip) on a forest of the caller's choosing, with no pool
+// and no table: the marks' reset, K12a, the rounds of K12b, K12c and K12d in
+// one section, then by K12d's total, as pow_pool_prune decides it: everything
+// marked, and K12a's positions are the map; otherwise new arrays at
+// pow_pool_prune_cap's capacity, K12e and K12f (nothing marked: the map is
+// POW_POOL_NONE throughout, as the library's reset makes it).  K10b is not run.
+// Two bounded waits, one per section: the second section's grid is the first's
+// result.  The scratch is pool_mark_run's: marks in depth[1 - fin], positions
+// in bad[1 - fin], the walks in next[], the partials in next[1].
+extern "C" int pow_test_pool_prune(pow_ctx* ctx, size_t n, const pow_test_prune_io* io) {
+  if (n > POW_POOL_MAX_BLOCKS) return fail(POW_EINVAL, "too many nodes (%zu > 2^20)", n);
+  if (!ctx || !io) return fail(POW_EINVAL, "null");
+  if (io->flags & ~(uint32_t)(POW_KEEP_BY_INDEX | POW_KEEP_SOUND_ONLY)) return fail(POW_EINVAL, "unknown flags 0x%x", io->flags);
+  if (io->fin > 1u) return fail(POW_EINVAL, "fin %u > 1", io->fin);
+  if (io->n_tips > POW_POOL_MAX_TIPS) return fail(POW_EINVAL, "too many tips (%zu > %u)", io->n_tips, POW_POOL_MAX_TIPS);
+  if (!io->tips && io->n_tips) return fail(POW_EINVAL, "null tips");
+  if ((!io->parent || !io->index || !io->n_bad || !io->status || !io->depth) && n) return fail(POW_EINVAL, "null");
+  for (size_t k = 0; k < io->n_tips; ++k)
+    if (io->tips[k] >= n) return fail(POW_EINVAL, "tip %zu (node %u) past the forest's %zu", k, io->tips[k], n);
+  for (size_t i = 0; i < n; ++i)
+    if (io->parent[i] >= n && io->parent[i] < POW_POOL_NONE)
+      return fail(POW_EINVAL, "parent %u of node %zu is neither a node nor an end", io->parent[i], i);
+  if (n == 0) return POW_OK;
+  HIP_OK(hipSetDevice(ctx->device));
+  const uint32_t n32 = (uint32_t)n, n_tips = (uint32_t)io->n_tips, fin = io->fin, rounds = pow_pool_rounds(n32);
+  const PowPoolLivePlan from = pow_pool_live_plan(n32);
+  const size_t words = (size_t)n32 * sizeof(uint32_t);
+  uint32_t* base = nullptr;
+  uint32_t* to_base = nullptr;
+  uint32_t* d_tips = nullptr;
+  PowPoolLiveCtl ctl{}, new_ctl{};
+  int rc = POW_OK;
+  auto step = [&](hipError_t e, const char* what) {
+    if (rc == POW_OK && e != hipSuccess) rc = fail(POW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
+  };
+  auto release = [&](int waited) {  // after a watchdog the launches may still write
+    if (waited == POW_OK || !ctx->wedged) (void)hipFree(base), (void)hipFree(to_base), (void)hipFree(d_tips);
+  };
+  step(hipMalloc(&base, from.words * sizeof(uint32_t)), "hipMalloc");
+  step(hipMalloc(&d_tips, std::max<size_t>(n_tips, 1) * sizeof(uint32_t)), "hipMalloc");
+  if (rc != POW_OK) {
+    release(POW_OK);
+    return rc;
+  }
+  const PowPoolDev F = pow_pool_live_dev(base, from, nullptr, n32, 0);
+  auto up = [&](void* dst, const void* src, size_t bytes) {
+    if (rc == POW_OK && src) step(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream), "copy in");
+  };
+  auto down = [&](void* dst, const void* src, size_t bytes) {
+    if (rc == POW_OK && dst && bytes) step(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream), "copy out");
+  };
+  step(hipMemsetAsync(base, 0, from.words * sizeof(uint32_t), ctx->stream), "reset");  // kind, and a null digest or prev
+  up(F.parent, io->parent, words), up(F.index, io->index, words), up(F.bad[fin], io->n_bad, words);
+  up(F.depth[fin], io->depth, words), up(F.status, io->status, n), up(F.dig, io->digest, 8 * words);
+  up(F.prev, io->prev, 8 * words), up(d_tips, n_tips ? io->tips : nullptr, n_tips * sizeof(uint32_t));
+  if (rc == POW_OK) {  // pool_mark_run's section
+    step(hipMemsetAsync(F.depth[fin ^ 1u], 0, (size_t)((n32 + 3u) / 4u) * sizeof(uint32_t), ctx->stream), "reset");
+    step(pow_launch_pool_prune_seed(ctx->stream, F, fin, d_tips, n_tips, io->min_index, io->flags), "K12a");
+    for (uint32_t r = 0; r < rounds; ++r) step(pow_launch_pool_prune_round(ctx->stream, F, fin, r), "K12b");
+    step(pow_launch_pool_prune_count(ctx->stream, F, fin), "K12c");
+    step(pow_launch_pool_prune_scan(ctx->stream, F), "K12d");
+    down(&ctl, F.ctl, sizeof ctl), down(io->marks, F.depth[fin ^ 1u], n);
+  }
+  int waited = pow_ctx_stream_wait(ctx, "pow_test_pool_prune (mark)", 100ull * n * (rounds + 3ull));
+  if (rc == POW_OK) rc = waited;
+  if (rc != POW_OK) {
+    release(waited);
+    return rc;
+  }
+  const uint32_t kept = ctl.marked;
+  if (kept > n32) {
+    release(waited);
+    return fail(POW_EHIP, "K12d counted %u marks on %u nodes", kept, n32);
+  }
+  if (io->kept) *io->kept = kept;
+  if (io->best) *io->best = 0;
+  if (io->n_flagged) *io->n_flagged = 0;
+  if (kept == n32) {  // nothing to drop: the arrays stay as they are
+    down(io->map, F.bad[fin ^ 1u], words), down(io->parent_out, F.parent, words), down(io->index_out, F.index, words);
+    down(io->depth_out, F.depth[fin], words), down(io->n_bad_out, F.bad[fin], words), down(io->status_out, F.status, n);
+    down(io->digest_out, F.dig, 8 * words), down(io->prev_out, F.prev, 8 * words);
+    waited = pow_ctx_stream_wait(ctx, "pow_test_pool_prune (map)", 100ull * n);
+    if (rc == POW_OK) rc = waited;
+    release(waited);
+    return rc;
+  }
+  const uint32_t cap = pow_pool_prune_cap(kept, pow_pool_live_first_cap(0, ctx->pool_first_cap));
+  const PowPoolLivePlan to = pow_pool_live_plan(cap);
+  step(hipMalloc(&to_base, to.words * sizeof(uint32_t)), "hipMalloc");
+  if (rc != POW_OK) {
+    release(POW_OK);
+    return rc;
+  }
+  const PowPoolDev T = pow_pool_live_dev(to_base, to, nullptr, kept, 0);
+  const size_t kw = (size_t)kept * sizeof(uint32_t);
+  step(hipMemsetAsync(T.ctl, 0, sizeof(PowPoolLiveCtl), ctx->stream), "reset");
+  if (kept) {
+    step(pow_launch_pool_prune_gather(ctx->stream, F, T, cap, fin), "K12e");
+    step(pow_launch_pool_prune_remap(ctx->stream, F, T, fin), "K12f");
+  } else if (io->map) {  // nothing marked: every node was dropped
+    step(hipMemsetD32Async((hipDeviceptr_t)F.next[0], (int)POW_POOL_NONE, n, ctx->stream), "reset");
+  }
+  down(&new_ctl, T.ctl, sizeof new_ctl), down(io->map, F.next[0], words);
+  down(io->parent_out, T.parent, kw), down(io->index_out, T.index, kw), down(io->depth_out, T.depth[fin], kw);
+  down(io->n_bad_out, T.bad[fin], kw), down(io->status_out, T.status, kept), down(io->digest_out, T.dig, 8 * kw);
+  down(io->prev_out, T.prev, 8 * kw);
+  waited = pow_ctx_stream_wait(ctx, "pow_test_pool_prune (gather)", 100ull * (n + 2ull * kept));
+  if (rc == POW_OK) rc = waited;
+  if (rc == POW_OK) {
+    if (io->best) *io->best = new_ctl.k10.best;
+    if (io->n_flagged) *io->n_flagged = new_ctl.k10.n_flagged;
+  }
+  release(waited);
+  return rc;
+}
+
+// What pow_test_pool_lift takes and gives.
+struct pow_test_lift_io {
+  const uint32_t* parent;  // n: a position below n, POW_POOL_ROOT or POW_POOL_NONE; the first `covered` closed under it
+  const uint32_t* depth;   // n: the nodes on the walk from each, itself included
+  uint32_t covered;        // the table covered this many nodes before the call (0: it is made from nothing)
+  uint32_t capacity;       // words of a row, n..POW_POOL_MAX_BLOCKS
+  uint32_t mode;           // 0: k ancestor queries (in0 = pos, in1 = steps); 1: k pairs (in0 = a, in1 = b);
+                           // 2: the chain of `tip`, k <= n answers
+  const uint32_t* in0;
+  const uint32_t* in1;
+  uint32_t tip;
+  size_t k;                // 0: the table alone, no query launch
+  uint32_t* out0;          // k answers (mode 1: at); mode 2: k answers and the length word behind them
+  uint32_t* out1;          // mode 1: back_a
+  uint32_t* out2;          // mode 1: back_b
+  uint32_t* launches;      // one word: the table's launches of the query call (the table at `covered` is not counted)
+  uint32_t* table;         // null, or pow_pool_lift_rows(n) x n words: row j at (j - 1) n
+};
+static_assert(sizeof(pow_test_lift_io) == 13 * 8, "tests/pool_deep_util.py LiftIO");
+
+// K13 (pow_pool_lift.hip) on a parent and a depth array of the caller's making,
+// with no pool: the table as a pool of `covered` nodes had it (K13a over its
+// rows, at that size), then pool_lift_update's launches for a pool of n nodes
+// (K13b for at most POW_POOL_LIFT_SMALL new nodes, else K13a per row over them;
+// then every new row over all nodes), then one query launch, K13c or K13d.  The
+// table is allocated at `capacity` words a row, as the pool's, and filled with
+// 0xEE bytes first: an entry no launch wrote shows in `table`, and as a value it
+// is past every size, so no walk takes it for a position.
+extern "C" int pow_test_pool_lift(pow_ctx* ctx, size_t n, const pow_test_lift_io* io) {
+  if (n > POW_POOL_MAX_BLOCKS) return fail(POW_EINVAL, "too many nodes (%zu > 2^20)", n);
+  if (!ctx || !io) return fail(POW_EINVAL, "null");
+  if (io->capacity < n || io->capacity > POW_POOL_MAX_BLOCKS)
+    return fail(POW_EINVAL, "capacity %u outside %zu..2^20", io->capacity, n);
+  if (io->covered > n) return fail(POW_EINVAL, "covered %u past the forest's %zu", io->covered, n);
+  if (io->mode > 2u) return fail(POW_EINVAL, "unknown mode %u", io->mode);
+  if (io->k > (io->mode == 2u ? n : (size_t)POW_POOL_MAX_BLOCKS))
+    return fail(POW_EINVAL, "too many queries (%zu > %zu)", io->k, io->mode == 2u ? n : (size_t)POW_POOL_MAX_BLOCKS);
+  if ((!io->parent || !io->depth) && n) return fail(POW_EINVAL, "null");
+  if (io->k && (!io->out0 || (io->mode != 2u && (!io->in0 || !io->in1)) || (io->mode == 1u && (!io->out1 || !io->out2))))
+    return fail(POW_EINVAL, "null");
+  for (size_t q = 0; q < io->k && io->mode != 2u; ++q)
+    if (io->in0[q] >= n || (io->mode == 1u && io->in1[q] >= n))
+      return fail(POW_EINVAL, "query %zu names a node past the forest's %zu", q, n);
+  if (io->mode == 2u && io->k && io->tip >= n) return fail(POW_EINVAL, "tip (node %u) past the forest's %zu", io->tip, n);
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t p = io->parent[i];
+    if (p >= n && p < POW_POOL_NONE) return fail(POW_EINVAL, "parent %u of node %zu is neither a node nor an end", p, i);
+    if (i < io->covered && p >= io->covered && p < n)
+      return fail(POW_EINVAL, "the first %u nodes are not closed under parent (node %zu, parent %u)", io->covered, i, p);
+  }
+  if (io->launches) *io->launches = 0;
+  if (n == 0) return POW_OK;
+  HIP_OK(hipSetDevice(ctx->device));
+  const uint32_t n32 = (uint32_t)n, cap = io->capacity, covered = io->covered, k = (uint32_t)io->k, m = n32 - covered;
+  const uint32_t have = pow_pool_lift_rows(covered), rows = pow_pool_lift_rows(n32);
+  const size_t words = (size_t)n32 * sizeof(uint32_t), kb = (size_t)k * sizeof(uint32_t);
+  const size_t up_words = std::max<size_t>((size_t)cap * pow_pool_lift_rows(cap), 1);
+  uint32_t* d_parent = nullptr;
+  uint32_t* d_depth = nullptr;
+  uint32_t* d_up = nullptr;
+  uint32_t* d_io = nullptr;  // in0, in1, then the results, as pool_lift_run lays them out
+  int rc = POW_OK;
+  auto step = [&](hipError_t e, const char* what) {
+    if (rc == POW_OK && e != hipSuccess) rc = fail(POW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
+  };
+  step(hipMalloc(&d_parent, words), "hipMalloc");
+  step(hipMalloc(&d_depth, words), "hipMalloc");
+  step(hipMalloc(&d_up, up_words * sizeof(uint32_t)), "hipMalloc");
+  step(hipMalloc(&d_io, (5 * (size_t)k + 1) * sizeof(uint32_t)), "hipMalloc");
+  uint32_t launches = 0;
+  uint64_t work = 0;
+  if (rc == POW_OK) {
+    step(hipMemsetAsync(d_up, 0xEE, up_words * sizeof(uint32_t), ctx->stream), "reset");
+    step(hipMemcpyAsync(d_parent, io->parent, words, hipMemcpyHostToDevice, ctx->stream), "copy in");
+    step(hipMemcpyAsync(d_depth, io->depth, words, hipMemcpyHostToDevice, ctx->stream), "copy in");
+    // the table a pool of `covered` nodes had
+    for (uint32_t j = 1; covered && j <= have; ++j)
+      step(pow_launch_pool_lift_row(ctx->stream, d_parent, d_up, cap, j, 0, covered, covered), "K13a");
+    work += (uint64_t)covered * have;
+    // pool_lift_update, stale when nothing was covered
+    if (m && have) {
+      if (m <= POW_POOL_LIFT_SMALL) {
+        step(pow_launch_pool_lift_small(ctx->stream, d_parent, d_up, cap, have, covered, n32), "K13b");
+        ++launches;
+      } else {
+        for (uint32_t j = 1; j <= have; ++j, ++launches)
+          step(pow_launch_pool_lift_row(ctx->stream, d_parent, d_up, cap, j, covered, m, n32), "K13a");
+      }
+      work += (uint64_t)m * have;
+    }
+    for (uint32_t j = have + 1u; j <= rows; ++j, ++launches)
+      step(pow_launch_pool_lift_row(ctx->stream, d_parent, d_up, cap, j, 0, n32, n32), "K13a");
+    work += (uint64_t)n32 * (rows - have);
+  }
+  if (rc == POW_OK && k) {
+    uint32_t* const d_in0 = d_io;
+    uint32_t* const d_in1 = d_io + k;
+    uint32_t* const d_out = d_in1 + k;
+    const PowLiftView v{d_parent, d_depth, d_up, cap, n32, pow_pool_rounds(n32)};
+    if (io->mode != 2u) {
+      step(hipMemcpyAsync(d_in0, io->in0, kb, hipMemcpyHostToDevice, ctx->stream), "copy in");
+      step(hipMemcpyAsync(d_in1, io->in1, kb, hipMemcpyHostToDevice, ctx->stream), "copy in");
+    }
+    if (io->mode == 1u) {
+      step(pow_launch_pool_lift_fork(ctx->stream, v, k, d_in0, d_in1, d_out, d_out + k, d_out + 2 * (size_t)k), "K13d");
+      step(hipMemcpyAsync(io->out0, d_out, kb, hipMemcpyDeviceToHost, ctx->stream), "copy out");
+      step(hipMemcpyAsync(io->out1, d_out + k, kb, hipMemcpyDeviceToHost, ctx->stream), "copy out");
+      step(hipMemcpyAsync(io->out2, d_out + 2 * (size_t)k, kb, hipMemcpyDeviceToHost, ctx->stream), "copy out");
+    } else {
+      const bool chain = io->mode == 2u;
+      step(pow_launch_pool_lift_ancestor(ctx->stream, v, k, chain ? nullptr : d_in0, d_in1, io->tip, d_out), "K13c");
+      step(hipMemcpyAsync(io->out0, d_out, kb + (chain ? sizeof(uint32_t) : 0), hipMemcpyDeviceToHost, ctx->stream), "copy out");
+    }
+  }
+  if (rc == POW_OK && io->table)
+    for (uint32_t j = 1; j <= rows; ++j)
+      step(hipMemcpyAsync(io->table + (size_t)(j - 1u) * n32, d_up + (size_t)(j - 1u) * cap, words, hipMemcpyDeviceToHost, ctx->stream),
+           "copy out");
+  // + 100 ns per node and launch
+  const int waited = pow_ctx_stream_wait(ctx, "pow_test_pool_lift", 100ull * (work + k + (io->table ? (uint64_t)n32 * rows : 0)));
+  if (rc == POW_OK) rc = waited;
+  if (rc == POW_OK && io->launches) *io->launches = launches;
+  if (waited == POW_OK || !ctx->wedged)  // after a watchdog the launches may still write
+    (void)hipFree(d_parent), (void)hipFree(d_depth), (void)hipFree(d_up), (void)hipFree(d_io);
   return rc;
 }

@@ -11,7 +11,13 @@
 //      level with a hand-off array, the wide form row by row, then the new
 //      rows over all blocks): the launches counted equal the plan's, the table
 //      equals the one built from nothing, and the queries are checked again;
-//   d. flat chains of exactly 64 and 65 blocks.
+//   d. flat chains of exactly 64 and 65 blocks;
+//   e. the pool's full depth against closed forms, since plain walks are
+//      quadratic there: lists of exactly 2^k and 2^k + 1 nodes for k = 7 .. 20
+//      (depth == 2^levels), a shuffled list of 2^20 with every row entry and
+//      every step count from its tip, four two-arm shapes of about 2^20 nodes,
+//      and the batches (2^19 - 100, 2^19 + 100) and (2^20 - 256, 2^20) through
+//      the batch model of c.
 // Every array is allocated at exactly its size, so ASan sees a read past it.
 #include <algorithm>
 #include <cstdint>
@@ -235,10 +241,183 @@ void flat_chain(uint32_t n) {
   check_queries(f, t, n * n, "flat chain");
 }
 
+// ---- the pool's full depth: up to POW_POOL_MAX_BLOCKS nodes, against closed forms (plain walks are quadratic here) ----
+
+// One list whose node at height h is order[h - 1] and whose last parent is
+// `end`.  The first `covered` heights take the positions below `covered`, the
+// rest those behind, each shuffled among themselves: the prefix is closed.
+struct List {
+  Forest f;
+  std::vector<uint32_t> order;
+  uint32_t end;
+};
+
+void shuffle(std::vector<uint32_t>& v, uint32_t lo, uint32_t hi) {
+  for (uint32_t i = hi; i > lo + 1; --i) std::swap(v[i - 1], v[lo + rnd(i - lo)]);
+}
+
+List shuffled_list(uint32_t n, uint32_t covered, uint32_t end) {
+  std::vector<uint32_t> order(n);
+  for (uint32_t i = 0; i < n; ++i) order[i] = i;
+  shuffle(order, 0, covered);
+  shuffle(order, covered, n);
+  Forest f(n);
+  for (uint32_t h = 0; h < n; ++h) f.parent.get()[order[h]] = h ? order[h - 1] : end, f.depth.get()[order[h]] = h + 1;
+  return List{std::move(f), std::move(order), end};
+}
+
+// The step counts where a level's bit comes or goes, around a walk of d blocks.
+std::vector<uint32_t> seam_steps(uint32_t d) {
+  std::vector<uint32_t> s = {0u, d - 2u, d - 1u, d, d + 1u, 0xFFFFFFFFu, 0xFFFFFFFEu};
+  for (uint32_t j = 0; j <= 20; ++j)
+    for (uint32_t x : {(1u << j) - 1u, 1u << j, (1u << j) + 1u}) s.push_back(x);
+  return s;
+}
+
+void check_list_rows(const List& l, const Table& t, const char* what) {
+  const uint32_t n = l.f.n;
+  for (uint32_t j = 1; j <= pow_pool_lift_rows(n); ++j)
+    for (uint32_t h = 0; h < n; ++h) {
+      const uint32_t want = h >= (1u << j) ? l.order[h - (1u << j)] : l.end, got = t.row(j)[l.order[h]];
+      CHECK(got == want, "%s of %u: row %u at height %u is %u, by the order %u", what, n, j, h + 1, got, want);
+    }
+}
+
+// every_step: every step count from the tip, else the seams only; from `sample`
+// random heights the seams; `pairs` fork points.
+void check_list_queries(const List& l, const Table& t, bool every_step, uint32_t sample, uint32_t pairs, const char* what) {
+  const uint32_t n = l.f.n;
+  const PowLiftView v{l.f.parent.get(), l.f.depth.get(), t.up.get(), t.cap, n, pow_pool_rounds(n)};
+  auto ancestor = [&](uint32_t h, uint32_t s) {  // from the node at height h + 1
+    const uint32_t got = pow_lift_ancestor(v, l.order[h], s), want = s <= h ? l.order[h - s] : l.end;
+    CHECK(got == want, "%s of %u: ancestor(height %u, %u) = %u, by the order %u", what, n, h + 1, s, got, want);
+  };
+  if (every_step)
+    for (uint32_t s = 0; s <= n + 1u; ++s) ancestor(n - 1u, s);
+  for (uint32_t s : seam_steps(n)) ancestor(n - 1u, s);
+  for (uint32_t q = 0; q < sample; ++q) {
+    const uint32_t h = q < 3 ? q % n : rnd(n);
+    for (uint32_t s : seam_steps(h + 1u)) ancestor(h, s);
+  }
+  for (uint32_t q = 0; q < pairs; ++q) {
+    const uint32_t ha = q == 0 ? n - 1u : rnd(n), hb = q < 2 ? 0u : q % 97u == 0 ? ha : rnd(n), lo = std::min(ha, hb);
+    uint32_t ba = 7, bb = 7;
+    const uint32_t got = pow_lift_fork(v, l.order[ha], l.order[hb], &ba, &bb);
+    CHECK(got == l.order[lo] && ba == ha - lo && bb == hb - lo, "%s of %u: fork(heights %u, %u) = %u (%u, %u)", what, n, ha + 1,
+          hb + 1, got, ba, bb);
+  }
+}
+
+// A list of exactly n nodes: depth == 2^levels when n is a power of two.
+void deep_chain(uint32_t n) {
+  const List l = shuffled_list(n, 0, n & 2u ? POW_POOL_NONE : POW_POOL_ROOT);
+  Table t(n);
+  CHECK(bring_up(t, l.f.parent.get(), n, true) == pow_pool_lift_rows(n), "launches of %u", n);
+  const PowLiftView v{l.f.parent.get(), l.f.depth.get(), t.up.get(), t.cap, n, pow_pool_rounds(n)};
+  const uint32_t tip = l.order[n - 1];
+  CHECK(l.f.depth.get()[tip] == n, "depth of the tip");
+  CHECK(pow_lift_ancestor(v, tip, n - 1) == l.order[0], "list of %u: the root", n);
+  CHECK(pow_lift_ancestor(v, tip, n) == l.end, "list of %u: the end", n);
+  CHECK(pow_lift_ancestor(v, tip, 0xFFFFFFFFu) == l.end, "list of %u: the end from afar", n);
+  check_list_queries(l, t, false, 200, 2000, "list");
+}
+
+void deep_list(uint32_t n) {
+  const List l = shuffled_list(n, 0, POW_POOL_ROOT);
+  Table t(n);
+  bring_up(t, l.f.parent.get(), n, true);
+  check_list_rows(l, t, "list");
+  check_list_queries(l, t, true, 2000, 200000, "every step");
+}
+
+// A list over the first `covered` positions, its table as a pool of that size
+// had it, then the rest as one batch: the launches, every entry against the
+// table made from nothing and against the closed form, then the queries.
+void deep_extension(uint32_t covered, uint32_t n) {
+  const List l = shuffled_list(n, covered, POW_POOL_ROOT);
+  Table fed(n);
+  {
+    const Forest g = prefix(l.f, covered);  // arrays of exactly `covered`
+    bring_up(fed, g.parent.get(), covered, true);
+  }
+  const uint32_t got = bring_up(fed, l.f.parent.get(), n, false), want = pow_pool_lift_launches(covered, n, false);
+  CHECK(got == want, "from %u to %u blocks: %u launches, the plan says %u", covered, n, got, want);
+  Table fresh(n);
+  bring_up(fresh, l.f.parent.get(), n, true);
+  for (uint32_t j = 1; j <= pow_pool_lift_rows(n); ++j)
+    for (uint32_t i = 0; i < n; ++i)
+      CHECK(fed.row(j)[i] == fresh.row(j)[i], "from %u to %u: row %u of block %u is %u, from nothing %u", covered, n, j, i,
+            fed.row(j)[i], fresh.row(j)[i]);
+  check_list_rows(l, fed, "extended");
+  check_list_queries(l, fed, false, 500, 20000, "extended");
+}
+
+// Two lists that share a trunk, positions shuffled: the fork point of a pair is
+// the lower node if both lie on one line, else the trunk's top.
+void deep_arms(uint32_t trunk, uint32_t arm_a, uint32_t arm_b, uint32_t pairs) {
+  const uint32_t n = trunk + arm_a + arm_b;
+  std::vector<uint32_t> perm(n);
+  for (uint32_t i = 0; i < n; ++i) perm[i] = i;
+  shuffle(perm, 0, n);
+  Forest f(n);
+  std::vector<uint8_t> side(n, 0);
+  for (uint32_t h = 0; h < trunk + arm_a; ++h) {  // line A: the trunk, then arm A
+    f.parent.get()[perm[h]] = h ? perm[h - 1] : POW_POOL_ROOT, f.depth.get()[perm[h]] = h + 1;
+    if (h >= trunk) side[perm[h]] = 1;
+  }
+  for (uint32_t k = 0; k < arm_b; ++k) {
+    const uint32_t i = perm[trunk + arm_a + k];
+    f.parent.get()[i] = k ? perm[trunk + arm_a + k - 1] : perm[trunk - 1], f.depth.get()[i] = trunk + k + 1, side[i] = 2;
+  }
+  Table t(n);
+  bring_up(t, f.parent.get(), n, true);
+  const PowLiftView v{f.parent.get(), f.depth.get(), t.up.get(), t.cap, n, pow_pool_rounds(n)};
+  const uint32_t top = perm[trunk - 1];
+  auto fork = [&](uint32_t a, uint32_t b) {
+    const uint32_t da = f.depth.get()[a], db = f.depth.get()[b];
+    const bool across = side[a] && side[b] && side[a] != side[b];
+    const uint32_t at = across ? top : da <= db ? a : b, to = across ? trunk : std::min(da, db);
+    uint32_t ba = 7, bb = 7;
+    const uint32_t got = pow_lift_fork(v, a, b, &ba, &bb);
+    CHECK(got == at && ba == da - to && bb == db - to, "arms %u + %u, %u: fork(%u, %u) = %u (%u, %u), closed form %u (%u, %u)", trunk,
+          arm_a, arm_b, a, b, got, ba, bb, at, da - to, db - to);
+  };
+  auto node_a = [&](uint32_t h) { return perm[trunk + h - 1]; };          // arm A at height h (1 .. arm_a) above the trunk
+  auto node_b = [&](uint32_t h) { return perm[trunk + arm_a + h - 1]; };  // arm B
+  std::vector<uint32_t> ha, hb;
+  for (uint32_t s : seam_steps(arm_a))
+    if (s >= 1 && s <= arm_a) ha.push_back(s);
+  for (uint32_t s : seam_steps(arm_b))
+    if (s >= 1 && s <= arm_b) hb.push_back(s);
+  for (uint32_t x : ha)
+    for (uint32_t y : hb) fork(node_a(x), node_b(y)), fork(node_b(y), node_a(x));
+  for (uint32_t s : seam_steps(trunk))
+    if (s >= 1 && s <= trunk) {  // one line: against the trunk
+      fork(node_a(arm_a), perm[s - 1]), fork(perm[s - 1], node_b(arm_b)), fork(perm[s - 1], perm[s - 1]);
+      if (s > 1) fork(perm[s - 1], perm[s - 2]), fork(perm[s - 2], perm[s - 1]);
+    }
+  for (uint32_t q = 0; q < pairs; ++q) fork(rnd(n), rnd(n));
+  for (uint32_t i = 0; i < n; i += 1 + n / 5000) {  // a == b, and a block against its parent
+    fork(i, i);
+    if (f.parent.get()[i] < n) fork(i, f.parent.get()[i]), fork(f.parent.get()[i], i);
+  }
+}
+
 }  // namespace
 
 int main() {
   plan_by_hand();
+  for (uint32_t k = 7; k <= 20; ++k) {
+    deep_chain(1u << k);
+    if (k < 20) deep_chain((1u << k) + 1u);  // 2^20 + 1 is past POW_POOL_MAX_BLOCKS
+  }
+  deep_list(1u << 20);
+  deep_arms(1u << 19, 1u << 18, (1u << 18) - 1u, 50000);
+  deep_arms(1u, 1u << 19, (1u << 19) - 2u, 50000);
+  deep_arms((1u << 19) + 1u, 1u, (1u << 19) - 2u, 50000);
+  deep_arms((1u << 20) - 2u, 1u, 1u, 50000);
+  deep_extension((1u << 19) - 100u, (1u << 19) + 100u);
+  deep_extension((1u << 20) - 256u, 1u << 20);
   for (uint32_t n : {1u, 2u, 3u, 4u, 5u, 64u, 65u}) flat_chain(n);
   forest_in_batches({0, 1, 2, 3, 4, 5, 261, 518, 519, 775, 1032, 1033}, 4000);  // + 1, + 256, + 257, across 512 and 1,024
   forest_in_batches({0, 300, 556, 813}, 4000);                                  // the GPU test's seam

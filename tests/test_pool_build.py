@@ -142,7 +142,7 @@ def test_insert_never_spins():
 def test_switch_and_rank_hook_only_in_the_test_library():
     shipped = open(_lib.LIB_PATH, "rb").read()
     test = open(_lib.TEST_LIB_PATH, "rb").read()
-    for s in (b"POW_POOL_SLOTS_LOG2", b"pow_test_pool_rank"):
+    for s in (b"POW_POOL_SLOTS_LOG2", b"pow_test_pool_rank", b"pow_test_pool_prune", b"pow_test_pool_lift"):
         assert s not in shipped and s in test, s
     for f in os.listdir(CSRC):
         p = os.path.join(CSRC, f)

@@ -33,7 +33,8 @@ def test_the_name_is_exported():
     for text in ("#define POW_POOL_MAX_BLOCKS (1u << 20)", "#define POW_POOL_ROOT 0xFFFFFFFFu",
                  "#define POW_POOL_NONE 0xFFFFFFFEu"):
         assert text in header
-    assert not hasattr(_lib.load(), "pow_test_pool_rank") and _lib.load(test_hooks=True).pow_test_pool_rank
+    for hook in ("pow_test_pool_rank", "pow_test_pool_prune", "pow_test_pool_lift"):
+        assert not hasattr(_lib.load(), hook) and getattr(_lib.load(test_hooks=True), hook) and hook not in _lib.EXPORTS
 
 
 def test_plan_under_sanitizers(tmp_path):

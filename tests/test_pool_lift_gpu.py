@@ -4,7 +4,8 @@ tests/test_pool_lift_host.py holds against plain walks).  After every query call
 every result is compared with the mirror's, the launches with the plan's
 (pow_pool_lift_launches restated here, plus the query's own), and lift_info()
 with what the history of the pool implies.  The pools are pool_util's, built
-on the CPU with hashlib."""
+on the CPU with hashlib, so they stop near 2,000 blocks (11 levels): levels 12
+to 19 and the chain call at 2^20 lanes are in tests/test_pool_deep_gpu.py."""
 import ctypes
 import random
 

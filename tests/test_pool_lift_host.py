@@ -3,7 +3,7 @@ only): the Python mirror (block.BlockPool.ancestor, .fork_point and .chain,
 the GPU tests' yardstick) against an independent statement; the export list
 and the null-pool check of the C calls; and the host plan with the kernels'
 own per-lane walks in tests/pool_lift_plan_unit.cpp, a process of its own
-under sanitizers."""
+under sanitizers, up to the pool's limit of 2^20 blocks."""
 import ctypes
 import os
 import random
@@ -175,4 +175,4 @@ def test_lift_plan_unit_under_sanitizers(tmp_path):
     print(r.stdout, r.stderr)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     assert " checks, 0 failed" in r.stdout, r.stdout
-    assert int(r.stdout.split(" checks, 0 failed")[0].split()[-1]) > 100_000  # the forests ran
+    assert int(r.stdout.split(" checks, 0 failed")[0].split()[-1]) > 80_000_000  # the forests and the lists of 2^20 ran

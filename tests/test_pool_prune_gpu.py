@@ -4,7 +4,8 @@ against block.index_blocks).  After every call the whole pool is compared with
 the mirror; after every prune also with pow_index_blocks over the surviving
 structs, pow_pool_find over the survivors' and the dropped names, and the
 launches with the plan's.  The pools are pool_util's, built on the CPU with
-hashlib."""
+hashlib, so the largest has 65,537 blocks (257 partials): the scan's cross-wave
+half, rounds 18 to 20 and 4,096 workgroups are in tests/test_pool_deep_gpu.py."""
 import ctypes
 import os
 import re
