@@ -723,58 +723,6 @@ int pow_verify_chains(pow_ctx* ctx, const pow_block* blocks, const uint32_t* len
   return clean ? 1 : 0;
 }
 
-// K10 over a pool: K10a tile by tile into the call's arrays, which stay on the
-// device, then the table, the join, the rounds and the fork choice queued back
-// to back behind one reset, with one bounded wait and one set of copies down.
-int pow_index_blocks(pow_ctx* ctx, const pow_block* pool, size_t n, unsigned diff_bits, uint8_t* status,
-                     uint32_t* parent, uint32_t* depth, uint32_t* n_bad, size_t* best) {
-  if (diff_bits > 256) return fail(POW_EINVAL, "diff_bits %u > 256", diff_bits);
-  if (n > POW_POOL_MAX_BLOCKS) return fail(POW_EINVAL, "pool too large (%zu blocks > %u)", n, POW_POOL_MAX_BLOCKS);
-  if (!ctx || (!pool && n)) return fail(POW_EINVAL, "null");
-  ctx->stats = pow_stats{};
-  if (best) *best = SIZE_MAX;
-  if (n == 0) return 1;
-  if (int rc = set_dev(ctx)) return rc;
-  if (int rc = ensure_verify_tile(ctx, std::min(n, kVerifyTile))) return rc;
-  const PowPoolPlan plan = pow_pool_plan((uint32_t)n, ctx->pool_slots_log2);
-  RESERVE(ctx->d_pool, plan.words);
-  RESERVE(ctx->h_pool, 1);
-  const PowPoolDev D = pow_pool_dev(ctx->d_pool.p, plan, (uint32_t)n);
-  if (int rc = verify_tiles(
-          ctx, pool, n, "pool audit kernel", [](const VerifyTile&) -> int { return POW_OK; },
-          [&](const VerifyTile& t) -> int {
-            HIP_OK(pow_launch_pool_audit(ctx->stream, (const uint32_t*)ctx->d_vblk.p, (uint32_t)t.tn, (uint32_t)t.t0,
-                                         diff_bits, D));
-            HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
-            return POW_OK;
-          },
-          [](const VerifyTile&) {}))
-    return rc;
-  if (int rc = timed_begin(ctx)) return rc;
-  HIP_OK(hipMemsetAsync(D.ctl, 0, sizeof(PowPoolCtl), ctx->stream));
-  HIP_OK(hipMemsetAsync(D.table, 0xFF, (size_t)D.slots * sizeof(uint32_t), ctx->stream));  // every call: no stale slot
-  HIP_OK(pow_launch_pool_insert(ctx->stream, D));
-  HIP_OK(pow_launch_pool_join(ctx->stream, D));
-  for (uint32_t r = 0; r < plan.rounds; ++r) HIP_OK(pow_launch_pool_round(ctx->stream, D, r));
-  const uint32_t last = plan.rounds & 1u;  // the buffers the last round wrote
-  HIP_OK(pow_launch_pool_finish(ctx->stream, D, last));
-  HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
-  PowPoolCtl* const ctl = ctx->h_pool.p;
-  HIP_OK(hipMemcpyAsync(ctl, D.ctl, sizeof(PowPoolCtl), hipMemcpyDeviceToHost, ctx->stream));
-  if (status) HIP_OK(hipMemcpyAsync(status, D.status, n, hipMemcpyDeviceToHost, ctx->stream));
-  if (parent) HIP_OK(hipMemcpyAsync(parent, D.parent, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (depth) HIP_OK(hipMemcpyAsync(depth, D.depth[last], n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (n_bad) HIP_OK(hipMemcpyAsync(n_bad, D.bad[last], n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  // + 100 ns per block and round
-  if (int rc = timed_end(ctx, "pool index kernels", 100ull * n * (plan.rounds + 1u), 3u + plan.rounds, &ctx->stats))
-    return rc;
-  if (ctl->err) return fail(POW_EHIP, "pool table overflow (%zu blocks, %u slots)", n, D.slots);
-  if (best && ctl->best) *best = (size_t)(uint32_t)~(uint32_t)ctl->best;
-  return ctl->n_flagged == 0 ? 1 : 0;
-}
-
-// ---- pow_pool (K11): K10's arrays and table resident, fed in batches ----
-
 }  // extern "C"
 
 // The binary-lifting table of a pool's ancestry queries (K13), made at the
@@ -808,7 +756,7 @@ struct pow_pool {
   PowPoolLivePlan plan{};      // the arrays' offsets at the present capacity
   DevBuf<uint32_t> d_arr;      // the arrays (plan.words)
   DevBuf<uint32_t> d_table;    // the table (slots)
-  DevBuf<uint32_t> d_old_arr, d_old_table;  // what an add that grew them left behind, until its wait has passed
+  DevBuf<uint32_t> d_old_arr, d_old_table;  // what a call that replaced them left behind, until its wait has passed
   DevBuf<uint32_t> d_find;     // pow_pool_find: 16 words per name up, then one per name down
   HostBuf<PowPoolLiveCtl> h_ctl;  // the pinned twin of the control words
   pow_pool_info info{};
@@ -819,7 +767,117 @@ struct pow_pool {
   }
 };
 
+// ---- the shared launch sequences (declared in pow_ctx.h) ----
+
+#define QUEUE_OK(expr)                    \
+  do {                                    \
+    const hipError_t e_ = (expr);         \
+    if (e_ != hipSuccess) return e_;      \
+  } while (0)
+
+hipError_t pow_queue_pool_rank(hipStream_t stream, const PowPoolDev& D, uint32_t rounds) {
+  for (uint32_t r = 0; r < rounds; ++r) QUEUE_OK(pow_launch_pool_round(stream, D, r));
+  return pow_launch_pool_finish(stream, D, rounds & 1u);  // the buffers the last round wrote
+}
+
+// The marks lie in depth[1 - fin], every block's own position in bad[1 - fin],
+// the partials' scan in next[1].
+hipError_t pow_queue_pool_mark(hipStream_t stream, const PowPoolDev& D, uint32_t fin, const uint32_t* d_tips,
+                               uint32_t n_tips, uint32_t min_index, uint32_t flags) {
+  const uint32_t rounds = pow_pool_rounds(D.n);
+  QUEUE_OK(hipMemsetAsync(D.depth[fin ^ 1u], 0, (size_t)((D.n + 3u) / 4u) * sizeof(uint32_t), stream));
+  QUEUE_OK(pow_launch_pool_prune_seed(stream, D, fin, d_tips, n_tips, min_index, flags));
+  for (uint32_t r = 0; r < rounds; ++r) QUEUE_OK(pow_launch_pool_prune_round(stream, D, fin, r));
+  QUEUE_OK(pow_launch_pool_prune_count(stream, D, fin));
+  return pow_launch_pool_prune_scan(stream, D);
+}
+
+hipError_t pow_queue_pool_compact(hipStream_t stream, const PowPoolDev& F, const PowPoolDev& T, uint32_t cap,
+                                  uint32_t fin, bool want_map) {
+  QUEUE_OK(hipMemsetAsync(T.ctl, 0, sizeof(PowPoolLiveCtl), stream));
+  if (T.table) QUEUE_OK(hipMemsetAsync(T.table, 0xFF, (size_t)T.slots * sizeof(uint32_t), stream));
+  if (T.n) {
+    QUEUE_OK(pow_launch_pool_prune_gather(stream, F, T, cap, fin));
+    QUEUE_OK(pow_launch_pool_prune_remap(stream, F, T, fin));
+    if (T.table) QUEUE_OK(pow_launch_pool_insert(stream, T));  // K10b: every named survivor
+  } else if (want_map) {  // nothing marked: every block was dropped
+    QUEUE_OK(hipMemsetD32Async((hipDeviceptr_t)F.next[0], (int)POW_POOL_NONE, F.n, stream));
+  }
+  return hipSuccess;
+}
+
+hipError_t pow_queue_pool_lift(hipStream_t stream, const uint32_t* parent, uint32_t* up, uint32_t capacity,
+                               uint32_t covered, uint32_t n, bool stale, uint32_t* launches, uint64_t* work) {
+  const uint32_t m = n - covered;
+  const uint32_t have = stale ? 0u : pow_pool_lift_rows(covered), rows = pow_pool_lift_rows(n);
+  if (m && have) {
+    if (m <= POW_POOL_LIFT_SMALL) {
+      QUEUE_OK(pow_launch_pool_lift_small(stream, parent, up, capacity, have, covered, n));
+      ++*launches;
+    } else {
+      for (uint32_t j = 1; j <= have; ++j, ++*launches)
+        QUEUE_OK(pow_launch_pool_lift_row(stream, parent, up, capacity, j, covered, m, n));
+    }
+    *work += m * (uint64_t)have;
+  }
+  for (uint32_t j = have + 1u; j <= rows; ++j, ++*launches)
+    QUEUE_OK(pow_launch_pool_lift_row(stream, parent, up, capacity, j, 0, n, n));
+  *work += (uint64_t)n * (rows - have);
+  return hipSuccess;
+}
+
 extern "C" {
+
+// K10 over a pool: K10a tile by tile into the call's arrays, which stay on the
+// device, then the table, the join, the rounds and the fork choice queued back
+// to back behind one reset, with one bounded wait and one set of copies down.
+int pow_index_blocks(pow_ctx* ctx, const pow_block* pool, size_t n, unsigned diff_bits, uint8_t* status,
+                     uint32_t* parent, uint32_t* depth, uint32_t* n_bad, size_t* best) {
+  if (diff_bits > 256) return fail(POW_EINVAL, "diff_bits %u > 256", diff_bits);
+  if (n > POW_POOL_MAX_BLOCKS) return fail(POW_EINVAL, "pool too large (%zu blocks > %u)", n, POW_POOL_MAX_BLOCKS);
+  if (!ctx || (!pool && n)) return fail(POW_EINVAL, "null");
+  ctx->stats = pow_stats{};
+  if (best) *best = SIZE_MAX;
+  if (n == 0) return 1;
+  if (int rc = set_dev(ctx)) return rc;
+  if (int rc = ensure_verify_tile(ctx, std::min(n, kVerifyTile))) return rc;
+  const PowPoolPlan plan = pow_pool_plan((uint32_t)n, ctx->pool_slots_log2);
+  RESERVE(ctx->d_pool, plan.words);
+  RESERVE(ctx->h_pool, 1);
+  const PowPoolDev D = pow_pool_dev(ctx->d_pool.p, plan, (uint32_t)n);
+  if (int rc = verify_tiles(
+          ctx, pool, n, "pool audit kernel", [](const VerifyTile&) -> int { return POW_OK; },
+          [&](const VerifyTile& t) -> int {
+            HIP_OK(pow_launch_pool_audit(ctx->stream, (const uint32_t*)ctx->d_vblk.p, (uint32_t)t.tn, (uint32_t)t.t0,
+                                         diff_bits, D));
+            HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+            return POW_OK;
+          },
+          [](const VerifyTile&) {}))
+    return rc;
+  if (int rc = timed_begin(ctx)) return rc;
+  HIP_OK(hipMemsetAsync(D.ctl, 0, sizeof(PowPoolCtl), ctx->stream));
+  HIP_OK(hipMemsetAsync(D.table, 0xFF, (size_t)D.slots * sizeof(uint32_t), ctx->stream));  // every call: no stale slot
+  HIP_OK(pow_launch_pool_insert(ctx->stream, D));
+  HIP_OK(pow_launch_pool_join(ctx->stream, D));
+  HIP_OK(pow_queue_pool_rank(ctx->stream, D, plan.rounds));
+  const uint32_t last = plan.rounds & 1u;  // the buffers the last round wrote
+  HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+  PowPoolCtl* const ctl = ctx->h_pool.p;
+  HIP_OK(hipMemcpyAsync(ctl, D.ctl, sizeof(PowPoolCtl), hipMemcpyDeviceToHost, ctx->stream));
+  if (status) HIP_OK(hipMemcpyAsync(status, D.status, n, hipMemcpyDeviceToHost, ctx->stream));
+  if (parent) HIP_OK(hipMemcpyAsync(parent, D.parent, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (depth) HIP_OK(hipMemcpyAsync(depth, D.depth[last], n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (n_bad) HIP_OK(hipMemcpyAsync(n_bad, D.bad[last], n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  // + 100 ns per block and round
+  if (int rc = timed_end(ctx, "pool index kernels", 100ull * n * (plan.rounds + 1u), 3u + plan.rounds, &ctx->stats))
+    return rc;
+  if (ctl->err) return fail(POW_EHIP, "pool table overflow (%zu blocks, %u slots)", n, D.slots);
+  if (best && ctl->best) *best = (size_t)(uint32_t)~(uint32_t)ctl->best;
+  return ctl->n_flagged == 0 ? 1 : 0;
+}
+
+// ---- pow_pool (K11): K10's arrays and table resident, fed in batches ----
 
 // What every pool call that reaches the GPU opens with, behind its argument
 // checks: a pool whose add failed, or whose context is wedged, fails at once.
@@ -853,15 +911,23 @@ static int pool_alloc(pow_pool* p, uint32_t cap, uint32_t slots) {
   return stream_wait_for(ctx, "pool reset", 0);
 }
 
+// A buffer replaced while queued work may still read it: `old` takes over what
+// `d_new` held and stays allocated until the caller's wait has passed (the
+// caller releases it there); `d_new` is made afresh with `n` words.
+static int pool_retire(DevBuf<uint32_t>& d_new, DevBuf<uint32_t>& old, size_t n) {
+  old = d_new;
+  d_new = DevBuf<uint32_t>{};
+  RESERVE(d_new, n);
+  return POW_OK;
+}
+
 // Room for `need` blocks: arrays of twice the capacity (pow_pool_live_grow),
 // filled device to device with what the pool's blocks have.  The arrays left
 // behind stay allocated until the add's wait has passed (d_old_arr).
 static int pool_grow(pow_pool* p, uint32_t need) {
   pow_ctx* const ctx = p->ctx;
   const PowPoolLivePlan from = p->plan, to = pow_pool_live_plan(pow_pool_live_grow(from.cap, need));
-  p->d_old_arr = p->d_arr;
-  p->d_arr = DevBuf<uint32_t>{};
-  RESERVE(p->d_arr, to.words);
+  if (int rc = pool_retire(p->d_arr, p->d_old_arr, to.words)) return rc;
   const uint32_t* const src = p->d_old_arr.p;
   uint32_t* const dst = p->d_arr.p;
   const size_t n = p->size, bytes = (n + 3) / 4;
@@ -933,11 +999,8 @@ int pow_pool_add(pow_pool* p, const pow_block* blocks, size_t m, pow_pool_info* 
     if (int rc = pool_grow(p, n)) return rc;
   const uint32_t slots = pow_pool_live_slots(p->slots, n);
   const bool rehashed = slots != p->slots;
-  if (slots > p->d_table.cap) {
-    p->d_old_table = p->d_table;
-    p->d_table = DevBuf<uint32_t>{};
-    RESERVE(p->d_table, slots);
-  }
+  if (slots > p->d_table.cap)
+    if (int rc = pool_retire(p->d_table, p->d_old_table, slots)) return rc;
   p->slots = slots;
   const PowPoolDev D = pool_dev(p, n);
   if (int rc = verify_tiles(
@@ -977,8 +1040,7 @@ int pow_pool_add(pow_pool* p, const pow_block* blocks, size_t m, pow_pool_info* 
     HIP_OK(pow_launch_pool_live_strip(ctx->stream, D));
     HIP_OK(hipMemsetAsync(d_ctl, 0, sizeof(PowPoolLiveCtl), ctx->stream));
     HIP_OK(pow_launch_pool_join(ctx->stream, D));
-    for (uint32_t r = 0; r < all; ++r) HIP_OK(pow_launch_pool_round(ctx->stream, D, r));
-    HIP_OK(pow_launch_pool_finish(ctx->stream, D, all & 1u));
+    HIP_OK(pow_queue_pool_rank(ctx->stream, D, all));
     HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
     HIP_OK(hipMemcpyAsync(ctl, d_ctl, sizeof(PowPoolLiveCtl), hipMemcpyDeviceToHost, ctx->stream));
     if (int rc = timed_end(ctx, "pool re-rank kernels", 100ull * n * (all + 3ull), 3u + all, &ctx->stats)) return rc;
@@ -1050,9 +1112,8 @@ static int pool_mark_args(const pow_pool* p, const uint32_t* tips, size_t n_tips
 }
 
 // One timed section over a pool that holds blocks: the tips up (d_find), the
-// marks' reset, K12a, the rounds of K12b, K12c and K12d, then the control words
-// and, if asked for, the marks down.  The marks lie in depth[1 - fin], every
-// block's own position in bad[1 - fin], the partials' scan in next[1].
+// mark's launches (pow_queue_pool_mark), then the control words and, if asked
+// for, the marks down.
 static int pool_mark_run(pow_pool* p, const uint32_t* tips, uint32_t n_tips, uint32_t min_index, unsigned flags,
                          uint8_t* on, uint32_t* marked) {
   pow_ctx* const ctx = p->ctx;
@@ -1062,11 +1123,7 @@ static int pool_mark_run(pow_pool* p, const uint32_t* tips, uint32_t n_tips, uin
   if (n_tips) HIP_OK(hipMemcpyAsync(p->d_find.p, tips, n_tips * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
   PowPoolLiveCtl* const ctl = p->h_ctl.p;
   if (int rc = timed_begin(ctx)) return rc;
-  HIP_OK(hipMemsetAsync(D.depth[p->fin ^ 1u], 0, (size_t)((n + 3u) / 4u) * sizeof(uint32_t), ctx->stream));
-  HIP_OK(pow_launch_pool_prune_seed(ctx->stream, D, p->fin, p->d_find.p, n_tips, min_index, flags));
-  for (uint32_t r = 0; r < rounds; ++r) HIP_OK(pow_launch_pool_prune_round(ctx->stream, D, p->fin, r));
-  HIP_OK(pow_launch_pool_prune_count(ctx->stream, D, p->fin));
-  HIP_OK(pow_launch_pool_prune_scan(ctx->stream, D));
+  HIP_OK(pow_queue_pool_mark(ctx->stream, D, p->fin, p->d_find.p, n_tips, min_index, flags));
   HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
   HIP_OK(hipMemcpyAsync(ctl, D.ctl, sizeof(PowPoolLiveCtl), hipMemcpyDeviceToHost, ctx->stream));
   if (on) HIP_OK(hipMemcpyAsync(on, D.depth[p->fin ^ 1u], n, hipMemcpyDeviceToHost, ctx->stream));
@@ -1118,24 +1175,12 @@ int pow_pool_prune(pow_pool* p, const uint32_t* tips, size_t n_tips, uint32_t mi
     const uint32_t cap = pow_pool_prune_cap(kept, pow_pool_live_first_cap(0, ctx->pool_first_cap));
     const uint32_t slots = pow_pool_prune_slots(cap, kept, ctx->pool_slots_log2);
     const PowPoolLivePlan to = pow_pool_live_plan(cap);
-    p->d_old_arr = p->d_arr;
-    p->d_arr = DevBuf<uint32_t>{};
-    RESERVE(p->d_arr, to.words);
-    p->d_old_table = p->d_table;
-    p->d_table = DevBuf<uint32_t>{};
-    RESERVE(p->d_table, slots);
+    if (int rc = pool_retire(p->d_arr, p->d_old_arr, to.words)) return rc;
+    if (int rc = pool_retire(p->d_table, p->d_old_table, slots)) return rc;
     const PowPoolDev T = pow_pool_live_dev(p->d_arr.p, to, p->d_table.p, kept, slots);
     PowPoolLiveCtl* const ctl = p->h_ctl.p;
     if (int rc = timed_begin(ctx)) return rc;
-    HIP_OK(hipMemsetAsync(T.ctl, 0, sizeof(PowPoolLiveCtl), ctx->stream));
-    HIP_OK(hipMemsetAsync(T.table, 0xFF, (size_t)slots * sizeof(uint32_t), ctx->stream));
-    if (kept) {
-      HIP_OK(pow_launch_pool_prune_gather(ctx->stream, F, T, cap, p->fin));
-      HIP_OK(pow_launch_pool_prune_remap(ctx->stream, F, T, p->fin));
-      HIP_OK(pow_launch_pool_insert(ctx->stream, T));  // K10b: every named survivor
-    } else if (map) {  // nothing marked: every block was dropped
-      HIP_OK(hipMemsetD32Async((hipDeviceptr_t)F.next[0], (int)POW_POOL_NONE, n, ctx->stream));
-    }
+    HIP_OK(pow_queue_pool_compact(ctx->stream, F, T, cap, p->fin, map != nullptr));
     HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
     HIP_OK(hipMemcpyAsync(ctl, T.ctl, sizeof(PowPoolLiveCtl), hipMemcpyDeviceToHost, ctx->stream));
     if (map) HIP_OK(hipMemcpyAsync(map, F.next[0], (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -1171,31 +1216,15 @@ static int pool_lift_args(const pow_pool* p, const uint32_t* a, const uint32_t* 
 
 // The table brought up to date with the pool, inside the caller's timed
 // section: made from nothing if `stale`, otherwise extended over the blocks
-// behind the first `covered` (pow_pool_lift_launches states the launches).
-// *work: the lanes of those launches, for the watchdog.
+// behind the first `covered` (pow_queue_pool_lift).  *launches: the launches
+// it queued; *work: their lanes, for the watchdog.  Both start at the caller's 0.
 static int pool_lift_update(pow_pool* p, uint32_t covered, bool stale, uint32_t* launches, uint64_t* work) {
-  pow_ctx* const ctx = p->ctx;
   PowPoolLift& t = p->lift;
-  const uint32_t n = p->size, m = n - covered;
-  const uint32_t have = stale ? 0u : pow_pool_lift_rows(covered), rows = pow_pool_lift_rows(n);
-  const uint32_t* const parent = pool_dev(p, n).parent;
-  *launches = pow_pool_lift_launches(covered, n, stale);
-  *work = 0;
-  if (m && have) {
-    if (m <= POW_POOL_LIFT_SMALL) {
-      HIP_OK(pow_launch_pool_lift_small(ctx->stream, parent, t.d_up.p, t.capacity, have, covered, n));
-      *work += m * (uint64_t)have;
-    } else {
-      for (uint32_t j = 1; j <= have; ++j)
-        HIP_OK(pow_launch_pool_lift_row(ctx->stream, parent, t.d_up.p, t.capacity, j, covered, m, n));
-      *work += m * (uint64_t)have;
-    }
-  }
-  for (uint32_t j = have + 1u; j <= rows; ++j)
-    HIP_OK(pow_launch_pool_lift_row(ctx->stream, parent, t.d_up.p, t.capacity, j, 0, n, n));
-  *work += (uint64_t)n * (rows - have);
+  const uint32_t n = p->size;
+  HIP_OK(pow_queue_pool_lift(p->ctx->stream, pool_dev(p, n).parent, t.d_up.p, t.capacity, covered, n, stale, launches,
+                             work));
   t.rebuilt = stale ? 1u : 0u;
-  t.extended = stale ? 0u : m;
+  t.extended = stale ? 0u : n - covered;
   return POW_OK;
 }
 

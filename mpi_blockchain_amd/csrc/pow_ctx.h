@@ -488,6 +488,23 @@ hipError_t pow_launch_pool_lift_ancestor(hipStream_t stream, const PowLiftView& 
                                          const uint32_t* steps, uint32_t tip, uint32_t* out);
 hipError_t pow_launch_pool_lift_fork(hipStream_t stream, const PowLiftView& v, uint32_t k, const uint32_t* a,
                                      const uint32_t* b, uint32_t* at, uint32_t* back_a, uint32_t* back_b);
+// The launch sequences of K10, K12 and K13 that more than one caller queues (pow_api.cpp), each stated once: the
+// library's calls and the test library's hooks run these.  As the wrappers above: a stream and views, the first
+// failing hipError_t; none waits, records an event or copies to the host.
+// `rounds` x K10d, then K10e on the buffers the last round wrote (rounds & 1).
+hipError_t pow_queue_pool_rank(hipStream_t stream, const PowPoolDev& D, uint32_t rounds);
+// The marks' reset (depth[fin ^ 1]), K12a, pow_pool_rounds(D.n) x K12b, K12c and K12d.
+hipError_t pow_queue_pool_mark(hipStream_t stream, const PowPoolDev& D, uint32_t fin, const uint32_t* d_tips,
+                               uint32_t n_tips, uint32_t min_index, uint32_t flags);
+// The reset of T's control words and of its table, if it has one; then, if T keeps blocks, K12e, K12f and (with a
+// table) K10b over T; otherwise, if want_map, F.next[0] filled with POW_POOL_NONE.
+hipError_t pow_queue_pool_compact(hipStream_t stream, const PowPoolDev& F, const PowPoolDev& T, uint32_t cap,
+                                  uint32_t fin, bool want_map);
+// K13's table (`capacity` words a row) brought from the first `covered` blocks to `n`, from nothing if `stale`: K13b
+// for at most POW_POOL_LIFT_SMALL new blocks, else K13a per old row over them; then every new row over all blocks.
+// *launches is incremented per launch queued (pow_pool_lift_launches is its closed form), *work by its lanes.
+hipError_t pow_queue_pool_lift(hipStream_t stream, const uint32_t* parent, uint32_t* up, uint32_t capacity,
+                               uint32_t covered, uint32_t n, bool stale, uint32_t* launches, uint64_t* work);
 hipError_t pow_sort_u32(void* temp, size_t* temp_bytes, uint32_t* keys, uint32_t* alt, uint32_t n,
                         uint32_t** sorted, hipStream_t stream);
 hipError_t pow_launch_search_lat(bool full, bool any, bool asm_groups, unsigned grid, hipStream_t stream,

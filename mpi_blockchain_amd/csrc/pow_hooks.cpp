@@ -232,8 +232,7 @@ extern "C" int pow_test_pool_rank(pow_ctx* ctx, const uint32_t* next, size_t n, 
   step(hipMemsetAsync(base, 0, plan.words * sizeof(uint32_t), ctx->stream), "reset");  // status, index, bad, ctl: all zero
   step(hipMemcpyAsync(D.next[0], next, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream), "copy in");
   step(hipMemcpyAsync(D.depth[0], ones.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream), "copy in");
-  for (uint32_t r = 0; r < plan.rounds; ++r) step(pow_launch_pool_round(ctx->stream, D, r), "pow_pool_round_kernel");
-  step(pow_launch_pool_finish(ctx->stream, D, last), "pow_pool_finish_kernel");
+  if (rc == POW_OK) step(pow_queue_pool_rank(ctx->stream, D, plan.rounds), "K10d, K10e");
   step(hipMemcpyAsync(depth_out, D.depth[last], n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream), "copy out");
   step(hipMemcpyAsync(n_bad_out, D.bad[last], n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream), "copy out");
   // waited for even after a failed step: the copies queued so far read `ones`
@@ -276,11 +275,12 @@ struct pow_test_prune_io {
 static_assert(sizeof(pow_test_prune_io) == 23 * 8, "tests/pool_deep_util.py PruneIO");
 
 // K12 (pow_pool_prune.hip) on a forest of the caller's choosing, with no pool
-// and no table: the marks' reset, K12a, the rounds of K12b, K12c and K12d in
-// one section, then by K12d's total, as pow_pool_prune decides it: everything
-// marked, and K12a's positions are the map; otherwise new arrays at
-// pow_pool_prune_cap's capacity, K12e and K12f (nothing marked: the map is
-// POW_POOL_NONE throughout, as the library's reset makes it).  K10b is not run.
+// and no table: the mark's launches (pow_queue_pool_mark, as pool_mark_run
+// queues them) in one section, then by K12d's total, as pow_pool_prune decides
+// it: everything marked, and K12a's positions are the map; otherwise new arrays
+// at pow_pool_prune_cap's capacity and pow_queue_pool_compact over a view with
+// no table: K12e and K12f (nothing marked: the map is POW_POOL_NONE throughout,
+// as the library's reset makes it).  K10b is not run.
 // Two bounded waits, one per section: the second section's grid is the first's
 // result.  The scratch is pool_mark_run's: marks in depth[1 - fin], positions
 // in bad[1 - fin], the walks in next[], the partials in next[1].
@@ -331,11 +331,7 @@ extern "C" int pow_test_pool_prune(pow_ctx* ctx, size_t n, const pow_test_prune_
   up(F.depth[fin], io->depth, words), up(F.status, io->status, n), up(F.dig, io->digest, 8 * words);
   up(F.prev, io->prev, 8 * words), up(d_tips, n_tips ? io->tips : nullptr, n_tips * sizeof(uint32_t));
   if (rc == POW_OK) {  // pool_mark_run's section
-    step(hipMemsetAsync(F.depth[fin ^ 1u], 0, (size_t)((n32 + 3u) / 4u) * sizeof(uint32_t), ctx->stream), "reset");
-    step(pow_launch_pool_prune_seed(ctx->stream, F, fin, d_tips, n_tips, io->min_index, io->flags), "K12a");
-    for (uint32_t r = 0; r < rounds; ++r) step(pow_launch_pool_prune_round(ctx->stream, F, fin, r), "K12b");
-    step(pow_launch_pool_prune_count(ctx->stream, F, fin), "K12c");
-    step(pow_launch_pool_prune_scan(ctx->stream, F), "K12d");
+    step(pow_queue_pool_mark(ctx->stream, F, fin, d_tips, n_tips, io->min_index, io->flags), "K12a to K12d");
     down(&ctl, F.ctl, sizeof ctl), down(io->marks, F.depth[fin ^ 1u], n);
   }
   int waited = pow_ctx_stream_wait(ctx, "pow_test_pool_prune (mark)", 100ull * n * (rounds + 3ull));
@@ -370,13 +366,7 @@ extern "C" int pow_test_pool_prune(pow_ctx* ctx, size_t n, const pow_test_prune_
   }
   const PowPoolDev T = pow_pool_live_dev(to_base, to, nullptr, kept, 0);
   const size_t kw = (size_t)kept * sizeof(uint32_t);
-  step(hipMemsetAsync(T.ctl, 0, sizeof(PowPoolLiveCtl), ctx->stream), "reset");
-  if (kept) {
-    step(pow_launch_pool_prune_gather(ctx->stream, F, T, cap, fin), "K12e");
-    step(pow_launch_pool_prune_remap(ctx->stream, F, T, fin), "K12f");
-  } else if (io->map) {  // nothing marked: every node was dropped
-    step(hipMemsetD32Async((hipDeviceptr_t)F.next[0], (int)POW_POOL_NONE, n, ctx->stream), "reset");
-  }
+  step(pow_queue_pool_compact(ctx->stream, F, T, cap, fin, io->map != nullptr), "K12e, K12f");  // no table: no K10b
   down(&new_ctl, T.ctl, sizeof new_ctl), down(io->map, F.next[0], words);
   down(io->parent_out, T.parent, kw), down(io->index_out, T.index, kw), down(io->depth_out, T.depth[fin], kw);
   down(io->n_bad_out, T.bad[fin], kw), down(io->status_out, T.status, kept), down(io->digest_out, T.dig, 8 * kw);
@@ -412,10 +402,9 @@ struct pow_test_lift_io {
 static_assert(sizeof(pow_test_lift_io) == 13 * 8, "tests/pool_deep_util.py LiftIO");
 
 // K13 (pow_pool_lift.hip) on a parent and a depth array of the caller's making,
-// with no pool: the table as a pool of `covered` nodes had it (K13a over its
-// rows, at that size), then pool_lift_update's launches for a pool of n nodes
-// (K13b for at most POW_POOL_LIFT_SMALL new nodes, else K13a per row over them;
-// then every new row over all nodes), then one query launch, K13c or K13d.  The
+// with no pool: the table as a pool of `covered` nodes had it, then the query
+// calls' update to a pool of n nodes (both pow_queue_pool_lift, the statement
+// pool_lift_update runs), then one query launch, K13c or K13d.  The
 // table is allocated at `capacity` words a row, as the pool's, and filled with
 // 0xEE bytes first: an entry no launch wrote shows in `table`, and as a value it
 // is past every size, so no walk takes it for a position.
@@ -444,8 +433,8 @@ extern "C" int pow_test_pool_lift(pow_ctx* ctx, size_t n, const pow_test_lift_io
   if (io->launches) *io->launches = 0;
   if (n == 0) return POW_OK;
   HIP_OK(hipSetDevice(ctx->device));
-  const uint32_t n32 = (uint32_t)n, cap = io->capacity, covered = io->covered, k = (uint32_t)io->k, m = n32 - covered;
-  const uint32_t have = pow_pool_lift_rows(covered), rows = pow_pool_lift_rows(n32);
+  const uint32_t n32 = (uint32_t)n, cap = io->capacity, covered = io->covered, k = (uint32_t)io->k;
+  const uint32_t rows = pow_pool_lift_rows(n32);
   const size_t words = (size_t)n32 * sizeof(uint32_t), kb = (size_t)k * sizeof(uint32_t);
   const size_t up_words = std::max<size_t>((size_t)cap * pow_pool_lift_rows(cap), 1);
   uint32_t* d_parent = nullptr;
@@ -466,24 +455,13 @@ extern "C" int pow_test_pool_lift(pow_ctx* ctx, size_t n, const pow_test_lift_io
     step(hipMemsetAsync(d_up, 0xEE, up_words * sizeof(uint32_t), ctx->stream), "reset");
     step(hipMemcpyAsync(d_parent, io->parent, words, hipMemcpyHostToDevice, ctx->stream), "copy in");
     step(hipMemcpyAsync(d_depth, io->depth, words, hipMemcpyHostToDevice, ctx->stream), "copy in");
-    // the table a pool of `covered` nodes had
-    for (uint32_t j = 1; covered && j <= have; ++j)
-      step(pow_launch_pool_lift_row(ctx->stream, d_parent, d_up, cap, j, 0, covered, covered), "K13a");
-    work += (uint64_t)covered * have;
-    // pool_lift_update, stale when nothing was covered
-    if (m && have) {
-      if (m <= POW_POOL_LIFT_SMALL) {
-        step(pow_launch_pool_lift_small(ctx->stream, d_parent, d_up, cap, have, covered, n32), "K13b");
-        ++launches;
-      } else {
-        for (uint32_t j = 1; j <= have; ++j, ++launches)
-          step(pow_launch_pool_lift_row(ctx->stream, d_parent, d_up, cap, j, covered, m, n32), "K13a");
-      }
-      work += (uint64_t)m * have;
-    }
-    for (uint32_t j = have + 1u; j <= rows; ++j, ++launches)
-      step(pow_launch_pool_lift_row(ctx->stream, d_parent, d_up, cap, j, 0, n32, n32), "K13a");
-    work += (uint64_t)n32 * (rows - have);
+    // the table a pool of `covered` nodes had: made from nothing at that size; its launches are not reported
+    uint32_t before = 0;
+    if (rc == POW_OK && covered)
+      step(pow_queue_pool_lift(ctx->stream, d_parent, d_up, cap, 0, covered, true, &before, &work), "K13a");
+    // the query call's update, stale when nothing was covered
+    if (rc == POW_OK)
+      step(pow_queue_pool_lift(ctx->stream, d_parent, d_up, cap, covered, n32, covered == 0, &launches, &work), "K13a, K13b");
   }
   if (rc == POW_OK && k) {
     uint32_t* const d_in0 = d_io;

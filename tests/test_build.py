@@ -489,11 +489,19 @@ def null_stream_calls(text: str) -> list[tuple[int, str]]:
     return bad
 
 
-def api_function(name: str) -> str:
-    """The text of pow_api.cpp's function `name`, from its return type to its closing brace."""
-    api = open(os.path.join(CSRC, "pow_api.cpp")).read()
-    body = api[api.index(f"int {name}("):]
+def api_function(name: str, file: str = "pow_api.cpp", ret: str = "int") -> str:
+    """The text of the function `name` of csrc/`file`, from its return type `ret` to its closing brace."""
+    api = open(os.path.join(CSRC, file)).read()
+    body = api[api.index(f"{ret} {name}("):]
     return body[:body.index("\n}\n")]
+
+
+POOL_API = "pow_api.cpp"  # where the pool's host side is: pow_index_blocks, pow_pool_*, pow_queue_pool_*
+
+
+def pool_function(name: str, ret: str = "int") -> str:
+    """api_function over the pool's host side; ret="hipError_t" for a pow_queue_pool_* sequence."""
+    return api_function(name, POOL_API, ret)
 
 
 def timed_section_helpers() -> dict:

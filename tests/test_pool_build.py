@@ -10,7 +10,7 @@ import pytest
 
 from mpi_blockchain_amd import _lib
 
-from test_build import CSRC, ROOT, api_function, null_stream_calls, timed_section_helpers
+from test_build import CSRC, POOL_API, ROOT, api_function, null_stream_calls, pool_function, timed_section_helpers
 
 SRC = "pow_pool.hip"
 SHARED = "pow_audit_dev.h"
@@ -83,7 +83,7 @@ def test_pool_kernels_are_in_both_libraries():
 
 def test_no_null_stream_in_pool_sources():
     found = {}
-    for f in (SRC, SHARED, "pow_api.cpp", "pow_ctx.h", "pow_hooks.cpp"):
+    for f in (SRC, SHARED, POOL_API, "pow_ctx.h", "pow_hooks.cpp"):
         hits = null_stream_calls(open(os.path.join(CSRC, f)).read())
         if hits:
             found[f] = hits
@@ -94,9 +94,12 @@ def test_no_null_stream_in_pool_sources():
 
 def test_index_blocks_has_one_bounded_wait_after_the_tiles():
     """The tile walk is pow_verify_chain's; behind it one timed section holds
-    the reset, K10b to K10e and the copies down, with one bounded wait."""
-    body, h = api_function("pow_index_blocks"), timed_section_helpers()
-    assert not null_stream_calls(body)
+    the reset, K10b to K10e and the copies down, with one bounded wait.  K10d
+    and K10e are the one statement of the rank, pow_queue_pool_rank."""
+    body, h = pool_function("pow_index_blocks"), timed_section_helpers()
+    rank = pool_function("pow_queue_pool_rank", "hipError_t")
+    assert not null_stream_calls(body + rank)
+    assert "hipStreamSynchronize" not in rank and "hipGraph" not in rank and "hipEvent" not in rank
     assert body.count("verify_tiles(") == 1 and "pow_launch_pool_audit(ctx->stream" in body
     after = body[body.index("[](const VerifyTile&) {}))"):]
     assert after.count("timed_begin(") == 1 and after.count("timed_end(") == 1
@@ -105,9 +108,15 @@ def test_index_blocks_has_one_bounded_wait_after_the_tiles():
     assert "stream_wait" not in body and "hipStreamSynchronize" not in body and "hipGraph" not in body
     assert h["timed_end"].count("stream_wait_for(") == 1
     order = [after.index(s) for s in ("timed_begin(", "hipMemsetAsync(D.table", "pow_launch_pool_insert(",
-                                      "pow_launch_pool_join(", "pow_launch_pool_round(", "pow_launch_pool_finish(",
+                                      "pow_launch_pool_join(", "pow_queue_pool_rank(ctx->stream, D, plan.rounds)",
                                       "hipEventRecord(ctx->ev1", "hipMemcpyAsync(", "timed_end(")]
     assert order == sorted(order)
+    # the rank: `rounds` rounds, then the finish on the buffers the last round wrote
+    order = [rank.index(s) for s in ("for (uint32_t r = 0; r < rounds; ++r)", "pow_launch_pool_round(stream, D, r)",
+                                     "pow_launch_pool_finish(stream, D, rounds & 1u)")]
+    assert order == sorted(order)
+    assert re.findall(r"\bfor \(([^;]*);", rank) == ["uint32_t r = 0"]
+    assert "for (" not in body and "while" not in body + rank
     # the table is reset on every call, over all of its slots
     assert "hipMemsetAsync(D.table, 0xFF, (size_t)D.slots * sizeof(uint32_t), ctx->stream)" in after
     # only what the caller asked for comes down

@@ -4,6 +4,8 @@ walks written out here; the two hooks pow_test_pool_prune and
 pow_test_pool_lift in the test library only; and their POW_EINVAL cases, which
 need no GPU: every check stands in front of the first use of the context."""
 import ctypes
+import os
+import re
 
 import numpy as np
 import pytest
@@ -264,3 +266,53 @@ def test_lift_hook_einval_without_a_gpu():
     assert lift(FAKE, 0, ctypes.byref(io)) == _lib.POW_EINVAL  # k = 1 queries on nothing
     io.k = 0
     assert lift(FAKE, 0, ctypes.byref(io)) == 0  # nothing to do
+
+
+# ---- the hooks run the library's own launch sequences ----
+SEQUENCE_LAUNCHERS = ("pow_launch_pool_round(", "pow_launch_pool_finish(", "pow_launch_pool_prune_seed(",
+                      "pow_launch_pool_prune_round(", "pow_launch_pool_prune_count(", "pow_launch_pool_prune_scan(",
+                      "pow_launch_pool_prune_gather(", "pow_launch_pool_prune_remap(", "pow_launch_pool_lift_row(",
+                      "pow_launch_pool_lift_small(")
+SEQUENCES = ("pow_queue_pool_rank", "pow_queue_pool_mark", "pow_queue_pool_compact", "pow_queue_pool_lift")
+
+
+def function_bodies(text):
+    """(name, body) of every function defined at file level in `text` (comments
+    and literals already blanked): a definition starts in column 0 and ends at
+    the next closing brace in column 0, as everywhere under csrc/."""
+    out = []
+    for m in re.finditer(r"^[A-Za-z_][^\n;{}()]*?\b(\w+)\s*\([^;{}]*\)\s*\{", text, flags=re.M):
+        out.append((m.group(1), text[m.end():text.index("\n}", m.end())]))
+    return out
+
+
+def test_each_shared_launch_sequence_is_stated_once():
+    """K10d/K10e, K12a to K12f and K13a/K13b are queued by pow_queue_pool_*
+    (csrc/pow_api.cpp) and by nothing else in the host sources: the calls
+    and the hooks of the deep tests run the same statements, so a test that
+    reaches 2^20 nodes holds the shipped sequence."""
+    from test_build import CSRC, POOL_API, _strip_comments_and_strings
+
+    users = {name: [] for name in SEQUENCE_LAUNCHERS}
+    for f in sorted(os.listdir(CSRC)):
+        if not f.endswith((".cpp", ".h")):
+            continue
+        text = _strip_comments_and_strings(open(os.path.join(CSRC, f)).read())
+        bodies = function_bodies(text)
+        for name in SEQUENCE_LAUNCHERS:
+            inside = sum(body.count(name) for _, body in bodies)
+            # outside a body: nothing but the wrapper's declaration in pow_ctx.h
+            assert text.count(name) - inside == (1 if f == "pow_ctx.h" else 0), (f, name)
+            users[name] += [(f, fn) for fn, body in bodies if name in body]
+    for name, where in users.items():
+        assert len(where) == 1, (name, where)
+        assert where[0][0] == POOL_API and where[0][1] in SEQUENCES, (name, where)
+    assert {fn for where in users.values() for _, fn in where} == set(SEQUENCES)
+    hooks = _strip_comments_and_strings(open(os.path.join(CSRC, "pow_hooks.cpp")).read())
+    for name in SEQUENCE_LAUNCHERS:
+        assert name not in hooks, name
+    for name in SEQUENCES:
+        assert f"{name}(ctx->stream, " in hooks, name
+    # the instrument sees a seeded copy: a launcher called from a second function
+    seeded = "int copy(pow_ctx* ctx) {\n  return (int)pow_launch_pool_round(ctx->stream, D, 0);\n}\n"
+    assert [fn for fn, body in function_bodies(seeded) if "pow_launch_pool_round(" in body] == ["copy"]

@@ -11,7 +11,7 @@ import pytest
 
 from mpi_blockchain_amd import _lib
 
-from test_build import CSRC, ROOT, api_function, null_stream_calls
+from test_build import CSRC, POOL_API, ROOT, api_function, null_stream_calls, pool_function
 from test_pool_build import kernel_metadata
 
 SRC = "pow_pool_lift.hip"
@@ -68,9 +68,11 @@ def test_no_null_stream_in_lift_sources():
     assert kernel.count("hipLaunchKernelGGL(") == 4 and kernel.count("__global__") == 4
     assert "<<<" not in kernel and "hipGraph" not in kernel
     assert kernel.count("__launch_bounds__(256)") == 4 and kernel.count("dim3(256), 0, stream") == 4
-    for name in ("pow_pool_ancestors", "pow_pool_fork_points", "pow_pool_chain", "pow_pool_lift_get_info",
-                 "pool_lift_args", "pool_lift_update", "pool_lift_run"):
-        body = api_function(name)
+    bodies = {name: pool_function(name) for name in ("pow_pool_ancestors", "pow_pool_fork_points", "pow_pool_chain",
+                                                     "pow_pool_lift_get_info", "pool_lift_args", "pool_lift_update",
+                                                     "pool_lift_run")}
+    bodies["pow_queue_pool_lift"] = pool_function("pow_queue_pool_lift", "hipError_t")
+    for name, body in bodies.items():
         assert not null_stream_calls(body), name
         assert "hipStreamSynchronize" not in body and "hipDeviceSynchronize" not in body and "hipGraph" not in body, name
 
@@ -113,39 +115,65 @@ def test_the_host_side_of_the_query_calls():
     """Each call: its argument checks, pool_ready, then one pool_lift_run, which
     holds the one timed section.  No host loop but the position check (over the
     queries) and the table's rows."""
-    args, update, run = api_function("pool_lift_args"), api_function("pool_lift_update"), api_function("pool_lift_run")
+    args, update, run = pool_function("pool_lift_args"), pool_function("pool_lift_update"), pool_function("pool_lift_run")
+    queue = pool_function("pow_queue_pool_lift", "hipError_t")  # the table's launches, stated once
     assert re.findall(r"\bfor \(([^;]*);", args) == ["size_t q = 0"] and "q < k" in args
-    assert re.findall(r"\bfor \(([^;]*);", update) == ["uint32_t j = 1", "uint32_t j = have + 1u"]  # rows, never blocks
-    assert "for (" not in run and "while" not in run + update + args
-    assert run.count("timed_begin(") == 1 and run.count("timed_end(") == 1 and "timed_" not in update
+    assert re.findall(r"\bfor \(([^;]*);", queue) == ["uint32_t j = 1", "uint32_t j = have + 1u"]  # rows, never blocks
+    assert "for (" not in run + update and "while" not in run + update + args + queue
+    assert run.count("timed_begin(") == 1 and run.count("timed_end(") == 1 and "timed_" not in update + queue
+    assert update.count("pow_queue_pool_lift(") == 1 and "pow_launch_pool" not in update
+    assert "stream_wait" not in queue and "hipEvent" not in queue and "hipMemcpy" not in queue and "ctx" not in queue
+    # K13b for at most POW_POOL_LIFT_SMALL new blocks, else K13a per old row over them; then every new row over all
+    order = [queue.index(s) for s in ("if (m && have) {", "if (m <= POW_POOL_LIFT_SMALL) {",
+                                      "pow_launch_pool_lift_small(stream, parent, up, capacity, have, covered, n)",
+                                      "for (uint32_t j = 1; j <= have;",
+                                      "pow_launch_pool_lift_row(stream, parent, up, capacity, j, covered, m, n)",
+                                      "for (uint32_t j = have + 1u; j <= rows;",
+                                      "pow_launch_pool_lift_row(stream, parent, up, capacity, j, 0, n, n)")]
+    assert order == sorted(order)
+    assert "have = stale ? 0u : pow_pool_lift_rows(covered), rows = pow_pool_lift_rows(n)" in queue
     assert run.count("hipMemcpyAsync(") == 2  # the arguments up in one copy, the results down in one
     order = [run.index(s) for s in ("RESERVE(t.d_up", "RESERVE(p->d_find", "hipMemcpyHostToDevice", "timed_begin(",
                                     "pool_lift_update(", "pow_launch_pool_lift_fork(", "pow_launch_pool_lift_ancestor(",
                                     "hipEventRecord(ctx->ev1", "hipMemcpyDeviceToHost", "timed_end(", "t.covered = n;")]
     assert order == sorted(order)
-    assert "launches + 1u, &ctx->stats" in run and "pow_pool_lift_launches(covered, n, stale)" in update
+    # pow_stats.launches is the count of what was queued: every launcher call in the sequence is counted exactly
+    # once, and pool_lift_run hands that count (and the query launch) to timed_end ...
+    launchers = re.findall(r"pow_launch_pool_lift_\w+\(", queue)
+    assert len(launchers) == 3 and len(re.findall(r"\+\+\*launches", queue)) == len(launchers)
+    assert len(re.findall(r"\*?\blaunches\b", queue)) == 1 + len(launchers)  # the parameter, then one increment each
+    assert re.search(r"pow_launch_pool_lift_small\([^;]*;\s+\+\+\*launches;", queue)  # K13b: once
+    assert len(re.findall(r"\+\+j, \+\+\*launches\)\s+QUEUE_OK\(pow_launch_pool_lift_row\(", queue)) == 2  # K13a: once a row
+    assert "uint32_t launches = 0;" in run and "pool_lift_update(p, covered, stale, &launches, &work)" in run
+    assert "launches + 1u, &ctx->stats" in run and len(re.findall(r"\blaunches\b", re.sub(r"//[^\n]*", "", run))) == 3
+    assert "launches" not in update.replace("uint32_t* launches", "").replace("stale, launches,", "")
+    # ... and the closed form the plan unit and Python restate has its one definition, in pow_host.cpp
+    defs = {f: len(re.findall(r"^uint32_t pow_pool_lift_launches\([^;{]*\) \{", open(os.path.join(CSRC, f)).read(), flags=re.M))
+            for f in os.listdir(CSRC) if os.path.isfile(os.path.join(CSRC, f))}
+    assert {f: n for f, n in defs.items() if n} == {"pow_host.cpp": 1}
+    assert "pow_pool_lift_launches" not in open(os.path.join(CSRC, POOL_API)).read()  # the calls count, they do not restate
     for name, checks in CALLS.items():
-        body = api_function(name)
+        body = pool_function(name)
         assert "for (" not in body and "while" not in body and "std::vector" not in body, name
         assert body.count("pool_lift_run(") == 1 and "timed_begin(" not in body and "hipMalloc" not in body, name
         first = "!p)" if checks is None else checks
         order = [body.index(s) for s in (first, "pool_ready(", "ctx->stats = pow_stats{}", "if (k == 0) return POW_OK;",
                                          "pool_lift_run(")]
         assert order == sorted(order), name
-    info = api_function("pow_pool_lift_get_info")
+    info = pool_function("pow_pool_lift_get_info")
     assert "hip" not in info and "ctx" not in info  # no GPU work
 
 
 def test_the_table_is_one_member_and_the_generation_has_two_bumps():
-    api = open(os.path.join(CSRC, "pow_api.cpp")).read()
+    api = open(os.path.join(CSRC, POOL_API)).read()
     struct = api[api.index("struct pow_pool {"):]
     struct = struct[:struct.index("\n};")]
     assert struct.count("PowPoolLift lift;") == 1 and "lift.release();" in struct[struct.index("void release_buffers()"):]
     assert api.count("++p->gen") == 2
     fill = api[api.index("static void pool_fill_info("):]
     assert "if (reranked) ++p->gen;" in fill[:fill.index("\n}\n")]
-    prune = api_function("pow_pool_prune")
+    prune = pool_function("pow_pool_prune")
     assert prune.count("p->lift.release_table(), ++p->gen;") == 1  # the prune gives the table's memory back
     assert prune.index("timed_end(") < prune.index("p->lift.release_table(), ++p->gen;") < prune.index("p->size = kept;")
-    add = api_function("pow_pool_add")
+    add = pool_function("pow_pool_add")
     assert "lift" not in add and "gen" not in add  # the add launches nothing new: the bump is pool_fill_info's

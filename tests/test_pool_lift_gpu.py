@@ -338,6 +338,31 @@ def test_adds_of_256_and_257_blocks(miner, chain1025):
         assert ask_forks(miner, pool, mirror, table, sample(900)) == 1
 
 
+def test_an_add_of_300_blocks_across_a_row_boundary(miner, chain1025):
+    """Both halves of the table's update in one query call: more new blocks
+    than the one workgroup takes (300 > 256), so K13a runs per old row over
+    them, and a size that passes a power of two (300 -> 600: 8 rows, then 9),
+    so the new row runs over all blocks behind them."""
+    pool, mirror, infos = feed(miner, [chain1025[:300]], 0, reserve=1024)
+    with pool:
+        table = Table()
+        rng = random.Random(9)
+
+        def sample(n):
+            return [(rng.randrange(n), rng.randrange(n)) for _ in range(300)] + [(n - 1, 0), (0, n - 1), (n - 1, 299)]
+
+        assert ask_forks(miner, pool, mirror, table, sample(300)) == rows(300) == 8
+        _, _, infos = feed(miner, [pu.shuffled(chain1025[300:600], 24)[0]], 0, mirror=mirror, pool=pool)
+        table.added(infos[0])
+        assert infos[0]["reranked"] == 0
+        assert ask_forks(miner, pool, mirror, table, sample(600)) == 8 + 1 == lift_launches(300, 600, False)
+        assert subset(pool.lift_info(), ("rebuilt", "extended", "rows")) == {"rebuilt": 0, "extended": 300, "rows": 9}
+        # the ninth row's entries (512 steps) and the old rows' over the new blocks
+        ask_ancestors(miner, pool, mirror, table, [(p, s) for p in range(300, 600, 3) for s in (1, 255, 256, 511, 512, mirror.depth[p])])
+        tip = mirror.best
+        assert mirror.depth[tip] == 600 and len(ask_chain(miner, pool, mirror, table, tip)) == 600
+
+
 # ---- capacity ----
 def test_the_table_follows_the_capacity(miner, tree, chain1025):
     pool, mirror, infos = feed(miner, [tree], pu.D)

@@ -10,7 +10,9 @@ import pytest
 
 from mpi_blockchain_amd import _lib
 
-from test_build import CSRC, ROOT, api_function, null_stream_calls
+from test_build import CSRC, POOL_API, ROOT, api_function, null_stream_calls, pool_function
+
+QUEUES = ("pow_queue_pool_mark", "pow_queue_pool_compact")  # the K12 sequences pow_api.cpp states once
 from test_pool_build import kernel_metadata
 
 SRC = "pow_pool_prune.hip"
@@ -67,8 +69,9 @@ def test_no_null_stream_in_prune_sources():
     assert kernel.count("hipLaunchKernelGGL(") == 6 and kernel.count("__global__") == 6
     assert "<<<" not in kernel and "hipGraph" not in kernel
     assert kernel.count("__launch_bounds__(256)") == 6 and kernel.count("dim3(256), 0, stream") == 6
-    for name in ("pow_pool_mark", "pow_pool_prune", "pool_mark_run", "pool_mark_args"):
-        body = api_function(name)
+    bodies = {name: pool_function(name) for name in ("pow_pool_mark", "pow_pool_prune", "pool_mark_run", "pool_mark_args")}
+    bodies.update({name: pool_function(name, "hipError_t") for name in QUEUES})
+    for name, body in bodies.items():
         assert not null_stream_calls(body), name
         assert "hipStreamSynchronize" not in body and "hipDeviceSynchronize" not in body and "hipGraph" not in body, name
 
@@ -97,9 +100,11 @@ def test_the_rounds_go_ping_pong():
     assert "next_b[i] = nx;" in kernel and not re.search(r"next_a\[[^\]]*\]\s*=[^=]", kernel)
     launcher = text[text.index("hipError_t pow_launch_pool_prune_round"):text.index("hipError_t pow_launch_pool_prune_count")]
     assert "D.next[a]" in launcher and "D.next[a ^ 1u]" in launcher
-    run = api_function("pool_mark_run")
-    assert "for (uint32_t r = 0; r < rounds; ++r) HIP_OK(pow_launch_pool_prune_round(ctx->stream, D, p->fin, r));" in run
-    assert "rounds = pow_pool_rounds(n)" in run
+    mark = pool_function("pow_queue_pool_mark", "hipError_t")
+    assert "for (uint32_t r = 0; r < rounds; ++r) QUEUE_OK(pow_launch_pool_prune_round(stream, D, fin, r));" in mark
+    assert "rounds = pow_pool_rounds(D.n)" in mark
+    run = pool_function("pool_mark_run")  # its D holds the pool's blocks, and its budget counts the same rounds
+    assert "n = p->size, rounds = pow_pool_rounds(n)" in run and "D = pool_dev(p, n)" in run
 
 
 def test_warmup_does_not_launch_the_kernels():
@@ -107,7 +112,7 @@ def test_warmup_does_not_launch_the_kernels():
 
 
 def test_the_pool_has_no_new_holder_and_k10_k11_are_as_they_were():
-    api = open(os.path.join(CSRC, "pow_api.cpp")).read()
+    api = open(os.path.join(CSRC, POOL_API)).read()
     struct = api[api.index("struct pow_pool {"):]
     struct = struct[:struct.index("\n};")]
     names = [n.strip() for decl in re.findall(r"^\s+(?:DevBuf|HostBuf)<[^>]+>\s+([^;]+);", struct, flags=re.M)
@@ -123,28 +128,48 @@ def test_the_host_side_of_both_calls():
     """mark: one timed section.  prune: that one and, if it drops and keeps,
     a second; the old arrays wait until its wait has passed.  No host loop
     runs over the pool's blocks: the one loop is the check of the tips."""
-    args, run = api_function("pool_mark_args"), api_function("pool_mark_run")
-    mark, prune = api_function("pow_pool_mark"), api_function("pow_pool_prune")
+    args, run = pool_function("pool_mark_args"), pool_function("pool_mark_run")
+    mark, prune = pool_function("pow_pool_mark"), pool_function("pow_pool_prune")
+    q_mark, q_compact = (pool_function(name, "hipError_t") for name in QUEUES)
     assert re.findall(r"\bfor \(([^;]*);", args) == ["size_t k = 0"] and "k < n_tips" in args
-    assert re.findall(r"\bfor \(([^;]*);", run) == ["uint32_t r = 0"]
-    for body in (mark, prune):
+    assert re.findall(r"\bfor \(([^;]*);", q_mark) == ["uint32_t r = 0"]
+    for body in (mark, prune, run, q_compact):
         assert "for (" not in body and "while" not in body and "std::vector" not in body and "std::iota" not in body
     assert run.count("timed_begin(") == 1 and run.count("timed_end(") == 1
-    order = [run.index(s) for s in ("hipMemcpyHostToDevice", "timed_begin(", "hipMemsetAsync(", "pow_launch_pool_prune_seed(",
-                                    "pow_launch_pool_prune_round(", "pow_launch_pool_prune_count(",
-                                    "pow_launch_pool_prune_scan(", "hipEventRecord(ctx->ev1", "hipMemcpyDeviceToHost",
-                                    "timed_end(")]
+    # the caller's part of the mark's section ...
+    order = [run.index(s) for s in ("hipMemcpyHostToDevice", "timed_begin(",
+                                    "pow_queue_pool_mark(ctx->stream, D, p->fin, p->d_find.p, n_tips, min_index, flags)",
+                                    "hipEventRecord(ctx->ev1", "hipMemcpyDeviceToHost", "timed_end(")]
     assert order == sorted(order)
+    # ... and the sequence's: the reset and the launches in their order; it waits for nothing and times nothing
+    order = [q_mark.index(s) for s in ("rounds = pow_pool_rounds(", "hipMemsetAsync(D.depth[fin ^ 1u], 0",
+                                       "pow_launch_pool_prune_seed(", "for (uint32_t r = 0; r < rounds; ++r)",
+                                       "pow_launch_pool_prune_round(", "pow_launch_pool_prune_count(",
+                                       "pow_launch_pool_prune_scan(")]
+    assert order == sorted(order)
+    for body in (q_mark, q_compact):
+        assert "timed_" not in body and "stream_wait" not in body and "hipEvent" not in body and "hipMemcpy" not in body
+        assert "ctx" not in body and "pow_pool*" not in body  # a stream and views, never a pool
     assert "3u + rounds, &ctx->stats" in run
     assert mark.count("pool_mark_run(") == 1 and "timed_begin(" not in mark and "hipMalloc" not in mark
     assert prune.count("pool_mark_run(") == 1 and prune.count("timed_begin(") == 1 and prune.count("timed_end(") == 1
-    order = [prune.index(s) for s in ("pool_mark_run(", "p->d_old_arr = p->d_arr;", "RESERVE(p->d_arr", "p->d_old_table = p->d_table;",
-                                      "RESERVE(p->d_table", "timed_begin(", "hipMemsetAsync(T.ctl, 0", "hipMemsetAsync(T.table, 0xFF",
-                                      "pow_launch_pool_prune_gather(", "pow_launch_pool_prune_remap(",
-                                      "pow_launch_pool_insert(ctx->stream, T)", "hipEventRecord(ctx->ev1",
+    order = [prune.index(s) for s in ("pool_mark_run(", "pool_retire(p->d_arr, p->d_old_arr, to.words)",
+                                      "pool_retire(p->d_table, p->d_old_table, slots)", "timed_begin(",
+                                      "pow_queue_pool_compact(ctx->stream, F, T, cap, p->fin, map != nullptr)",
+                                      "hipEventRecord(ctx->ev1",
                                       "sizeof(PowPoolLiveCtl), hipMemcpyDeviceToHost", "timed_end(",
                                       "p->d_old_arr.release(), p->d_old_table.release();", "p->dead = false;")]
     assert order == sorted(order)
+    retire = pool_function("pool_retire")  # what each of the two lines above does: the old buffer kept, a new one made
+    order = [retire.index(s) for s in ("old = d_new;", "d_new = DevBuf<uint32_t>{};", "RESERVE(d_new, n);")]
+    assert order == sorted(order)
+    order = [q_compact.index(s) for s in ("hipMemsetAsync(T.ctl, 0", "if (T.table) QUEUE_OK(hipMemsetAsync(T.table, 0xFF",
+                                          "if (T.n) {", "pow_launch_pool_prune_gather(", "pow_launch_pool_prune_remap(",
+                                          "if (T.table) QUEUE_OK(pow_launch_pool_insert(stream, T))",
+                                          "} else if (want_map) {", "hipMemsetD32Async((hipDeviceptr_t)F.next[0], (int)POW_POOL_NONE, F.n")]
+    assert order == sorted(order)
+    # the prune's T is the survivors' view with the new table: T.n = kept, T.slots = slots
+    assert "T = pow_pool_live_dev(p->d_arr.p, to, p->d_table.p, kept, slots)" in prune
     assert "pow_pool_prune_cap(kept, pow_pool_live_first_cap(0, ctx->pool_first_cap))" in prune
     assert "pow_pool_prune_slots(cap, kept, ctx->pool_slots_log2)" in prune
     assert "HostToDevice" not in prune and "padded_message" not in prune and "verify_tiles" not in prune  # no struct goes up

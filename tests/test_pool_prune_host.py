@@ -223,7 +223,7 @@ def test_a_null_pool_is_the_first_fault():
 def test_the_checks_stand_in_the_stated_order():
     """Both calls open with one helper, whose checks are in the header's
     order, then pool_ready, then the statistics' reset."""
-    from test_build import api_function
+    from test_build import pool_function as api_function
 
     args = api_function("pool_mark_args")
     order = [args.index(s) for s in ("!p)", "POW_KEEP_BY_INDEX | POW_KEEP_SOUND_ONLY", "n_tips > POW_POOL_MAX_TIPS",

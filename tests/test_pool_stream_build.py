@@ -10,7 +10,7 @@ import pytest
 
 from mpi_blockchain_amd import _lib
 
-from test_build import CSRC, ROOT, api_function, null_stream_calls, timed_section_helpers
+from test_build import CSRC, POOL_API, ROOT, api_function, null_stream_calls, pool_function, timed_section_helpers
 from test_pool_build import kernel_metadata
 
 SRC = "pow_pool_live.hip"
@@ -67,8 +67,9 @@ def test_no_null_stream_in_live_sources():
         assert not null_stream_calls(open(os.path.join(CSRC, f)).read()), f
     kernel = open(os.path.join(CSRC, SRC)).read()
     assert kernel.count("hipLaunchKernelGGL(") == 6 and "<<<" not in kernel and "hipGraph" not in kernel
-    for name in ("pow_pool_open", "pow_pool_add", "pow_pool_read", "pow_pool_find", "pool_alloc", "pool_grow"):
-        assert not null_stream_calls(api_function(name)), name
+    for name in ("pow_pool_open", "pow_pool_add", "pow_pool_read", "pow_pool_find", "pool_alloc", "pool_grow",
+                 "pool_retire"):
+        assert not null_stream_calls(pool_function(name)), name
 
 
 def test_the_helpers_have_one_copy():
@@ -118,7 +119,8 @@ def test_add_has_at_most_two_bounded_waits_and_no_work_per_earlier_block():
     """One tile walk over the new structs, then the fast path's timed section
     and, behind `if (adopted)`, the re-rank's.  Nothing on the host runs over
     the pool's earlier blocks and nothing goes up whose size depends on them."""
-    body, h = api_function("pow_pool_add"), timed_section_helpers()
+    body, h = pool_function("pow_pool_add"), timed_section_helpers()
+    rank = pool_function("pow_queue_pool_rank", "hipError_t")
     assert h["timed_end"].count("stream_wait_for(") == 1
     assert body.count("verify_tiles(") == 1 and "pow_launch_pool_audit(ctx->stream" in body
     assert "ctx, blocks, m," in body[body.index("verify_tiles("):]  # the batch, not the pool
@@ -133,17 +135,30 @@ def test_add_has_at_most_two_bounded_waits_and_no_work_per_earlier_block():
                                      "hipEventRecord(ctx->ev1", "hipMemcpyAsync(", "timed_end(")]
     assert order == sorted(order)
     order = [slow.index(s) for s in ("timed_begin(", "pow_launch_pool_live_strip(", "hipMemsetAsync(d_ctl, 0",
-                                     "pow_launch_pool_join(", "pow_launch_pool_round(", "pow_launch_pool_finish(",
+                                     "pow_launch_pool_join(", "pow_queue_pool_rank(ctx->stream, D, all)",
                                      "hipEventRecord(ctx->ev1", "hipMemcpyAsync(", "timed_end(")]
     assert order == sorted(order)
-    # the only loops are the rounds'; no per-block host work
-    assert re.findall(r"\bfor \(([^;]*);", body) == ["uint32_t r = 0", "uint32_t r = 0"] and "while" not in body
+    # ... whose rank is K10's, stated once: the rounds, then the finish on the buffers the last round wrote
+    order = [rank.index(s) for s in ("for (uint32_t r = 0; r < rounds; ++r)", "pow_launch_pool_round(stream, D, r)",
+                                     "pow_launch_pool_finish(stream, D, rounds & 1u)")]
+    assert order == sorted(order)
+    assert "all = pow_pool_rounds(n)" in slow and "p->fin = all & 1u;" in slow
+    # the only loops are the rounds': K11d's here, K10d's in the rank; no per-block host work
+    assert re.findall(r"\bfor \(([^;]*);", body) == ["uint32_t r = 0"] and "while" not in body + rank
+    assert re.findall(r"\bfor \(([^;]*);", rank) == ["uint32_t r = 0"]
     assert "padded_message" not in body and "std::vector" not in body
     # nothing goes up but the batch (verify_tiles) and resets; what comes down is the control words
     copies = re.findall(r"hipMemcpyAsync\(([^;]*);", body)
     assert len(copies) == 2 and all("sizeof(PowPoolLiveCtl), hipMemcpyDeviceToHost" in c for c in copies)
-    grow = api_function("pool_grow")
+    grow = pool_function("pool_grow")
     assert grow.count("hipMemcpyAsync(") == 1 and "hipMemcpyDeviceToDevice" in grow and "HostToDevice" not in grow
+    # the arrays and the table an add outgrows wait in d_old_* until the waits have passed
+    assert grow.index("pool_retire(p->d_arr, p->d_old_arr, to.words)") < grow.index("hipMemcpyAsync(")
+    order = [body.index(s) for s in ("pool_grow(p, n)", "pool_retire(p->d_table, p->d_old_table, slots)", "verify_tiles(",
+                                     "if (adopted) {", "p->d_old_arr.release(), p->d_old_table.release();",
+                                     "p->dead = false;")]
+    assert order == sorted(order) and body.count("timed_end(") == 2
+    assert body.rindex("timed_end(") < body.index("p->d_old_arr.release(), p->d_old_table.release();")
     # the argument checks come first, in the stated order
     checks = [body.index(s) for s in ("!p)", "!blocks && m", "m > POW_POOL_MAX_BLOCKS - p->size", "pool_ready(",
                                       "ctx->stats")]
@@ -152,7 +167,7 @@ def test_add_has_at_most_two_bounded_waits_and_no_work_per_earlier_block():
 
 def test_pool_buffers_are_released():
     """Every holder of pow_pool is named in its release_buffers, which open's failure path and close call."""
-    api = open(os.path.join(CSRC, "pow_api.cpp")).read()
+    api = open(os.path.join(CSRC, POOL_API)).read()
     struct = api[api.index("struct pow_pool {"):]
     struct = struct[:struct.index("\n};")]
     release = struct[struct.index("void release_buffers()"):]
@@ -162,7 +177,13 @@ def test_pool_buffers_are_released():
     for n in names:
         assert f"{n}.release()" in release, n
     assert api.count("p->release_buffers()") == 2
-    assert "if (!ctx->wedged) p->release_buffers();" in api_function("pow_pool_open")
+    assert "if (!ctx->wedged) p->release_buffers();" in pool_function("pow_pool_open")
+    # the retired-buffer idiom has one statement and four users; the old holder is released by its caller alone
+    retire = pool_function("pool_retire")
+    order = [retire.index(s) for s in ("old = d_new;", "d_new = DevBuf<uint32_t>{};", "RESERVE(d_new, n);")]
+    assert order == sorted(order) and "release" not in retire
+    assert api.count("DevBuf<uint32_t>{}") == 1 and len(re.findall(r"\bpool_retire\(p->", api)) == 4
+    assert api.count("p->d_old_arr.release(), p->d_old_table.release();") == 2
     assert "if (!ctx->wedged) p->release_buffers();" in api[api.index("void pow_pool_close("):]
 
 

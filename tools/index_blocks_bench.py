@@ -18,12 +18,14 @@ which tip wins?" on one MI355X and on the same box's CPU.  Pools at difficulty
               chain copied out) and then ONE pow_verify_chains call over them
 
 Median [min, max] of 9 calls (or --calls) after 2 warm-up calls.  Writes the
-table to profiles/index_blocks/README.md (or --out) and prints it.
+table to profiles/index_blocks/README.md (or --out) and prints it; --json FILE keeps
+every timed call of every row.
 
-    python tools/index_blocks_bench.py [--calls 9] [--out FILE] [--shapes 5,16,race,200,4096,65536,1048576]
+    python tools/index_blocks_bench.py [--calls 9] [--out FILE] [--json FILE] [--device-only] [--shapes 5,16,race,200,4096,65536,1048576]
 """
 import argparse
 import ctypes
+import json
 import os
 import statistics
 import subprocess
@@ -59,6 +61,32 @@ def cpu_lib():
     return C
 
 
+class Calls(tuple):
+    """(median, min, max) ms of timed calls; .ms keeps the calls themselves for --json."""
+
+    def __new__(cls, ts):
+        self = super().__new__(cls, (statistics.median(ts), min(ts), max(ts)))
+        self.ms = list(ts)
+        return self
+
+
+def write_json(path, rows, names=None):
+    """--json FILE (this tool and the pool tools): every row as it was measured,
+    a timed column as {"ms": its calls}, so that a script can take medians and
+    interquartile ranges; names = the fields of a row that is a tuple."""
+    def plain(v):
+        if isinstance(v, Calls):
+            return {"ms": v.ms}
+        if isinstance(v, dict):
+            return {k: plain(x) for k, x in v.items()}
+        if isinstance(v, (tuple, list)):
+            return [plain(x) for x in v]
+        return v.item() if isinstance(v, np.generic) else v
+
+    with open(path, "w") as f:
+        json.dump([plain(dict(zip(names, r)) if names else r) for r in rows], f, indent=1, default=str)
+
+
 def median_ms(fn):
     for _ in range(WARM):
         fn()
@@ -67,7 +95,7 @@ def median_ms(fn):
         t0 = time.perf_counter()
         fn()
         ts.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(ts), min(ts), max(ts)
+    return Calls(ts)
 
 
 def make_pool(C, shape: str):
@@ -96,10 +124,13 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "index_blocks", "README.md"))
     ap.add_argument("--shapes", default="5,16,race,200,4096,65536,1048576")
     ap.add_argument("--calls", type=int, default=REPS)
+    ap.add_argument("--json")
+    ap.add_argument("--device-only", action="store_true",
+                    help="time the index call alone: the two CPU columns (19 s and 15 s a call at 2^20 blocks) read nan")
     args = ap.parse_args()
     REPS = args.calls
     C = cpu_lib()
-    rows = []
+    rows, tops = [], []
     with GpuMiner(0) as m:
         m.warmup()
         info = m.device_info()
@@ -127,8 +158,8 @@ def main():
                 sound = C.pool_ref_audit(pool, n, 0, ctypes.byref(n_tips), ctypes.byref(ref_best), ctypes.byref(hashed))
                 assert sound == n_tips.value == tips and hashed.value == walked, (sound, n_tips.value, hashed.value, walked)
 
-            c = median_ms(ref_call)
-            assert pool[ref_best.value].index == top
+            c = Calls([float("nan")]) if args.device_only else median_ms(ref_call)
+            assert args.device_only or pool[ref_best.value].index == top
 
             out = (Block * walked)()
             lengths = (ctypes.c_uint32 * tips)()
@@ -140,9 +171,10 @@ def main():
                 rc = check(L.pow_verify_chains(ctx, out, lengths, tips, 0, None, None, None, ctypes.byref(vbest)), L)
                 assert rc == 1
 
-            t = median_ms(today_call)
-            assert out[sum(lengths[:vbest.value])].index == top
+            t = Calls([float("nan")]) if args.device_only else median_ms(today_call)
+            assert args.device_only or out[sum(lengths[:vbest.value])].index == top
             rows.append((name, n, tips, walked, launches, g, kern, c, t))
+            tops.append(top)
             print(f"{name}: index call {g[0]:.3f} ms (kernel {kern:.3f}, {launches} launches), ref -O2 {c[0]:.3f} ms, "
                   f"today {t[0]:.3f} ms", flush=True)
             del out
@@ -170,6 +202,9 @@ def main():
     with open(args.out, "w") as f:
         f.write(text)
     print(text)
+    if args.json:
+        write_json(args.json, [r + (top,) for r, top in zip(rows, tops)],
+                   ("pool", "blocks", "tips", "walked", "launches", "index_call", "kernel_ms", "ref", "today", "best_index"))
 
 
 if __name__ == "__main__":

@@ -21,9 +21,10 @@ pow_get_stats' for that add.  Median [min, max] of 9 repetitions (or --calls)
 after 2 warm-up repetitions.  Where N + the arrival would pass
 POW_POOL_MAX_BLOCKS, the re-rank's and the run's pools are that much smaller
 (pools of their own, built the same way).  Writes the table to
-profiles/pool_stream/README.md (or --out) and prints it.
+profiles/pool_stream/README.md (or --out) and prints it; --json FILE keeps
+every timed call of every row.
 
-    python tools/pool_add_bench.py [--calls 9] [--out FILE] [--sizes 31,200,4096,65536,1048575]
+    python tools/pool_add_bench.py [--calls 9] [--out FILE] [--json FILE] [--sizes 31,200,4096,65536,1048575]
 """
 import argparse
 import ctypes
@@ -58,8 +59,7 @@ def cpu_lib():
     return C
 
 
-def stats_of(ts):
-    return statistics.median(ts), min(ts), max(ts)
+stats_of = ib.Calls  # (median, min, max); the calls are kept for --json
 
 
 def shuffled_pool(C, n):
@@ -101,6 +101,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pool_stream", "README.md"))
     ap.add_argument("--sizes", default="31,200,4096,65536,1048575")
     ap.add_argument("--calls", type=int, default=REPS)
+    ap.add_argument("--json")
     args = ap.parse_args()
     REPS = args.calls
     C = cpu_lib()
@@ -203,6 +204,8 @@ def main():
     with open(args.out, "w") as f:
         f.write(text)
     print(text)
+    if args.json:  # fast, rerank, five: (calls, kernel ms, launches, (size, best, best_index, capacity, slots))
+        ib.write_json(args.json, rows, ("size", "n1", "n2", "n5", "fast", "rerank", "five", "index", "ref"))
 
 
 if __name__ == "__main__":

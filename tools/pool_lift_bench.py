@@ -28,9 +28,10 @@ Host clock around every call; kernel ms and launches are pow_get_stats' for
 that call.  Median [min, max] of 9 repetitions (or --calls) after 2 warm-up
 repetitions; `first` is 3 repetitions, each on a pool of its own.  Every
 device answer is held against the host walk's before anything is reported.
-Writes the table to profiles/pool_lift/README.md (or --out) and prints it.
+Writes the table to profiles/pool_lift/README.md (or --out) and prints it; --json FILE keeps
+every timed call of every row.
 
-    python tools/pool_lift_bench.py [--calls 9] [--out FILE] [--sizes 31,200,4096,65536,1048560]
+    python tools/pool_lift_bench.py [--calls 9] [--out FILE] [--json FILE] [--sizes 31,200,4096,65536,1048560]
 """
 import argparse
 import ctypes
@@ -54,8 +55,7 @@ BS = ctypes.sizeof(Block)
 U32P = ctypes.POINTER(ctypes.c_uint32)
 
 
-def stats_of(ts):
-    return statistics.median(ts), min(ts), max(ts)
+stats_of = ib.Calls  # (median, min, max); the calls are kept for --json
 
 
 def timed(fn, reps):
@@ -85,6 +85,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pool_lift", "README.md"))
     ap.add_argument("--sizes", default="31,200,4096,65536,1048560")
     ap.add_argument("--calls", type=int, default=REPS)
+    ap.add_argument("--json")
     args = ap.parse_args()
     REPS = args.calls
     C = bind(ib.cpu_lib())
@@ -235,6 +236,8 @@ def main():
     with open(args.out, "w") as f:
         f.write(text)
     print(text)
+    if args.json:
+        ib.write_json(args.json, rows)
 
 
 if __name__ == "__main__":

@@ -22,7 +22,7 @@ re-added one (info and all four per-block results) before anything is
 reported.  Writes the table to profiles/pool_prune/README.md (or --out) and
 prints it.
 
-    python tools/pool_prune_bench.py [--calls 9] [--out FILE] [--sizes 31,200,4096,65536,1048575]
+    python tools/pool_prune_bench.py [--calls 9] [--out FILE] [--json FILE] [--sizes 31,200,4096,65536,1048575]
 """
 import argparse
 import ctypes
@@ -46,8 +46,7 @@ BS = ctypes.sizeof(Block)
 U32P = ctypes.POINTER(ctypes.c_uint32)
 
 
-def stats_of(ts):
-    return statistics.median(ts), min(ts), max(ts)
+stats_of = ib.Calls  # (median, min, max); the calls are kept for --json
 
 
 def device_bytes(cap: int, slots: int) -> int:
@@ -77,6 +76,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pool_prune", "README.md"))
     ap.add_argument("--sizes", default="31,200,4096,65536,1048575")
     ap.add_argument("--calls", type=int, default=REPS)
+    ap.add_argument("--json")
     args = ap.parse_args()
     REPS = args.calls
     C = ib.cpu_lib()
@@ -181,6 +181,8 @@ def main():
     with open(args.out, "w") as f:
         f.write(text)
     print(text)
+    if args.json:
+        ib.write_json(args.json, rows)
 
 
 if __name__ == "__main__":
