@@ -389,7 +389,9 @@ int pow_index_blocks(pow_ctx* ctx, const pow_block* pool, size_t n, unsigned dif
  * ancestor and the fork point of two chains run on the device:
  * pow_pool_chain, pow_pool_ancestors, pow_pool_fork_points below.  So do
  * which blocks lie under a tip, and dropping the forks that lost:
- * pow_pool_mark, pow_pool_prune below.
+ * pow_pool_mark, pow_pool_prune below; and the live tips, what stands on a
+ * block, and dropping a block with all that stands on it: pow_pool_tips,
+ * pow_pool_subtrees, pow_pool_drop below.
  * Lifetime and threads.  A pool is driven by its context's one thread.
  * Several pools may live on one context; pow_index_blocks and the verify calls
  * may be used between adds (they share the tile staging buffer and do not
@@ -615,6 +617,114 @@ typedef struct pow_pool_lift_info {
   uint64_t bytes;     /* device memory the table holds */
 } pow_pool_lift_info;
 int pow_pool_lift_get_info(const pow_pool* p, pow_pool_lift_info* out);
+
+/* "Which blocks are the live fork tips?", "what has been built on this block?"
+ * and "forget this block and everything built on it": the questions that look
+ * up the tree.  Every rank's last_block_in_chain is a tip (node.cpp:249); the
+ * blocks over a block are its confirmations and hold the tip a node that has
+ * committed to it should mine on; and valid_new_block's time window
+ * (node.cpp:199) is the caller's business, so a caller that rules a block out
+ * later needs a way to remove it, which pow_pool_prune (ancestors of seeds)
+ * cannot express.  All three are defined over what pow_pool_read returns, and
+ * answered on the device from it.  Nothing is hashed and no struct goes up.
+ * pow_pool_tips: block i is a tip when no block j has parent[j] == i.  A twin
+ * that is not the lowest of its name, and a POW_V_HASH block, have no name a
+ * child could find, so they are tips.  With POW_TIPS_SOUND_ONLY a tip must also
+ * have n_bad[i] == 0.  out takes the tips ascending by position; *n_tips is
+ * their total, also when it exceeds cap: then POW_ENOSPC is returned and out
+ * holds the first cap of them, as pow_find_seed does it.  Only out[0 ..
+ * min(cap, total)) is written.  Otherwise POW_OK.  An empty pool: 0 tips, no
+ * GPU work.
+ * pow_pool_subtrees: block i is a member of root r's subtree when r lies on
+ * the walk from i along parent; r itself is a member.  Per root q (every output
+ * k entries, each may be NULL): size[q] the members; height[q] the greatest
+ * depth[i] - depth[roots[q]] among them, 0 for a leaf; best[q], best_index[q]
+ * pow_index_blocks' fork choice among the members: of those with n_bad == 0 the
+ * greatest index, ties to the lowest position; POW_POOL_NONE and 0 if there is
+ * none.  on[i] (size bytes, may be NULL) is 1 when i is a member of any root's
+ * subtree and 0 otherwise, *n_on (may be NULL) the count of those.  Duplicate
+ * and nested roots are allowed.  The pool's answers do not change.  Returns
+ * POW_OK.  k == 0: no GPU work and no table work; on is all 0, *n_on 0.
+ * pow_pool_drop: the pool afterwards holds exactly the blocks that are in no
+ * root's subtree, in their old order.  map, info and the return value are
+ * pow_pool_prune's, and so is the contract: status, parent, depth, n_bad, best,
+ * n_flagged and pow_pool_find are byte for byte what pow_index_blocks gives on
+ * the surviving structs in that order, and after later adds on the survivors
+ * followed by everything added since.  Why: the complement of a union of
+ * subtrees is closed under parent (if i's parent were a member of r's subtree,
+ * r would lie on the parent's walk and so on i's), so every survivor keeps its
+ * whole walk, and the prune's argument applies from there.  For twins it needs
+ * one thing more: a dropped lower twin of a kept block names nobody that is
+ * kept, because a child of that name has the lower twin as its parent and is
+ * dropped with it.  A block that later names a dropped block is an orphan, as
+ * in that pow_index_blocks call.  Nothing dropped (k == 0, the only way: a
+ * root goes with its subtree): the pool is untouched, map is the identity,
+ * no GPU work and no table work.  Every block dropped: an empty pool, best
+ * POW_POOL_NONE.  A drop that drops something frees K13's table, as a prune
+ * does.
+ * How they run.  One bounded wait per call, and a second for a drop that
+ * keeps some blocks.  Tips: a byte per block is zeroed,
+ * every block sets its parent's (K14a), every block turns its own into "is a
+ * tip and passes the filter" (K14b), the bytes are counted per 256 blocks and
+ * scanned (K12c, K12d) and the marked positions gathered into a list (K14c);
+ * the total and min(cap, size) entries come down into pinned memory.  Subtrees:
+ * K13's table is brought up to date inside the call exactly as a K13 query
+ * does it (allocated by the first call that needs it), then one launch of
+ * ceil(size / 256) x k workgroups (K14d): lane (i, q) compares the two depths
+ * and, if i is not higher than the root, jumps depth[i] - depth[root] steps and
+ * compares what it finds with the root; the members are counted and their
+ * height and key reduced per wave, one atomic per wave and result.  With on or
+ * n_on the members also set a byte, and K12c and K12d count those.  Drop: the
+ * same launch clears the members' bytes in marks preset to 1, K12c and K12d
+ * count what is kept; then exactly what a prune does behind a mark that
+ * drops something: an empty pool, or behind one more bounded wait new arrays,
+ * K12e, K12f and K10b.  The scratch is K12's.
+ * Cost.  Launches (pow_get_stats; hashes = 0), with T the table's launches as
+ * under pow_pool_ancestors (0 when it is up to date, 1 after an add of at most
+ * 256 blocks that passed no power of two, max(ceil(log2 size) - 1, 0) when it
+ * is stale): tips 5; subtrees T + 1, and T + 3 with on or n_on; drop T + 3,
+ * and T + 6 when it keeps some blocks; drop with k == 0: none.  The one host
+ * loop is the check of the roots (and the identity map of a drop with k == 0).
+ * The tips' list comes down as min(cap, size) entries, since the total is not
+ * known before the wait: with cap = size at 2^20 blocks that copy (4 MB) is
+ * most of the call, so pass the cap that is needed.  pow_warmup does not launch
+ * these kernels.
+ * Measured (MI355X, profiles/pool_above/README.md; medians of 9 calls on
+ * shuffled pools at d = 0: a trunk of half the blocks and eight chains forking
+ * from its tip; the root asked for is the first block of a chain that lost,
+ * N / 16 blocks; against pow_pool_read of parent, depth and n_bad for the
+ * whole pool and numpy on the host, which is what a caller did before): tips
+ * with cap = N (kernels 0.03 ms at 2^20 - 16, the rest the list's copy)
+ * 60 us at N = 31, 57 us at 4,096, 75 us at 2^16, 0.15 ms at 2^20 - 16, against
+ * 40 us, 48 us, 0.15 ms and 2.2 ms for read and numpy: slower up to a few
+ * thousand blocks, 14x faster at 2^20 - 16.  One root with the table up to
+ * date 31, 34, 67 us and 0.59 ms (1 launch, kernel 0.57 ms: half a million
+ * lanes each jump up to 19 dependent reads through an 80 MB table); after a
+ * one-block add 50, 48, 88 us and 0.62 ms (2 launches), against 73 us, 0.21,
+ * 3.3 and 93 ms for read and numpy doubling: faster at every size measured.
+ * 64 roots, among them the pool's root: 33 us, 47 us, 0.55 ms and 12.1 ms; the
+ * launch grows with k x the members' jumps.  Drop (6 launches, the table up to
+ * date before and freed by it): 0.15, 0.16, 0.61 and 2.6 ms, against
+ * pow_pool_prune handed the seven tips of what stays (11 to 26 launches, no
+ * table to free): 0.15, 0.19, 0.44 and 1.2 ms.  So where the caller already
+ * knows the tips of everything it wants to keep, the prune is the faster way
+ * to say it from 2^16 blocks on; the drop is for the caller who knows the one
+ * block it wants gone.
+ * POW_EINVAL, in this order before the context is touched and with nothing
+ * written: a null pool; flag bits other than POW_TIPS_SOUND_ONLY; k >
+ * POW_POOL_MAX_ROOTS; null roots with k > 0 (for the tips: a null n_tips, or a
+ * null out with cap > 0); a root at or past size.  Then as every pool call:
+ * POW_EHIP on a pool that is unusable, POW_EINVAL on a context bound to a stop
+ * board.  A drop that fails with POW_EHIP leaves the pool unusable, as a failed
+ * prune does. */
+enum { POW_TIPS_SOUND_ONLY = 1 };
+#define POW_POOL_MAX_ROOTS 64
+int pow_pool_tips(pow_pool* p, unsigned flags, uint32_t* out, size_t cap, size_t* n_tips);
+int pow_pool_subtrees(pow_pool* p, const uint32_t* roots, size_t k, uint32_t* size, uint32_t* height, uint32_t* best,
+                      uint32_t* best_index /* k each, may be NULL */, uint8_t* on /* size bytes, may be NULL */,
+                      size_t* n_on /* may be NULL */);
+int pow_pool_drop(pow_pool* p, const uint32_t* roots, size_t k, uint32_t* map /* the size BEFORE the call, may be NULL */,
+                  pow_pool_info* info /* may be NULL */);
 
 /* Mining round: replaces node.cpp:302-308 (nonce -> hash -> test) for every
  * counter in [ctr_start, ctr_start + ctr_count).  The header fields and the

@@ -99,6 +99,7 @@ class PoolLiftInfo(ctypes.Structure):
 
 
 POW_KEEP_BY_INDEX, POW_KEEP_SOUND_ONLY, POOL_MAX_TIPS = 1, 2, 1 << 16  # pow_pool_mark, pow_pool_prune
+POW_TIPS_SOUND_ONLY, POOL_MAX_ROOTS = 1, 64  # pow_pool_tips; pow_pool_subtrees, pow_pool_drop
 POW_VALU_MIX, POW_VALU_FULL, POW_VALU_HALF = 0, 1, 2
 POW_LAUNCH_HIP, POW_LAUNCH_DIRECT = 0, 1
 
@@ -181,6 +182,14 @@ def load(test_hooks: bool = False) -> ctypes.CDLL:
         "pow_pool_chain": ([ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32),
                             c_sizep], ctypes.c_int),
         "pow_pool_lift_get_info": ([ctypes.c_void_p, ctypes.POINTER(PoolLiftInfo)], ctypes.c_int),
+        "pow_pool_tips": ([ctypes.c_void_p, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t, c_sizep],
+                          ctypes.c_int),
+        "pow_pool_subtrees": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t,
+                               ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+                               ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p,
+                               c_sizep], ctypes.c_int),
+        "pow_pool_drop": ([ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t,
+                           ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(PoolInfo)], ctypes.c_int),
         "pow_mine_chain": ([ctypes.c_void_p, P, ctypes.c_size_t, ctypes.c_uint, ctypes.c_uint32, c_u64p,
                             ctypes.c_uint64, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, P,
                             c_sizep, c_u64p], ctypes.c_int),
@@ -241,7 +250,7 @@ def load(test_hooks: bool = False) -> ctypes.CDLL:
 EXPORTS = ("pow_device_count", "pow_init", "pow_warmup", "pow_destroy", "pow_last_error", "pow_get_stats", "pow_launch_path",
            "pow_device_info", "pow_device_pci_bus_id",
            "pow_nonce_from_counter", "pow_block_to_bytes", "pow_solves_problem", "pow_hash_blocks",
-           "pow_hash_block", "pow_verify_chain", "pow_verify_chains", "pow_index_blocks", "pow_pool_open", "pow_pool_close", "pow_pool_add", "pow_pool_get_info", "pow_pool_read", "pow_pool_find", "pow_pool_mark", "pow_pool_prune", "pow_pool_ancestors", "pow_pool_fork_points", "pow_pool_chain", "pow_pool_lift_get_info", "pow_mine_chain", "pow_mine_batch", "pow_mine_race", "pow_mine_rand", "pow_rand_nonces", "pow_find_seed", "pow_mine", "pow_mine_any", "pow_cancel", "pow_sweep", "pow_sweep_device", "pow_dev_alloc", "pow_dev_free",
+           "pow_hash_block", "pow_verify_chain", "pow_verify_chains", "pow_index_blocks", "pow_pool_open", "pow_pool_close", "pow_pool_add", "pow_pool_get_info", "pow_pool_read", "pow_pool_find", "pow_pool_mark", "pow_pool_prune", "pow_pool_ancestors", "pow_pool_fork_points", "pow_pool_chain", "pow_pool_lift_get_info", "pow_pool_tips", "pow_pool_subtrees", "pow_pool_drop", "pow_mine_chain", "pow_mine_batch", "pow_mine_race", "pow_mine_rand", "pow_rand_nonces", "pow_find_seed", "pow_mine", "pow_mine_any", "pow_cancel", "pow_sweep", "pow_sweep_device", "pow_dev_alloc", "pow_dev_free",
            "pow_dev_read", "pow_valu_peak", "pow_valu_rate", "pow_valu_rate_ctx", "pow_group_partition", "pow_group_unique_id", "pow_group_init",
            "pow_group_init_within",
            "pow_group_init_custom", "pow_group_destroy", "pow_group_info", "pow_group_rccl_path", "pow_group_last_search",

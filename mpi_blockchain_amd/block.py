@@ -433,6 +433,60 @@ class BlockPool:
             i = self.parent[i]
         return walk
 
+    def tips(self, sound_only: bool = False) -> list[int]:
+        """The host statement of ``pow_pool_tips``: the positions no block has
+        as its ``parent``, ascending (`sound_only`: and ``n_bad == 0``)."""
+        named = set(self.parent)
+        return [i for i in range(len(self)) if i not in named and not (sound_only and self.n_bad[i])]
+
+    def _members(self, root: int) -> list[int]:
+        """The blocks whose walk along ``parent`` passes `root`, itself included, ascending."""
+        n = len(self)
+        state = [None] * n  # per block: is `root` on its walk
+        state[root] = True
+        for i in range(n):
+            walk = []
+            while i < n and state[i] is None:
+                walk.append(i)
+                i = self.parent[i]
+            for j in walk:
+                state[j] = i < n and state[i]
+        return [i for i in range(n) if state[i]]
+
+    def subtrees(self, roots):
+        """The host statement of ``pow_pool_subtrees``, as plain walks:
+        ``(size, height, best, best_index, on)``, the first four one entry per
+        root, `on` per block 1 if it is a member of any root's subtree.  A
+        root's members are the blocks whose walk passes it; ``best`` is the
+        fork choice among them (``POOL_NONE`` and index 0 if none is sound)."""
+        roots = [int(r) for r in roots]
+        self._at(*roots)
+        size, height, best, best_index, on = [], [], [], [], [0] * len(self)
+        for r in roots:
+            members = self._members(r)
+            pick = None
+            for i in members:
+                on[i] = 1
+                if self.n_bad[i] == 0 and (pick is None or self.index[i] > self.index[pick]):
+                    pick = i
+            size.append(len(members))
+            height.append(max(self.depth[i] for i in members) - self.depth[r])
+            best.append(POOL_NONE if pick is None else pick)
+            best_index.append(0 if pick is None else self.index[pick])
+        return size, height, best, best_index, on
+
+    def drop(self, roots) -> list[int]:
+        """The host statement of ``pow_pool_drop``: the pool loses every member
+        of every root's subtree and keeps the rest in its order; returns the
+        map as :meth:`prune` does.  What is kept is closed under ``parent``
+        and is exactly what its own tips mark, so the prune does the rest."""
+        on = self.subtrees(roots)[4]
+        keep = [i for i in range(len(self)) if not on[i]]
+        if len(keep) == len(self):
+            self.adopted = 0
+            return list(range(len(self)))
+        return self.prune(tips=keep)
+
 
 def prune_structs(blocks, new):
     """The survivors of a prune in their order: the blocks whose entry in

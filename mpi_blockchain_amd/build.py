@@ -20,8 +20,8 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libpow_gpu.so")
 # In link order; every library links its sources in this order (the shipped one without TEST_ONLY).
 SOURCES = ["pow_board.cpp", "pow_kernels.hip", "pow_sort.hip", "valu_peak.hip", "pow_api.cpp", "pow_group.cpp", "pow_host.cpp",
-           "pow_verify.hip", "pow_verify_batch.hip", "pow_chain.hip", "pow_batch.hip", "pow_race.hip", "pow_rand.hip", "pow_seed.hip", "pow_pool.hip", "pow_pool_live.hip", "pow_pool_prune.hip", "pow_pool_lift.hip", "pow_hooks.cpp", "pow_aql.cpp", "pow_test_kernels.hip"]
-HEADERS = ["pow_template.h", "sha256_dev.h", "pow_aql.h", "pow_host.h", "pow_ctx.h", "pow_walk_dev.h", "pow_rand_dev.h", "pow_audit_dev.h", "pow_pool_dev.h", "pow_lift_dev.h"]
+           "pow_verify.hip", "pow_verify_batch.hip", "pow_chain.hip", "pow_batch.hip", "pow_race.hip", "pow_rand.hip", "pow_seed.hip", "pow_pool.hip", "pow_pool_live.hip", "pow_pool_prune.hip", "pow_pool_lift.hip", "pow_pool_above.hip", "pow_hooks.cpp", "pow_aql.cpp", "pow_test_kernels.hip"]
+HEADERS = ["pow_template.h", "sha256_dev.h", "pow_aql.h", "pow_host.h", "pow_ctx.h", "pow_walk_dev.h", "pow_rand_dev.h", "pow_audit_dev.h", "pow_pool_dev.h", "pow_lift_dev.h", "pow_above_dev.h"]
 INCLUDES = [os.path.join(ROOT, "include", h) for h in ("pow_gpu.h", "pow_tools.h")]
 ARCH = "gfx950"
 

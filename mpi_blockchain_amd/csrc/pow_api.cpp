@@ -11,6 +11,7 @@
 #include <sys/prctl.h>
 
 #include <algorithm>
+#include <numeric>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -753,6 +754,7 @@ struct pow_pool {
   uint32_t fin = 0;            // which of depth[], bad[] hold the final values
   uint32_t gen = 0;            // bumped when an old block's walk or position may have changed: a re-rank, a prune that drops
   bool dead = false;           // an add failed half way: every later call is POW_EHIP
+  bool keep_ready = false;     // pow_pool_drop's hand-over to the prune: the marks and their count stand, as a mark leaves them
   PowPoolLivePlan plan{};      // the arrays' offsets at the present capacity
   DevBuf<uint32_t> d_arr;      // the arrays (plan.words)
   DevBuf<uint32_t> d_table;    // the table (slots)
@@ -824,6 +826,25 @@ hipError_t pow_queue_pool_lift(hipStream_t stream, const uint32_t* parent, uint3
     QUEUE_OK(pow_launch_pool_lift_row(stream, parent, up, capacity, j, 0, n, n));
   *work += (uint64_t)n * (rows - have);
   return hipSuccess;
+}
+
+// The marks lie in depth[1 - fin], the partials' scan in next[1], the list in next[0].
+hipError_t pow_queue_pool_tips(hipStream_t stream, const PowPoolDev& D, uint32_t fin, uint32_t flags) {
+  QUEUE_OK(hipMemsetAsync(D.depth[fin ^ 1u], 0, (size_t)((D.n + 3u) / 4u) * sizeof(uint32_t), stream));
+  QUEUE_OK(pow_launch_pool_above_child(stream, D, fin));
+  QUEUE_OK(pow_launch_pool_above_tip(stream, D, fin, (flags & POW_TIPS_SOUND_ONLY) ? 1u : 0u));
+  QUEUE_OK(pow_launch_pool_above_count(stream, D, fin));
+  return pow_launch_pool_above_gather(stream, D, fin);
+}
+
+// K12c counts whole words: the marks past D.n stay zero under the keep-marks' preset.
+hipError_t pow_queue_pool_above(hipStream_t stream, const PowPoolDev& D, uint32_t fin, const PowLiftView& v,
+                                const uint32_t* d_roots, uint32_t k, PowAboveAcc* d_acc, bool marks, bool keep) {
+  QUEUE_OK(hipMemsetAsync(d_acc, 0, (size_t)k * sizeof(PowAboveAcc), stream));
+  if (marks) QUEUE_OK(hipMemsetAsync(D.depth[fin ^ 1u], 0, (size_t)((D.n + 3u) / 4u) * sizeof(uint32_t), stream));
+  if (marks && keep) QUEUE_OK(hipMemsetAsync(D.depth[fin ^ 1u], 1, D.n, stream));
+  QUEUE_OK(pow_launch_pool_above_subtree(stream, D, fin, v, d_roots, k, d_acc, marks, keep ? 0u : 1u));
+  return marks ? pow_launch_pool_above_count(stream, D, fin) : hipSuccess;
 }
 
 extern "C" {
@@ -1113,10 +1134,22 @@ static int pool_mark_args(const pow_pool* p, const uint32_t* tips, size_t n_tips
 
 // One timed section over a pool that holds blocks: the tips up (d_find), the
 // mark's launches (pow_queue_pool_mark), then the control words and, if asked
-// for, the marks down.
+// for, the marks down.  Behind pow_pool_drop (keep_ready, which only that call
+// sets, around a prune with no seeds of its own) there is nothing to run: its
+// section has left the marks in depth[1 - fin], the partials' scan in next[1]
+// and the total in h_ctl, which is all a prune that drops something reads of a
+// mark; and a drop of at least one root always drops something.
 static int pool_mark_run(pow_pool* p, const uint32_t* tips, uint32_t n_tips, uint32_t min_index, unsigned flags,
                          uint8_t* on, uint32_t* marked) {
   pow_ctx* const ctx = p->ctx;
+  if (p->keep_ready) {
+    p->keep_ready = false;
+    if (tips || n_tips || flags || on || p->h_ctl.p->marked >= p->size)
+      return fail(POW_EHIP, "pow_pool_drop's keep-marks met a prune that is not its own (%u of %u kept)",
+                  p->h_ctl.p->marked, p->size);
+    *marked = p->h_ctl.p->marked;
+    return POW_OK;
+  }
   const uint32_t n = p->size, rounds = pow_pool_rounds(n);
   const PowPoolDev D = pool_dev(p, n);
   RESERVE(p->d_find, std::max<size_t>(n_tips, 1));
@@ -1324,6 +1357,150 @@ int pow_pool_lift_get_info(const pow_pool* p, pow_pool_lift_info* out) {
   *out = pow_pool_lift_info{covered, pow_pool_lift_rows(covered), t.capacity, t.rebuilt, t.extended,
                             pow_pool_lift_bytes(t.capacity)};
   return POW_OK;
+}
+
+// ---- pow_pool_tips, pow_pool_subtrees, pow_pool_drop (K14) ----
+
+// One timed section: the tips' launches (pow_queue_pool_tips), then the control
+// words and the head of the list down into pinned memory.  The caller's array is
+// written once the wait has passed and the total is known: never past it.
+int pow_pool_tips(pow_pool* p, unsigned flags, uint32_t* out, size_t cap, size_t* n_tips) {
+  if (!p) return fail(POW_EINVAL, "null pool");
+  if (flags & ~(unsigned)POW_TIPS_SOUND_ONLY) return fail(POW_EINVAL, "unknown flags 0x%x", flags);
+  if (!n_tips || (!out && cap)) return fail(POW_EINVAL, "null");
+  if (int rc = pool_ready(p, "pow_pool_tips")) return rc;
+  pow_ctx* const ctx = p->ctx;
+  ctx->stats = pow_stats{};
+  *n_tips = 0;
+  const uint32_t n = p->size;
+  if (n == 0) return POW_OK;
+  const size_t room = std::min<size_t>(cap, n);
+  RESERVE(p->lift.h_io, std::max<size_t>(room, 1));
+  const PowPoolDev D = pool_dev(p, n);
+  PowPoolLiveCtl* const ctl = p->h_ctl.p;
+  if (int rc = timed_begin(ctx)) return rc;
+  HIP_OK(pow_queue_pool_tips(ctx->stream, D, p->fin, flags));
+  HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+  HIP_OK(hipMemcpyAsync(ctl, D.ctl, sizeof(PowPoolLiveCtl), hipMemcpyDeviceToHost, ctx->stream));
+  if (room)
+    HIP_OK(hipMemcpyAsync(p->lift.h_io.p, D.next[0], room * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  // + 100 ns per block and launch
+  if (int rc = timed_end(ctx, "pool tips kernels", 500ull * n, 5u, &ctx->stats)) return rc;
+  const size_t total = ctl->marked;
+  if (room) memcpy(out, p->lift.h_io.p, std::min(room, total) * sizeof(uint32_t));
+  *n_tips = total;
+  return total > cap ? fail(POW_ENOSPC, "%zu tips > cap %zu", total, cap) : POW_OK;
+}
+
+// The argument checks of pow_pool_subtrees and pow_pool_drop behind the pool's,
+// in the header's order.  The one host loop over the roots.
+static int pool_above_args(const pow_pool* p, const uint32_t* roots, size_t k) {
+  if (k > POW_POOL_MAX_ROOTS) return fail(POW_EINVAL, "too many roots (%zu > %d)", k, POW_POOL_MAX_ROOTS);
+  if (!roots && k) return fail(POW_EINVAL, "null roots");
+  for (size_t q = 0; q < k; ++q)
+    if (roots[q] >= p->size) return fail(POW_EINVAL, "root %zu (block %u) past the pool's %u", q, roots[q], p->size);
+  return POW_OK;
+}
+
+// One timed section over a pool that holds blocks, for k >= 1 roots: the table
+// made ready as pool_lift_run makes it, the roots up (d_find: the k records,
+// then the roots; h_io is its pinned twin), the table's launches
+// (pool_lift_update), the subtrees' (pow_queue_pool_above), the records down
+// into h_io and, with `marks`, the control words and (on != nullptr) the marks.
+static int pool_above_run(pow_pool* p, const char* what, const uint32_t* roots, uint32_t k, bool marks, bool keep,
+                          uint8_t* on, uint32_t* marked) {
+  pow_ctx* const ctx = p->ctx;
+  PowPoolLift& t = p->lift;
+  const uint32_t n = p->size;
+  const bool stale = t.covered == 0 || t.capacity == 0 || t.gen != p->gen || t.covered > n || p->plan.cap > t.capacity;
+  if (t.capacity < p->plan.cap) {  // the first call that needs it, or the pool has outgrown it: not copied, made again
+    t.release_table();
+    RESERVE(t.d_up, (size_t)p->plan.cap * pow_pool_lift_rows(p->plan.cap));
+    t.capacity = p->plan.cap;
+  }
+  const uint32_t covered = stale ? 0u : t.covered;
+  t.covered = 0;  // until the launches are through
+  RESERVE(p->d_find, 5 * (size_t)k);
+  RESERVE(t.h_io, 5 * (size_t)k);
+  PowAboveAcc* const d_acc = (PowAboveAcc*)p->d_find.p;
+  uint32_t* const d_roots = p->d_find.p + 4 * (size_t)k;
+  uint32_t* const h_roots = t.h_io.p + 4 * (size_t)k;
+  memcpy(h_roots, roots, (size_t)k * sizeof(uint32_t));
+  HIP_OK(hipMemcpyAsync(d_roots, h_roots, (size_t)k * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+  const PowPoolDev D = pool_dev(p, n);
+  const PowLiftView v{D.parent, D.depth[p->fin], t.d_up.p, t.capacity, n, pow_pool_rounds(n)};
+  PowPoolLiveCtl* const ctl = p->h_ctl.p;
+  uint32_t launches = 0;
+  uint64_t work = 0;
+  if (int rc = timed_begin(ctx)) return rc;
+  if (int rc = pool_lift_update(p, covered, stale, &launches, &work)) return rc;
+  HIP_OK(pow_queue_pool_above(ctx->stream, D, p->fin, v, d_roots, k, d_acc, marks, keep));
+  HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+  HIP_OK(hipMemcpyAsync(t.h_io.p, d_acc, (size_t)k * sizeof(PowAboveAcc), hipMemcpyDeviceToHost, ctx->stream));
+  if (marks) HIP_OK(hipMemcpyAsync(ctl, D.ctl, sizeof(PowPoolLiveCtl), hipMemcpyDeviceToHost, ctx->stream));
+  if (on) HIP_OK(hipMemcpyAsync(on, D.depth[p->fin ^ 1u], n, hipMemcpyDeviceToHost, ctx->stream));
+  // + 100 ns per lane and launch
+  if (int rc = timed_end(ctx, what, 100ull * (work + (uint64_t)n * (k + (marks ? 2u : 0u))),
+                         launches + (marks ? 3u : 1u), &ctx->stats))
+    return rc;
+  t.covered = n;
+  t.gen = p->gen;
+  if (marks) *marked = ctl->marked;
+  return POW_OK;
+}
+
+int pow_pool_subtrees(pow_pool* p, const uint32_t* roots, size_t k, uint32_t* size, uint32_t* height, uint32_t* best,
+                      uint32_t* best_index, uint8_t* on, size_t* n_on) {
+  if (!p) return fail(POW_EINVAL, "null pool");
+  if (int rc = pool_above_args(p, roots, k)) return rc;
+  if (int rc = pool_ready(p, "pow_pool_subtrees")) return rc;
+  p->ctx->stats = pow_stats{};
+  uint32_t marked = 0;
+  if (k == 0) {  // no root, no member
+    if (on && p->size) memset(on, 0, p->size);
+  } else {
+    if (int rc = pool_above_run(p, "pool subtree kernels", roots, (uint32_t)k, on || n_on, false, on, &marked)) return rc;
+    const PowAboveAcc* const acc = (const PowAboveAcc*)p->lift.h_io.p;
+    for (size_t q = 0; q < k; ++q) {
+      if (size) size[q] = acc[q].size;
+      if (height) height[q] = acc[q].height;
+      if (best) best[q] = acc[q].best ? (uint32_t)~(uint32_t)acc[q].best : POW_POOL_NONE;
+      if (best_index) best_index[q] = (uint32_t)(acc[q].best >> 32);
+    }
+  }
+  if (n_on) *n_on = marked;
+  return POW_OK;
+}
+
+// The keep-marks' section (every block but the roots' members, counted and
+// scanned as a mark's are), then the prune's own second half: pow_pool_prune
+// takes the marks as they stand (keep_ready) and goes on by their total as it
+// always does; a root is a member of its own subtree, so something is always
+// dropped and the prune never takes its "everything marked" way.  No roots:
+// nothing goes, no GPU work; the identity map is written here.
+int pow_pool_drop(pow_pool* p, const uint32_t* roots, size_t k, uint32_t* map, pow_pool_info* info) {
+  if (!p) return fail(POW_EINVAL, "null pool");
+  if (int rc = pool_above_args(p, roots, k)) return rc;
+  if (int rc = pool_ready(p, "pow_pool_drop")) return rc;
+  pow_ctx* const ctx = p->ctx;
+  ctx->stats = pow_stats{};
+  if (k == 0) {
+    if (map) std::iota(map, map + p->size, 0u);
+    p->info.adopted = p->info.reranked = p->info.rehashed = 0;
+    if (info) *info = p->info;
+    return p->info.n_flagged == 0 ? 1 : 0;
+  }
+  uint32_t kept = 0;
+  p->dead = true;  // until the drop has gone through
+  if (int rc = pool_above_run(p, "pool drop kernels", roots, (uint32_t)k, true, true, nullptr, &kept)) return rc;
+  const pow_stats first = ctx->stats;
+  p->dead = false;
+  p->keep_ready = true;
+  const int rc = pow_pool_prune(p, nullptr, 0, 0, 0, map, info);
+  p->keep_ready = false;
+  ctx->stats.kernel_ms += first.kernel_ms;
+  ctx->stats.launches += first.launches;
+  return rc;
 }
 
 int pow_sweep_device(pow_ctx* ctx, const pow_block* tmpl, uint64_t ctr_start, uint64_t ctr_count,

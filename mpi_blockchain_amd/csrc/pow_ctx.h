@@ -303,6 +303,14 @@ inline PowPoolDev pow_pool_live_dev(uint32_t* base, const PowPoolLivePlan& p, ui
                     table, n, slots};
 }
 
+// K14 (pow_pool_above.hip): one root's record of pow_pool_subtrees and pow_pool_drop, zeroed by the host before K14d.
+struct PowAboveAcc {
+  unsigned long long best;  // K10e's key over the members with n_bad == 0 (atomic max); 0 = none
+  unsigned int size;        // the members (atomic add)
+  unsigned int height;      // the greatest depth over the root's among them (atomic max)
+};
+static_assert(sizeof(PowAboveAcc) == 16, "four words a root in d_find");
+
 struct pow_ctx {
   int device = 0;
   int cu_count = 0;
@@ -488,6 +496,15 @@ hipError_t pow_launch_pool_lift_ancestor(hipStream_t stream, const PowLiftView& 
                                          const uint32_t* steps, uint32_t tip, uint32_t* out);
 hipError_t pow_launch_pool_lift_fork(hipStream_t stream, const PowLiftView& v, uint32_t k, const uint32_t* a,
                                      const uint32_t* b, uint32_t* at, uint32_t* back_a, uint32_t* back_b);
+// K14 (pow_pool_above.hip), the kernels of pow_pool_tips, pow_pool_subtrees and pow_pool_drop.  The marks lie in
+// depth[1 - fin], as K12's.  _count is K12c and K12d behind each other on those marks.
+hipError_t pow_launch_pool_above_child(hipStream_t stream, const PowPoolDev& D, uint32_t fin);
+hipError_t pow_launch_pool_above_tip(hipStream_t stream, const PowPoolDev& D, uint32_t fin, uint32_t sound_only);
+hipError_t pow_launch_pool_above_count(hipStream_t stream, const PowPoolDev& D, uint32_t fin);
+hipError_t pow_launch_pool_above_gather(hipStream_t stream, const PowPoolDev& D, uint32_t fin);
+hipError_t pow_launch_pool_above_subtree(hipStream_t stream, const PowPoolDev& D, uint32_t fin, const PowLiftView& v,
+                                         const uint32_t* roots, uint32_t k, PowAboveAcc* acc, bool marks,
+                                         uint32_t value);
 // The launch sequences of K10, K12 and K13 that more than one caller queues (pow_api.cpp), each stated once: the
 // library's calls and the test library's hooks run these.  As the wrappers above: a stream and views, the first
 // failing hipError_t; none waits, records an event or copies to the host.
@@ -505,6 +522,14 @@ hipError_t pow_queue_pool_compact(hipStream_t stream, const PowPoolDev& F, const
 // *launches is incremented per launch queued (pow_pool_lift_launches is its closed form), *work by its lanes.
 hipError_t pow_queue_pool_lift(hipStream_t stream, const uint32_t* parent, uint32_t* up, uint32_t capacity,
                                uint32_t covered, uint32_t n, bool stale, uint32_t* launches, uint64_t* work);
+// K14's two sequences.  The tips: the marks' reset, K14a, K14b, K12c, K12d and K14c; the list lies in next[0], its
+// length in the control words' `marked`.
+hipError_t pow_queue_pool_tips(hipStream_t stream, const PowPoolDev& D, uint32_t fin, uint32_t flags);
+// The subtrees of k >= 1 roots (d_roots), behind a table that is up to date: the records' reset, and with `marks`
+// the marks' (to 0; with `keep` then to 1 over the D.n blocks, the tail of the last word staying 0); K14d, whose
+// members store 1, or 0 with `keep`; with `marks` K12c and K12d on what it left.
+hipError_t pow_queue_pool_above(hipStream_t stream, const PowPoolDev& D, uint32_t fin, const PowLiftView& v,
+                                const uint32_t* d_roots, uint32_t k, PowAboveAcc* d_acc, bool marks, bool keep);
 hipError_t pow_sort_u32(void* temp, size_t* temp_bytes, uint32_t* keys, uint32_t* alt, uint32_t n,
                         uint32_t** sorted, hipStream_t stream);
 hipError_t pow_launch_search_lat(bool full, bool any, bool asm_groups, unsigned grid, hipStream_t stream,

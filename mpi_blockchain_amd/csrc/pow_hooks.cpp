@@ -4,8 +4,9 @@
 // pow_init, the direct-dispatch launch path (pow_aql.cpp, POW_AQL=1), the stall
 // kernel of the watchdog tests, the stand-in RCCL of the shard tests and
 // the exports the shipped library does not have: pow_test_leading_zero_bits,
-// pow_test_pool_rank, pow_test_pool_prune and pow_test_pool_lift (K10d/K10e, K12
-// and K13 on trees of the caller's making, up to POW_POOL_MAX_BLOCKS nodes).
+// pow_test_pool_rank, pow_test_pool_prune, pow_test_pool_lift and
+// pow_test_pool_above (K10d/K10e, K12, K13 and K14 on trees of the caller's
+// making, up to POW_POOL_MAX_BLOCKS nodes).
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -493,5 +494,144 @@ extern "C" int pow_test_pool_lift(pow_ctx* ctx, size_t n, const pow_test_lift_io
   if (rc == POW_OK && io->launches) *io->launches = launches;
   if (waited == POW_OK || !ctx->wedged)  // after a watchdog the launches may still write
     (void)hipFree(d_parent), (void)hipFree(d_depth), (void)hipFree(d_up), (void)hipFree(d_io);
+  return rc;
+}
+
+// What pow_test_pool_above takes and gives: arrays of n entries unless said.
+// An output that is null is not written.
+struct pow_test_above_io {
+  // in: a forest of the caller's making, as K10 and K11 would have left it (every status 0)
+  const uint32_t* parent;  // a position below n, POW_POOL_ROOT or POW_POOL_NONE
+  const uint32_t* depth;   // the nodes on the walk from each, itself included
+  const uint32_t* index;
+  const uint32_t* n_bad;
+  const uint32_t* roots;   // k positions below n (modes 1 and 2)
+  size_t k;                // 1..POW_POOL_MAX_ROOTS in modes 1 and 2
+  uint32_t mode;           // 0: pow_pool_tips; 1: pow_pool_subtrees with on[]; 2: pow_pool_drop
+  uint32_t flags;          // mode 0: POW_TIPS_SOUND_ONLY
+  uint32_t fin;            // 0 or 1: which of depth[], bad[] hold the final values; the others are the scratch
+  uint32_t pad;
+  // out
+  uint8_t* marks;          // mode 0: the tip marks; 1: on[]; 2: the keep-marks
+  uint32_t* total;         // one word: K12d's total of those marks
+  uint32_t* list;          // mode 0: K14c's list, the first `total` entries (room for n)
+  uint32_t* size;          // modes 1, 2: k each, K14d's records
+  uint32_t* height;
+  unsigned long long* best;  // k: the key as K14d left it (0: none)
+  uint32_t* map;           // mode 2: K12e's newpos
+  uint32_t* parent_out;    // mode 2: the first `total` entries of what K12e and K12f left
+  uint32_t* depth_out;
+};
+static_assert(sizeof(pow_test_above_io) == 17 * 8, "tests/pool_above_util.py AboveIO");
+
+// K14 (pow_pool_above.hip) on a forest of the caller's choosing, with no pool,
+// no hashing and no name table: the library's own sequences.  Mode 0:
+// pow_queue_pool_tips.  Modes 1 and 2: K13's table made from nothing
+// (pow_queue_pool_lift), then pow_queue_pool_above, as pool_above_run queues
+// them; mode 2 goes on as pow_pool_drop does through the prune's second half,
+// by K12d's total (a root is dropped with its subtree, so never everything kept):
+// new arrays at pow_pool_prune_cap's capacity and pow_queue_pool_compact over a
+// view with no table (K12e, K12f; K10b is not run), behind a second bounded wait.
+extern "C" int pow_test_pool_above(pow_ctx* ctx, size_t n, const pow_test_above_io* io) {
+  if (n > POW_POOL_MAX_BLOCKS) return fail(POW_EINVAL, "too many nodes (%zu > 2^20)", n);
+  if (!ctx || !io) return fail(POW_EINVAL, "null");
+  if (io->mode > 2u) return fail(POW_EINVAL, "unknown mode %u", io->mode);
+  if (io->flags & ~(uint32_t)POW_TIPS_SOUND_ONLY) return fail(POW_EINVAL, "unknown flags 0x%x", io->flags);
+  if (io->fin > 1u) return fail(POW_EINVAL, "fin %u > 1", io->fin);
+  if (io->mode && (io->k == 0 || io->k > POW_POOL_MAX_ROOTS || !io->roots))
+    return fail(POW_EINVAL, "1..%d roots", POW_POOL_MAX_ROOTS);
+  if ((!io->parent || !io->depth || !io->index || !io->n_bad) && n) return fail(POW_EINVAL, "null");
+  for (size_t q = 0; io->mode && q < io->k; ++q)
+    if (io->roots[q] >= n) return fail(POW_EINVAL, "root %zu (node %u) past the forest's %zu", q, io->roots[q], n);
+  for (size_t i = 0; i < n; ++i)
+    if (io->parent[i] >= n && io->parent[i] < POW_POOL_NONE)
+      return fail(POW_EINVAL, "parent %u of node %zu is neither a node nor an end", io->parent[i], i);
+  if (n == 0) return POW_OK;
+  HIP_OK(hipSetDevice(ctx->device));
+  const uint32_t n32 = (uint32_t)n, fin = io->fin, k = io->mode ? (uint32_t)io->k : 0u;
+  const PowPoolLivePlan from = pow_pool_live_plan(n32);
+  const size_t words = (size_t)n32 * sizeof(uint32_t);
+  const size_t up_words = std::max<size_t>((size_t)n32 * pow_pool_lift_rows(n32), 1);
+  uint32_t* base = nullptr;
+  uint32_t* to_base = nullptr;
+  uint32_t* d_up = nullptr;
+  uint32_t* d_find = nullptr;  // the k records, then the roots, as pool_above_run lays them out
+  std::vector<PowAboveAcc> acc(std::max<uint32_t>(k, 1));
+  PowPoolLiveCtl ctl{};
+  int rc = POW_OK;
+  auto step = [&](hipError_t e, const char* what) {
+    if (rc == POW_OK && e != hipSuccess) rc = fail(POW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
+  };
+  auto release = [&](int waited) {  // after a watchdog the launches may still write
+    if (waited == POW_OK || !ctx->wedged) (void)hipFree(base), (void)hipFree(to_base), (void)hipFree(d_up), (void)hipFree(d_find);
+  };
+  step(hipMalloc(&base, from.words * sizeof(uint32_t)), "hipMalloc");
+  step(hipMalloc(&d_up, up_words * sizeof(uint32_t)), "hipMalloc");
+  step(hipMalloc(&d_find, (5 * (size_t)std::max<uint32_t>(k, 1)) * sizeof(uint32_t)), "hipMalloc");
+  if (rc != POW_OK) {
+    release(POW_OK);
+    return rc;
+  }
+  const PowPoolDev F = pow_pool_live_dev(base, from, nullptr, n32, 0);
+  PowAboveAcc* const d_acc = (PowAboveAcc*)d_find;
+  uint32_t* const d_roots = d_find + 4 * (size_t)k;
+  auto up = [&](void* dst, const void* src, size_t bytes) {
+    if (rc == POW_OK && src && bytes) step(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream), "copy in");
+  };
+  auto down = [&](void* dst, const void* src, size_t bytes) {
+    if (rc == POW_OK && dst && bytes) step(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream), "copy out");
+  };
+  step(hipMemsetAsync(base, 0, from.words * sizeof(uint32_t), ctx->stream), "reset");  // status, kind, digests, names
+  step(hipMemsetAsync(d_up, 0xEE, up_words * sizeof(uint32_t), ctx->stream), "reset");  // past every size, as the lift hook's
+  up(F.parent, io->parent, words), up(F.index, io->index, words), up(F.bad[fin], io->n_bad, words);
+  up(F.depth[fin], io->depth, words), up(d_roots, io->roots, (size_t)k * sizeof(uint32_t));
+  uint32_t launches = 0;
+  uint64_t work = 0;
+  if (rc == POW_OK && io->mode == 0u) step(pow_queue_pool_tips(ctx->stream, F, fin, io->flags), "K14a, K14b, K12c, K12d, K14c");
+  if (rc == POW_OK && io->mode) {
+    const PowLiftView v{F.parent, F.depth[fin], d_up, n32, n32, pow_pool_rounds(n32)};
+    step(pow_queue_pool_lift(ctx->stream, F.parent, d_up, n32, 0, n32, true, &launches, &work), "K13a");
+    if (rc == POW_OK) step(pow_queue_pool_above(ctx->stream, F, fin, v, d_roots, k, d_acc, true, io->mode == 2u), "K14d, K12c, K12d");
+    down(acc.data(), d_acc, (size_t)k * sizeof(PowAboveAcc));
+  }
+  down(&ctl, F.ctl, sizeof ctl), down(io->marks, F.depth[fin ^ 1u], n);
+  // the list comes down whole: what lies past the total is scratch, and the caller's array has room for n
+  if (io->mode == 0u) down(io->list, F.next[0], words);
+  int waited = pow_ctx_stream_wait(ctx, "pow_test_pool_above", 100ull * (work + (uint64_t)n32 * (k + 5ull)));
+  if (rc == POW_OK) rc = waited;
+  if (rc == POW_OK && ctl.marked > n32) rc = fail(POW_EHIP, "K12d counted %u marks on %u nodes", ctl.marked, n32);
+  if (rc != POW_OK) {
+    release(waited);
+    return rc;
+  }
+  const uint32_t kept = ctl.marked;
+  if (io->total) *io->total = kept;
+  for (uint32_t q = 0; q < k; ++q) {
+    if (io->size) io->size[q] = acc[q].size;
+    if (io->height) io->height[q] = acc[q].height;
+    if (io->best) io->best[q] = acc[q].best;
+  }
+  if (io->mode != 2u) {
+    release(waited);
+    return rc;
+  }
+  if (kept >= n32) {  // a root is a member of its own subtree
+    release(waited);
+    return fail(POW_EHIP, "K14d kept all %u nodes under %u roots", n32, k);
+  }
+  const uint32_t cap = pow_pool_prune_cap(kept, pow_pool_live_first_cap(0, ctx->pool_first_cap));
+  const PowPoolLivePlan to = pow_pool_live_plan(cap);
+  step(hipMalloc(&to_base, to.words * sizeof(uint32_t)), "hipMalloc");
+  if (rc != POW_OK) {
+    release(POW_OK);
+    return rc;
+  }
+  const PowPoolDev T = pow_pool_live_dev(to_base, to, nullptr, kept, 0);
+  const size_t kw = (size_t)kept * sizeof(uint32_t);
+  step(pow_queue_pool_compact(ctx->stream, F, T, cap, fin, io->map != nullptr), "K12e, K12f");  // no table: no K10b
+  down(io->map, F.next[0], words), down(io->parent_out, T.parent, kw), down(io->depth_out, T.depth[fin], kw);
+  waited = pow_ctx_stream_wait(ctx, "pow_test_pool_above (gather)", 100ull * (n + 2ull * kept));
+  if (rc == POW_OK) rc = waited;
+  release(waited);
   return rc;
 }

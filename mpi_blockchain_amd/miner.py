@@ -13,8 +13,9 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import (HASH_SIZE, NONCE_SIZE, POOL_NONE, POW_KEEP_BY_INDEX, POW_KEEP_SOUND_ONLY, SEED_MAX_SEEDS,
-                   SEED_MAX_TARGETS, Block, PoolInfo, PoolLiftInfo, PowStats, SeedMatchRec, check, load)
+from ._lib import (HASH_SIZE, NONCE_SIZE, POOL_NONE, POW_ENOSPC, POW_KEEP_BY_INDEX, POW_KEEP_SOUND_ONLY,
+                   POW_TIPS_SOUND_ONLY, SEED_MAX_SEEDS, SEED_MAX_TARGETS, Block, PoolInfo, PoolLiftInfo, PowStats,
+                   SeedMatchRec, check, load)
 from .block import DEFAULT_DIFFICULTY, field, nonce_from_counter
 
 
@@ -295,6 +296,55 @@ class GpuPool:
         check(self.L.pow_pool_chain(self.handle, int(tip), room, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
                                     ctypes.byref(n)), self.L)
         return out[:n.value]
+
+    def tips(self, sound_only: bool = False, cap: int | None = None) -> np.ndarray:
+        """pow_pool_tips: the positions nobody names as a parent, ascending, as
+        ``numpy.uint32`` (`sound_only`: only those with ``n_bad == 0``).  With
+        `cap` at most that many; ``self.n_tips`` holds the total of the last
+        call either way.  The host statement is :meth:`block.BlockPool.tips`."""
+        room = len(self) if cap is None else int(cap)
+        out = np.zeros(max(room, 1), dtype=np.uint32)
+        n = ctypes.c_size_t()
+        rc = self.L.pow_pool_tips(self.handle, POW_TIPS_SOUND_ONLY if sound_only else 0,
+                                  out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), room, ctypes.byref(n))
+        if rc != POW_ENOSPC:
+            check(rc, self.L)
+        self.n_tips = n.value
+        return out[:min(room, n.value)]
+
+    def subtrees(self, roots, marks: bool = False):
+        """pow_pool_subtrees: ``(size, height, best, best_index)`` per root as
+        ``numpy.uint32`` arrays (``best`` is ``block.POOL_NONE`` where no member
+        has ``n_bad == 0``); with `marks` a fifth result, per block 1 if it is a
+        member of any root's subtree (``numpy.uint8``).  The host statement is
+        :meth:`block.BlockPool.subtrees`."""
+        roots = self._u32(roots)
+        k = len(roots)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        size, height, best, best_index = (np.zeros(k, dtype=np.uint32) for _ in range(4))
+        on = np.zeros(len(self), dtype=np.uint8) if marks else None
+        n_on = ctypes.c_size_t()
+        check(self.L.pow_pool_subtrees(self.handle, roots.ctypes.data_as(u32p), k, size.ctypes.data_as(u32p),
+                                       height.ctypes.data_as(u32p), best.ctypes.data_as(u32p),
+                                       best_index.ctypes.data_as(u32p),
+                                       on.ctypes.data_as(ctypes.c_void_p) if marks else None,
+                                       ctypes.byref(n_on) if marks else None), self.L)
+        if not marks:
+            return size, height, best, best_index
+        assert n_on.value == int(on.sum())
+        return size, height, best, best_index, on
+
+    def drop(self, roots):
+        """pow_pool_drop: the pool loses every block of every root's subtree
+        and keeps the rest in its order.  Returns ``(map, info)`` as
+        :meth:`prune` does.  The host statement is :meth:`block.BlockPool.drop`."""
+        roots = self._u32(roots)
+        new = np.zeros(len(self), dtype=np.uint32)
+        raw = PoolInfo()
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        rc = check(self.L.pow_pool_drop(self.handle, roots.ctypes.data_as(u32p), len(roots), new.ctypes.data_as(u32p),
+                                        ctypes.byref(raw)), self.L)
+        return new, {**self._info(raw), "ok": rc == 1}
 
     def lift_info(self) -> dict:
         """pow_pool_lift_get_info: the queries' table as the next query will find it."""
