@@ -754,7 +754,6 @@ struct pow_pool {
   uint32_t fin = 0;            // which of depth[], bad[] hold the final values
   uint32_t gen = 0;            // bumped when an old block's walk or position may have changed: a re-rank, a prune that drops
   bool dead = false;           // an add failed half way: every later call is POW_EHIP
-  bool keep_ready = false;     // pow_pool_drop's hand-over to the prune: the marks and their count stand, as a mark leaves them
   PowPoolLivePlan plan{};      // the arrays' offsets at the present capacity
   DevBuf<uint32_t> d_arr;      // the arrays (plan.words)
   DevBuf<uint32_t> d_table;    // the table (slots)
@@ -919,6 +918,12 @@ static void pool_fill_info(pow_pool* p, const PowPoolLiveCtl& ctl, uint32_t adop
   if (reranked) ++p->gen;  // K13's table is stale
 }
 
+// How a call that gives the pool's info ends: the info out, then 1 if no block is flagged.
+static int pool_result(const pow_pool* p, pow_pool_info* info) {
+  if (info) *info = p->info;
+  return p->info.n_flagged == 0 ? 1 : 0;
+}
+
 // The pool's first buffers, their reset and one bounded wait.
 static int pool_alloc(pow_pool* p, uint32_t cap, uint32_t slots) {
   pow_ctx* const ctx = p->ctx;
@@ -1009,10 +1014,7 @@ int pow_pool_add(pow_pool* p, const pow_block* blocks, size_t m, pow_pool_info* 
   if (int rc = pool_ready(p, "pow_pool_add")) return rc;
   pow_ctx* const ctx = p->ctx;
   ctx->stats = pow_stats{};
-  if (m == 0) {
-    if (info) *info = p->info;
-    return p->info.n_flagged == 0 ? 1 : 0;
-  }
+  if (m == 0) return pool_result(p, info);
   p->dead = true;  // until the add has gone through
   const uint32_t base = p->size, n = base + (uint32_t)m;
   if (int rc = ensure_verify_tile(ctx, std::min(m, kVerifyTile))) return rc;
@@ -1071,8 +1073,7 @@ int pow_pool_add(pow_pool* p, const pow_block* blocks, size_t m, pow_pool_info* 
   p->size = n;
   pool_fill_info(p, *ctl, adopted, adopted != 0, rehashed);
   p->dead = false;
-  if (info) *info = p->info;
-  return p->info.n_flagged == 0 ? 1 : 0;
+  return pool_result(p, info);
 }
 
 int pow_pool_get_info(const pow_pool* p, pow_pool_info* info) {
@@ -1134,22 +1135,10 @@ static int pool_mark_args(const pow_pool* p, const uint32_t* tips, size_t n_tips
 
 // One timed section over a pool that holds blocks: the tips up (d_find), the
 // mark's launches (pow_queue_pool_mark), then the control words and, if asked
-// for, the marks down.  Behind pow_pool_drop (keep_ready, which only that call
-// sets, around a prune with no seeds of its own) there is nothing to run: its
-// section has left the marks in depth[1 - fin], the partials' scan in next[1]
-// and the total in h_ctl, which is all a prune that drops something reads of a
-// mark; and a drop of at least one root always drops something.
+// for, the marks down.
 static int pool_mark_run(pow_pool* p, const uint32_t* tips, uint32_t n_tips, uint32_t min_index, unsigned flags,
                          uint8_t* on, uint32_t* marked) {
   pow_ctx* const ctx = p->ctx;
-  if (p->keep_ready) {
-    p->keep_ready = false;
-    if (tips || n_tips || flags || on || p->h_ctl.p->marked >= p->size)
-      return fail(POW_EHIP, "pow_pool_drop's keep-marks met a prune that is not its own (%u of %u kept)",
-                  p->h_ctl.p->marked, p->size);
-    *marked = p->h_ctl.p->marked;
-    return POW_OK;
-  }
   const uint32_t n = p->size, rounds = pow_pool_rounds(n);
   const PowPoolDev D = pool_dev(p, n);
   RESERVE(p->d_find, std::max<size_t>(n_tips, 1));
@@ -1178,12 +1167,42 @@ int pow_pool_mark(pow_pool* p, const uint32_t* tips, size_t n_tips, uint32_t min
   return POW_OK;
 }
 
-// The mark's section, then by its total: everything marked, and only the
-// positions K12a wrote come down as the map; otherwise new arrays and a table
-// fitted to what is left (pow_pool_prune_cap, _slots), and a second timed
+// The second half of pow_pool_prune and pow_pool_drop, over the marks, their
+// scan and their total `kept` < size as the first half left them: new arrays
+// and a table fitted to what is left (pow_pool_prune_cap, _slots), and one timed
 // section: their reset, K12e, K12f, K10b over the survivors, the control words
 // and the map down.  The arrays and the table left behind stay allocated until
 // that section's wait has passed, as pool_grow leaves them.
+static int pool_compact(pow_pool* p, uint32_t kept, uint32_t* map) {
+  pow_ctx* const ctx = p->ctx;
+  const uint32_t n = p->size;
+  const PowPoolDev F = pool_dev(p, n);  // the arrays the compaction leaves behind
+  const uint32_t cap = pow_pool_prune_cap(kept, pow_pool_live_first_cap(0, ctx->pool_first_cap));
+  const uint32_t slots = pow_pool_prune_slots(cap, kept, ctx->pool_slots_log2);
+  const PowPoolLivePlan to = pow_pool_live_plan(cap);
+  if (int rc = pool_retire(p->d_arr, p->d_old_arr, to.words)) return rc;
+  if (int rc = pool_retire(p->d_table, p->d_old_table, slots)) return rc;
+  const PowPoolDev T = pow_pool_live_dev(p->d_arr.p, to, p->d_table.p, kept, slots);
+  PowPoolLiveCtl* const ctl = p->h_ctl.p;
+  if (int rc = timed_begin(ctx)) return rc;
+  HIP_OK(pow_queue_pool_compact(ctx->stream, F, T, cap, p->fin, map != nullptr));
+  HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
+  HIP_OK(hipMemcpyAsync(ctl, T.ctl, sizeof(PowPoolLiveCtl), hipMemcpyDeviceToHost, ctx->stream));
+  if (map) HIP_OK(hipMemcpyAsync(map, F.next[0], (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  // + 100 ns per block and launch
+  if (int rc = timed_end(ctx, "pool prune kernels", 100ull * (n + 2ull * kept), kept ? 3u : 0u, &ctx->stats)) return rc;
+  if (ctl->k10.err) return fail(POW_EHIP, "pool table overflow (%u blocks, %u slots)", kept, slots);
+  p->d_old_arr.release(), p->d_old_table.release();  // the wait has passed: nothing reads them
+  p->lift.release_table(), ++p->gen;  // K13's table goes with the blocks it covered
+  p->plan = to;
+  p->slots = slots;
+  p->size = kept;
+  pool_fill_info(p, *ctl, 0, false, true);
+  return POW_OK;
+}
+
+// The mark's section, then by its total: everything marked, and only the
+// positions K12a wrote come down as the map; otherwise pool_compact.
 int pow_pool_prune(pow_pool* p, const uint32_t* tips, size_t n_tips, uint32_t min_index, unsigned flags, uint32_t* map,
                    pow_pool_info* info) {
   if (int rc = pool_mark_args(p, tips, n_tips, flags)) return rc;
@@ -1203,33 +1222,11 @@ int pow_pool_prune(pow_pool* p, const uint32_t* tips, size_t n_tips, uint32_t mi
       if (int rc = stream_wait_for(ctx, "pool map", 100ull * n)) return rc;
     }
     p->info.adopted = p->info.reranked = p->info.rehashed = 0;
-  } else {
-    const PowPoolDev F = pool_dev(p, n);  // the arrays the prune leaves behind
-    const uint32_t cap = pow_pool_prune_cap(kept, pow_pool_live_first_cap(0, ctx->pool_first_cap));
-    const uint32_t slots = pow_pool_prune_slots(cap, kept, ctx->pool_slots_log2);
-    const PowPoolLivePlan to = pow_pool_live_plan(cap);
-    if (int rc = pool_retire(p->d_arr, p->d_old_arr, to.words)) return rc;
-    if (int rc = pool_retire(p->d_table, p->d_old_table, slots)) return rc;
-    const PowPoolDev T = pow_pool_live_dev(p->d_arr.p, to, p->d_table.p, kept, slots);
-    PowPoolLiveCtl* const ctl = p->h_ctl.p;
-    if (int rc = timed_begin(ctx)) return rc;
-    HIP_OK(pow_queue_pool_compact(ctx->stream, F, T, cap, p->fin, map != nullptr));
-    HIP_OK(hipEventRecord(ctx->ev1, ctx->stream));
-    HIP_OK(hipMemcpyAsync(ctl, T.ctl, sizeof(PowPoolLiveCtl), hipMemcpyDeviceToHost, ctx->stream));
-    if (map) HIP_OK(hipMemcpyAsync(map, F.next[0], (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    // + 100 ns per block and launch
-    if (int rc = timed_end(ctx, "pool prune kernels", 100ull * (n + 2ull * kept), kept ? 3u : 0u, &ctx->stats)) return rc;
-    if (ctl->k10.err) return fail(POW_EHIP, "pool table overflow (%u blocks, %u slots)", kept, slots);
-    p->d_old_arr.release(), p->d_old_table.release();  // the wait has passed: nothing reads them
-    p->lift.release_table(), ++p->gen;  // K13's table goes with the blocks it covered
-    p->plan = to;
-    p->slots = slots;
-    p->size = kept;
-    pool_fill_info(p, *ctl, 0, false, true);
+  } else if (int rc = pool_compact(p, kept, map)) {
+    return rc;
   }
   p->dead = false;
-  if (info) *info = p->info;
-  return p->info.n_flagged == 0 ? 1 : 0;
+  return pool_result(p, info);
 }
 
 // ---- pow_pool_ancestors, pow_pool_fork_points, pow_pool_chain (K13) ----
@@ -1245,6 +1242,35 @@ static int pool_lift_args(const pow_pool* p, const uint32_t* a, const uint32_t* 
     if (a[q] >= p->size || (both && b[q] >= p->size))
       return fail(POW_EINVAL, "query %zu names a block past the pool's %u", q, p->size);
   return POW_OK;
+}
+
+// Whether the table has to be made from nothing: it covers nothing, an earlier
+// generation's blocks, or fewer words a row than the pool has room for.
+static bool pool_lift_stale(const pow_pool* p) {
+  const PowPoolLift& t = p->lift;
+  return t.covered == 0 || t.capacity == 0 || t.gen != p->gen || t.covered > p->size || p->plan.cap > t.capacity;
+}
+
+// The table's step of a call that reads it, around the call's timed section.
+// In front: what pool_lift_update is to start from, and the table allocated
+// (the first call that needs it, or the pool has outgrown it: not copied,
+// made again).  Behind the wait: the pool's blocks at its generation.
+static int pool_lift_ready(pow_pool* p, uint32_t* covered, bool* stale) {
+  PowPoolLift& t = p->lift;
+  *stale = pool_lift_stale(p);
+  if (t.capacity < p->plan.cap) {
+    t.release_table();
+    RESERVE(t.d_up, (size_t)p->plan.cap * pow_pool_lift_rows(p->plan.cap));
+    t.capacity = p->plan.cap;
+  }
+  *covered = *stale ? 0u : t.covered;
+  t.covered = 0;  // until the launches are through
+  return POW_OK;
+}
+
+static void pool_lift_commit(pow_pool* p) {
+  p->lift.covered = p->size;
+  p->lift.gen = p->gen;
 }
 
 // The table brought up to date with the pool, inside the caller's timed
@@ -1273,14 +1299,9 @@ static int pool_lift_run(pow_pool* p, const char* what, bool fork, const uint32_
   PowPoolLift& t = p->lift;
   const uint32_t n = p->size;
   const size_t kb = (size_t)k * sizeof(uint32_t);
-  const bool stale = t.covered == 0 || t.capacity == 0 || t.gen != p->gen || t.covered > n || p->plan.cap > t.capacity;
-  if (t.capacity < p->plan.cap) {  // the first query, or the pool has outgrown it: not copied, made again
-    t.release_table();
-    RESERVE(t.d_up, (size_t)p->plan.cap * pow_pool_lift_rows(p->plan.cap));
-    t.capacity = p->plan.cap;
-  }
-  const uint32_t covered = stale ? 0u : t.covered;
-  t.covered = 0;  // until the launches are through
+  uint32_t covered = 0;
+  bool stale = true;
+  if (int rc = pool_lift_ready(p, &covered, &stale)) return rc;
   RESERVE(p->d_find, 5 * (size_t)k + 1);
   RESERVE(t.h_io, 5 * (size_t)k + 1);
   uint32_t* const d_in0 = p->d_find.p;
@@ -1311,8 +1332,7 @@ static int pool_lift_run(pow_pool* p, const char* what, bool fork, const uint32_
   if (out1) memcpy(out1, h_out + k, kb);
   if (out2) memcpy(out2, h_out + 2 * (size_t)k, kb);
   if (len) *len = h_out[k];
-  t.covered = n;
-  t.gen = p->gen;
+  pool_lift_commit(p);
   return POW_OK;
 }
 
@@ -1352,8 +1372,7 @@ int pow_pool_chain(pow_pool* p, uint32_t tip, size_t max_len, uint32_t* out, siz
 int pow_pool_lift_get_info(const pow_pool* p, pow_pool_lift_info* out) {
   if (!p || !out) return fail(POW_EINVAL, "null");
   const PowPoolLift& t = p->lift;
-  const bool fresh = t.capacity && t.gen == p->gen && t.covered <= p->size && p->plan.cap <= t.capacity;
-  const uint32_t covered = fresh ? t.covered : 0u;
+  const uint32_t covered = pool_lift_stale(p) ? 0u : t.covered;
   *out = pow_pool_lift_info{covered, pow_pool_lift_rows(covered), t.capacity, t.rebuilt, t.extended,
                             pow_pool_lift_bytes(t.capacity)};
   return POW_OK;
@@ -1403,7 +1422,7 @@ static int pool_above_args(const pow_pool* p, const uint32_t* roots, size_t k) {
 }
 
 // One timed section over a pool that holds blocks, for k >= 1 roots: the table
-// made ready as pool_lift_run makes it, the roots up (d_find: the k records,
+// made ready (pool_lift_ready), the roots up (d_find: the k records,
 // then the roots; h_io is its pinned twin), the table's launches
 // (pool_lift_update), the subtrees' (pow_queue_pool_above), the records down
 // into h_io and, with `marks`, the control words and (on != nullptr) the marks.
@@ -1412,14 +1431,9 @@ static int pool_above_run(pow_pool* p, const char* what, const uint32_t* roots, 
   pow_ctx* const ctx = p->ctx;
   PowPoolLift& t = p->lift;
   const uint32_t n = p->size;
-  const bool stale = t.covered == 0 || t.capacity == 0 || t.gen != p->gen || t.covered > n || p->plan.cap > t.capacity;
-  if (t.capacity < p->plan.cap) {  // the first call that needs it, or the pool has outgrown it: not copied, made again
-    t.release_table();
-    RESERVE(t.d_up, (size_t)p->plan.cap * pow_pool_lift_rows(p->plan.cap));
-    t.capacity = p->plan.cap;
-  }
-  const uint32_t covered = stale ? 0u : t.covered;
-  t.covered = 0;  // until the launches are through
+  uint32_t covered = 0;
+  bool stale = true;
+  if (int rc = pool_lift_ready(p, &covered, &stale)) return rc;
   RESERVE(p->d_find, 5 * (size_t)k);
   RESERVE(t.h_io, 5 * (size_t)k);
   PowAboveAcc* const d_acc = (PowAboveAcc*)p->d_find.p;
@@ -1443,8 +1457,7 @@ static int pool_above_run(pow_pool* p, const char* what, const uint32_t* roots, 
   if (int rc = timed_end(ctx, what, 100ull * (work + (uint64_t)n * (k + (marks ? 2u : 0u))),
                          launches + (marks ? 3u : 1u), &ctx->stats))
     return rc;
-  t.covered = n;
-  t.gen = p->gen;
+  pool_lift_commit(p);
   if (marks) *marked = ctl->marked;
   return POW_OK;
 }
@@ -1473,11 +1486,10 @@ int pow_pool_subtrees(pow_pool* p, const uint32_t* roots, size_t k, uint32_t* si
 }
 
 // The keep-marks' section (every block but the roots' members, counted and
-// scanned as a mark's are), then the prune's own second half: pow_pool_prune
-// takes the marks as they stand (keep_ready) and goes on by their total as it
-// always does; a root is a member of its own subtree, so something is always
-// dropped and the prune never takes its "everything marked" way.  No roots:
-// nothing goes, no GPU work; the identity map is written here.
+// scanned as a mark's are), then the prune's own second half, pool_compact, by
+// their total; a root is a member of its own subtree, so something is always
+// dropped.  The pool is dead from before the first section until the second is
+// through.  No roots: nothing goes, no GPU work; the identity map is written here.
 int pow_pool_drop(pow_pool* p, const uint32_t* roots, size_t k, uint32_t* map, pow_pool_info* info) {
   if (!p) return fail(POW_EINVAL, "null pool");
   if (int rc = pool_above_args(p, roots, k)) return rc;
@@ -1487,20 +1499,15 @@ int pow_pool_drop(pow_pool* p, const uint32_t* roots, size_t k, uint32_t* map, p
   if (k == 0) {
     if (map) std::iota(map, map + p->size, 0u);
     p->info.adopted = p->info.reranked = p->info.rehashed = 0;
-    if (info) *info = p->info;
-    return p->info.n_flagged == 0 ? 1 : 0;
+    return pool_result(p, info);
   }
   uint32_t kept = 0;
   p->dead = true;  // until the drop has gone through
   if (int rc = pool_above_run(p, "pool drop kernels", roots, (uint32_t)k, true, true, nullptr, &kept)) return rc;
-  const pow_stats first = ctx->stats;
+  if (kept >= p->size) return fail(POW_EHIP, "pow_pool_drop: the keep-marks kept all %u blocks under %zu roots", p->size, k);
+  if (int rc = pool_compact(p, kept, map)) return rc;
   p->dead = false;
-  p->keep_ready = true;
-  const int rc = pow_pool_prune(p, nullptr, 0, 0, 0, map, info);
-  p->keep_ready = false;
-  ctx->stats.kernel_ms += first.kernel_ms;
-  ctx->stats.launches += first.launches;
-  return rc;
+  return pool_result(p, info);
 }
 
 int pow_sweep_device(pow_ctx* ctx, const pow_block* tmpl, uint64_t ctr_start, uint64_t ctr_count,

@@ -6,7 +6,10 @@
 // the exports the shipped library does not have: pow_test_leading_zero_bits,
 // pow_test_pool_rank, pow_test_pool_prune, pow_test_pool_lift and
 // pow_test_pool_above (K10d/K10e, K12, K13 and K14 on trees of the caller's
-// making, up to POW_POOL_MAX_BLOCKS nodes).
+// making, up to POW_POOL_MAX_BLOCKS nodes).  Those five stand on one frame
+// (Frame: first error, buffers, copies, bounded waits); the three that take a
+// forest share its check (check_forest) and, where they compact it, the
+// prune's second half (compact_half).
 #include <dlfcn.h>
 
 #include <algorithm>
@@ -181,6 +184,81 @@ const pow_test_hooks kHooks = {configure,   open_path, before_launch, dispatch_l
                                path_status, path_diag, warm_path,     close_path,   rccl_lib};
 const bool kRegistered = (pow_hooks = &kHooks, true);  // as the library loads
 
+// The frame of the exports below: the first error of a hook's HIP calls (rc),
+// the device buffers it made, its copies and its bounded waits.  Nothing is
+// reported behind the first error, and `up` and `down` queue nothing behind it,
+// nor for a null host pointer or no bytes.  The buffers are freed as the frame
+// goes, unless a wait failed and left the context wedged: after a watchdog the
+// launches may still write.
+struct Frame {
+  pow_ctx* const ctx;
+  int rc = POW_OK;
+  bool wait_failed = false;
+  std::vector<void*> owned;
+  explicit Frame(pow_ctx* c) : ctx(c) {}
+  Frame(const Frame&) = delete;
+  ~Frame() {
+    if (wait_failed && ctx->wedged) return;
+    for (void* d : owned) (void)hipFree(d);
+  }
+  void step(hipError_t e, const char* what) {
+    if (rc == POW_OK && e != hipSuccess) rc = fail(POW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
+  }
+  uint32_t* alloc(size_t words) {
+    void* d = nullptr;
+    step(hipMalloc(&d, words * sizeof(uint32_t)), "hipMalloc");
+    if (d) owned.push_back(d);
+    return (uint32_t*)d;
+  }
+  void up(void* dst, const void* src, size_t bytes) {
+    if (rc == POW_OK && src && bytes) step(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream), "copy in");
+  }
+  void down(void* dst, const void* src, size_t bytes) {
+    if (rc == POW_OK && dst && bytes) step(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream), "copy out");
+  }
+  // Every hook waits even after a failed step: the copies queued so far read and write host memory.
+  int wait(const char* what, uint64_t extra_ns) {
+    const int waited = pow_ctx_stream_wait(ctx, what, extra_ns);
+    wait_failed = wait_failed || waited != POW_OK;
+    if (rc == POW_OK) rc = waited;
+    return rc;
+  }
+};
+
+// The forest of pow_test_pool_prune, _lift and _above, behind the size and the
+// hook's own scalars (which its refusals name first): `arrays` says that none
+// of the hook's input arrays is null; every parent is a node or an end.
+int check_forest(size_t n, bool arrays, const uint32_t* parent) {
+  if (!arrays && n) return fail(POW_EINVAL, "null");
+  for (size_t i = 0; i < n; ++i)
+    if (parent[i] >= n && parent[i] < POW_POOL_NONE)
+      return fail(POW_EINVAL, "parent %u of node %zu is neither a node nor an end", parent[i], i);
+  return POW_OK;
+}
+
+// The second half of pow_test_pool_prune and of pow_test_pool_above's mode 2, as
+// pool_compact (pow_api.cpp) runs it on a pool: `kept` < F.n marks stand in
+// F as the first half left them; new arrays at pow_pool_prune_cap's capacity
+// and pow_queue_pool_compact over a view with no table (K12e, K12f; K10b is
+// not run; nothing marked: the map is POW_POOL_NONE throughout, as the
+// library's reset makes it), the map and the survivors' parent and depth
+// down, what `more` queues of the survivors' view, and the second bounded wait.
+template <class More>
+int compact_half(Frame& f, const char* what, const PowPoolDev& F, uint32_t kept, uint32_t fin, uint32_t* map,
+                 uint32_t* parent_out, uint32_t* depth_out, More more) {
+  pow_ctx* const ctx = f.ctx;
+  const uint32_t cap = pow_pool_prune_cap(kept, pow_pool_live_first_cap(0, ctx->pool_first_cap));
+  const PowPoolLivePlan to = pow_pool_live_plan(cap);
+  uint32_t* const to_base = f.alloc(to.words);
+  if (f.rc != POW_OK) return f.rc;
+  const PowPoolDev T = pow_pool_live_dev(to_base, to, nullptr, kept, 0);
+  const size_t kw = (size_t)kept * sizeof(uint32_t);
+  f.step(pow_queue_pool_compact(ctx->stream, F, T, cap, fin, map != nullptr), "K12e, K12f");  // no table: no K10b
+  f.down(map, F.next[0], (size_t)F.n * sizeof(uint32_t)), f.down(parent_out, T.parent, kw), f.down(depth_out, T.depth[fin], kw);
+  more(T);
+  return f.wait(what, 100ull * (F.n + 2ull * kept));
+}
+
 }  // namespace
 
 // The kernels' leading-zero count (sha256_dev.h leading_zero_bits) of n digests
@@ -191,23 +269,13 @@ extern "C" int pow_test_leading_zero_bits(pow_ctx* ctx, const uint32_t* digests,
   if (n > (1u << 20)) return fail(POW_EINVAL, "too many digests (%zu > 2^20)", n);
   if (n == 0) return POW_OK;
   HIP_OK(hipSetDevice(ctx->device));
-  uint32_t* d_in = nullptr;
-  uint32_t* d_out = nullptr;
-  int rc = POW_OK;
-  auto step = [&](hipError_t e, const char* what) {
-    if (rc == POW_OK && e != hipSuccess) rc = fail(POW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
-  };
-  step(hipMalloc(&d_in, n * 32), "hipMalloc");
-  step(hipMalloc(&d_out, n * 4), "hipMalloc");
-  if (rc == POW_OK) step(hipMemcpyAsync(d_in, digests, n * 32, hipMemcpyHostToDevice, ctx->stream), "copy in");
-  if (rc == POW_OK) step(pow_launch_test_lz(ctx->stream, d_in, (uint32_t)n, d_out), "pow_test_lz");
-  if (rc == POW_OK) step(hipMemcpyAsync(out, d_out, n * 4, hipMemcpyDeviceToHost, ctx->stream), "copy out");
-  if (rc == POW_OK) rc = pow_ctx_stream_wait(ctx, "pow_test_lz", 0);
-  if (rc == POW_OK || !ctx->wedged) {  // after a watchdog the launch may still write
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-  }
-  return rc;
+  Frame f(ctx);
+  uint32_t* const d_in = f.alloc(n * 8);
+  uint32_t* const d_out = f.alloc(n);
+  f.up(d_in, digests, n * 32);
+  if (f.rc == POW_OK) f.step(pow_launch_test_lz(ctx->stream, d_in, (uint32_t)n, d_out), "pow_test_lz");
+  f.down(out, d_out, n * 4);
+  return f.rc == POW_OK ? f.wait("pow_test_lz", 0) : f.rc;  // nothing is queued behind a failed step
 }
 
 // K10d and K10e (pow_pool.hip) on a next[] of the caller's choosing, the only
@@ -220,27 +288,19 @@ extern "C" int pow_test_pool_rank(pow_ctx* ctx, const uint32_t* next, size_t n, 
   if (n == 0) return POW_OK;
   HIP_OK(hipSetDevice(ctx->device));
   const PowPoolPlan plan = pow_pool_plan((uint32_t)n, 0);
-  uint32_t* base = nullptr;
-  int rc = POW_OK;
-  auto step = [&](hipError_t e, const char* what) {
-    if (rc == POW_OK && e != hipSuccess) rc = fail(POW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
-  };
-  step(hipMalloc(&base, plan.words * sizeof(uint32_t)), "hipMalloc");
-  if (rc != POW_OK) return rc;
+  const size_t words = n * sizeof(uint32_t);
+  Frame f(ctx);
+  uint32_t* const base = f.alloc(plan.words);
+  if (f.rc != POW_OK) return f.rc;
   const PowPoolDev D = pow_pool_dev(base, plan, (uint32_t)n);
   const uint32_t last = plan.rounds & 1u;
   std::vector<uint32_t> ones(n, 1u);
-  step(hipMemsetAsync(base, 0, plan.words * sizeof(uint32_t), ctx->stream), "reset");  // status, index, bad, ctl: all zero
-  step(hipMemcpyAsync(D.next[0], next, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream), "copy in");
-  step(hipMemcpyAsync(D.depth[0], ones.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream), "copy in");
-  if (rc == POW_OK) step(pow_queue_pool_rank(ctx->stream, D, plan.rounds), "K10d, K10e");
-  step(hipMemcpyAsync(depth_out, D.depth[last], n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream), "copy out");
-  step(hipMemcpyAsync(n_bad_out, D.bad[last], n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream), "copy out");
+  f.step(hipMemsetAsync(base, 0, plan.words * sizeof(uint32_t), ctx->stream), "reset");  // status, index, bad, ctl: all zero
+  f.up(D.next[0], next, words), f.up(D.depth[0], ones.data(), words);
+  if (f.rc == POW_OK) f.step(pow_queue_pool_rank(ctx->stream, D, plan.rounds), "K10d, K10e");
+  f.down(depth_out, D.depth[last], words), f.down(n_bad_out, D.bad[last], words);
   // waited for even after a failed step: the copies queued so far read `ones`
-  const int waited = pow_ctx_stream_wait(ctx, "pow_test_pool_rank", 100ull * n * (plan.rounds + 1u));
-  if (rc == POW_OK) rc = waited;
-  if (waited == POW_OK || !ctx->wedged) (void)hipFree(base);  // after a watchdog the launches may still write
-  return rc;
+  return f.wait("pow_test_pool_rank", 100ull * n * (plan.rounds + 1u));
 }
 
 // What pow_test_pool_prune takes and gives: arrays of n entries unless said.
@@ -278,13 +338,11 @@ static_assert(sizeof(pow_test_prune_io) == 23 * 8, "tests/pool_deep_util.py Prun
 // K12 (pow_pool_prune.hip) on a forest of the caller's choosing, with no pool
 // and no table: the mark's launches (pow_queue_pool_mark, as pool_mark_run
 // queues them) in one section, then by K12d's total, as pow_pool_prune decides
-// it: everything marked, and K12a's positions are the map; otherwise new arrays
-// at pow_pool_prune_cap's capacity and pow_queue_pool_compact over a view with
-// no table: K12e and K12f (nothing marked: the map is POW_POOL_NONE throughout,
-// as the library's reset makes it).  K10b is not run.
-// Two bounded waits, one per section: the second section's grid is the first's
-// result.  The scratch is pool_mark_run's: marks in depth[1 - fin], positions
-// in bad[1 - fin], the walks in next[], the partials in next[1].
+// it: everything marked, and K12a's positions are the map; otherwise
+// compact_half.  Two bounded waits, one per section: the second section's grid
+// is the first's result.  The scratch is pool_mark_run's: marks in
+// depth[1 - fin], positions in bad[1 - fin], the walks in next[], the partials
+// in next[1].
 extern "C" int pow_test_pool_prune(pow_ctx* ctx, size_t n, const pow_test_prune_io* io) {
   if (n > POW_POOL_MAX_BLOCKS) return fail(POW_EINVAL, "too many nodes (%zu > 2^20)", n);
   if (!ctx || !io) return fail(POW_EINVAL, "null");
@@ -292,93 +350,51 @@ extern "C" int pow_test_pool_prune(pow_ctx* ctx, size_t n, const pow_test_prune_
   if (io->fin > 1u) return fail(POW_EINVAL, "fin %u > 1", io->fin);
   if (io->n_tips > POW_POOL_MAX_TIPS) return fail(POW_EINVAL, "too many tips (%zu > %u)", io->n_tips, POW_POOL_MAX_TIPS);
   if (!io->tips && io->n_tips) return fail(POW_EINVAL, "null tips");
-  if ((!io->parent || !io->index || !io->n_bad || !io->status || !io->depth) && n) return fail(POW_EINVAL, "null");
   for (size_t k = 0; k < io->n_tips; ++k)
     if (io->tips[k] >= n) return fail(POW_EINVAL, "tip %zu (node %u) past the forest's %zu", k, io->tips[k], n);
-  for (size_t i = 0; i < n; ++i)
-    if (io->parent[i] >= n && io->parent[i] < POW_POOL_NONE)
-      return fail(POW_EINVAL, "parent %u of node %zu is neither a node nor an end", io->parent[i], i);
+  if (int rc = check_forest(n, io->parent && io->index && io->n_bad && io->status && io->depth, io->parent)) return rc;
   if (n == 0) return POW_OK;
   HIP_OK(hipSetDevice(ctx->device));
   const uint32_t n32 = (uint32_t)n, n_tips = (uint32_t)io->n_tips, fin = io->fin, rounds = pow_pool_rounds(n32);
   const PowPoolLivePlan from = pow_pool_live_plan(n32);
   const size_t words = (size_t)n32 * sizeof(uint32_t);
-  uint32_t* base = nullptr;
-  uint32_t* to_base = nullptr;
-  uint32_t* d_tips = nullptr;
   PowPoolLiveCtl ctl{}, new_ctl{};
-  int rc = POW_OK;
-  auto step = [&](hipError_t e, const char* what) {
-    if (rc == POW_OK && e != hipSuccess) rc = fail(POW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
-  };
-  auto release = [&](int waited) {  // after a watchdog the launches may still write
-    if (waited == POW_OK || !ctx->wedged) (void)hipFree(base), (void)hipFree(to_base), (void)hipFree(d_tips);
-  };
-  step(hipMalloc(&base, from.words * sizeof(uint32_t)), "hipMalloc");
-  step(hipMalloc(&d_tips, std::max<size_t>(n_tips, 1) * sizeof(uint32_t)), "hipMalloc");
-  if (rc != POW_OK) {
-    release(POW_OK);
-    return rc;
-  }
+  Frame f(ctx);
+  uint32_t* const base = f.alloc(from.words);
+  uint32_t* const d_tips = f.alloc(std::max<size_t>(n_tips, 1));
+  if (f.rc != POW_OK) return f.rc;
   const PowPoolDev F = pow_pool_live_dev(base, from, nullptr, n32, 0);
-  auto up = [&](void* dst, const void* src, size_t bytes) {
-    if (rc == POW_OK && src) step(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream), "copy in");
-  };
-  auto down = [&](void* dst, const void* src, size_t bytes) {
-    if (rc == POW_OK && dst && bytes) step(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream), "copy out");
-  };
-  step(hipMemsetAsync(base, 0, from.words * sizeof(uint32_t), ctx->stream), "reset");  // kind, and a null digest or prev
-  up(F.parent, io->parent, words), up(F.index, io->index, words), up(F.bad[fin], io->n_bad, words);
-  up(F.depth[fin], io->depth, words), up(F.status, io->status, n), up(F.dig, io->digest, 8 * words);
-  up(F.prev, io->prev, 8 * words), up(d_tips, n_tips ? io->tips : nullptr, n_tips * sizeof(uint32_t));
-  if (rc == POW_OK) {  // pool_mark_run's section
-    step(pow_queue_pool_mark(ctx->stream, F, fin, d_tips, n_tips, io->min_index, io->flags), "K12a to K12d");
-    down(&ctl, F.ctl, sizeof ctl), down(io->marks, F.depth[fin ^ 1u], n);
+  f.step(hipMemsetAsync(base, 0, from.words * sizeof(uint32_t), ctx->stream), "reset");  // kind, and a null digest or prev
+  f.up(F.parent, io->parent, words), f.up(F.index, io->index, words), f.up(F.bad[fin], io->n_bad, words);
+  f.up(F.depth[fin], io->depth, words), f.up(F.status, io->status, n), f.up(F.dig, io->digest, 8 * words);
+  f.up(F.prev, io->prev, 8 * words), f.up(d_tips, io->tips, n_tips * sizeof(uint32_t));
+  if (f.rc == POW_OK) {  // pool_mark_run's section
+    f.step(pow_queue_pool_mark(ctx->stream, F, fin, d_tips, n_tips, io->min_index, io->flags), "K12a to K12d");
+    f.down(&ctl, F.ctl, sizeof ctl), f.down(io->marks, F.depth[fin ^ 1u], n);
   }
-  int waited = pow_ctx_stream_wait(ctx, "pow_test_pool_prune (mark)", 100ull * n * (rounds + 3ull));
-  if (rc == POW_OK) rc = waited;
-  if (rc != POW_OK) {
-    release(waited);
-    return rc;
-  }
+  if (f.wait("pow_test_pool_prune (mark)", 100ull * n * (rounds + 3ull)) != POW_OK) return f.rc;
   const uint32_t kept = ctl.marked;
-  if (kept > n32) {
-    release(waited);
-    return fail(POW_EHIP, "K12d counted %u marks on %u nodes", kept, n32);
-  }
+  if (kept > n32) return fail(POW_EHIP, "K12d counted %u marks on %u nodes", kept, n32);
   if (io->kept) *io->kept = kept;
   if (io->best) *io->best = 0;
   if (io->n_flagged) *io->n_flagged = 0;
   if (kept == n32) {  // nothing to drop: the arrays stay as they are
-    down(io->map, F.bad[fin ^ 1u], words), down(io->parent_out, F.parent, words), down(io->index_out, F.index, words);
-    down(io->depth_out, F.depth[fin], words), down(io->n_bad_out, F.bad[fin], words), down(io->status_out, F.status, n);
-    down(io->digest_out, F.dig, 8 * words), down(io->prev_out, F.prev, 8 * words);
-    waited = pow_ctx_stream_wait(ctx, "pow_test_pool_prune (map)", 100ull * n);
-    if (rc == POW_OK) rc = waited;
-    release(waited);
-    return rc;
+    f.down(io->map, F.bad[fin ^ 1u], words), f.down(io->parent_out, F.parent, words), f.down(io->index_out, F.index, words);
+    f.down(io->depth_out, F.depth[fin], words), f.down(io->n_bad_out, F.bad[fin], words), f.down(io->status_out, F.status, n);
+    f.down(io->digest_out, F.dig, 8 * words), f.down(io->prev_out, F.prev, 8 * words);
+    return f.wait("pow_test_pool_prune (map)", 100ull * n);
   }
-  const uint32_t cap = pow_pool_prune_cap(kept, pow_pool_live_first_cap(0, ctx->pool_first_cap));
-  const PowPoolLivePlan to = pow_pool_live_plan(cap);
-  step(hipMalloc(&to_base, to.words * sizeof(uint32_t)), "hipMalloc");
-  if (rc != POW_OK) {
-    release(POW_OK);
-    return rc;
-  }
-  const PowPoolDev T = pow_pool_live_dev(to_base, to, nullptr, kept, 0);
-  const size_t kw = (size_t)kept * sizeof(uint32_t);
-  step(pow_queue_pool_compact(ctx->stream, F, T, cap, fin, io->map != nullptr), "K12e, K12f");  // no table: no K10b
-  down(&new_ctl, T.ctl, sizeof new_ctl), down(io->map, F.next[0], words);
-  down(io->parent_out, T.parent, kw), down(io->index_out, T.index, kw), down(io->depth_out, T.depth[fin], kw);
-  down(io->n_bad_out, T.bad[fin], kw), down(io->status_out, T.status, kept), down(io->digest_out, T.dig, 8 * kw);
-  down(io->prev_out, T.prev, 8 * kw);
-  waited = pow_ctx_stream_wait(ctx, "pow_test_pool_prune (gather)", 100ull * (n + 2ull * kept));
-  if (rc == POW_OK) rc = waited;
+  const int rc = compact_half(f, "pow_test_pool_prune (gather)", F, kept, fin, io->map, io->parent_out, io->depth_out,
+                              [&](const PowPoolDev& T) {
+                                const size_t kw = (size_t)kept * sizeof(uint32_t);
+                                f.down(&new_ctl, T.ctl, sizeof new_ctl), f.down(io->index_out, T.index, kw);
+                                f.down(io->n_bad_out, T.bad[fin], kw), f.down(io->status_out, T.status, kept);
+                                f.down(io->digest_out, T.dig, 8 * kw), f.down(io->prev_out, T.prev, 8 * kw);
+                              });
   if (rc == POW_OK) {
     if (io->best) *io->best = new_ctl.k10.best;
     if (io->n_flagged) *io->n_flagged = new_ctl.k10.n_flagged;
   }
-  release(waited);
   return rc;
 }
 
@@ -418,19 +434,17 @@ extern "C" int pow_test_pool_lift(pow_ctx* ctx, size_t n, const pow_test_lift_io
   if (io->mode > 2u) return fail(POW_EINVAL, "unknown mode %u", io->mode);
   if (io->k > (io->mode == 2u ? n : (size_t)POW_POOL_MAX_BLOCKS))
     return fail(POW_EINVAL, "too many queries (%zu > %zu)", io->k, io->mode == 2u ? n : (size_t)POW_POOL_MAX_BLOCKS);
-  if ((!io->parent || !io->depth) && n) return fail(POW_EINVAL, "null");
   if (io->k && (!io->out0 || (io->mode != 2u && (!io->in0 || !io->in1)) || (io->mode == 1u && (!io->out1 || !io->out2))))
     return fail(POW_EINVAL, "null");
   for (size_t q = 0; q < io->k && io->mode != 2u; ++q)
     if (io->in0[q] >= n || (io->mode == 1u && io->in1[q] >= n))
       return fail(POW_EINVAL, "query %zu names a node past the forest's %zu", q, n);
   if (io->mode == 2u && io->k && io->tip >= n) return fail(POW_EINVAL, "tip (node %u) past the forest's %zu", io->tip, n);
-  for (size_t i = 0; i < n; ++i) {
-    const uint32_t p = io->parent[i];
-    if (p >= n && p < POW_POOL_NONE) return fail(POW_EINVAL, "parent %u of node %zu is neither a node nor an end", p, i);
-    if (i < io->covered && p >= io->covered && p < n)
-      return fail(POW_EINVAL, "the first %u nodes are not closed under parent (node %zu, parent %u)", io->covered, i, p);
-  }
+  if (int rc = check_forest(n, io->parent && io->depth, io->parent)) return rc;
+  for (size_t i = 0; i < io->covered; ++i)
+    if (io->parent[i] >= io->covered && io->parent[i] < n)
+      return fail(POW_EINVAL, "the first %u nodes are not closed under parent (node %zu, parent %u)", io->covered, i,
+                  io->parent[i]);
   if (io->launches) *io->launches = 0;
   if (n == 0) return POW_OK;
   HIP_OK(hipSetDevice(ctx->device));
@@ -438,62 +452,44 @@ extern "C" int pow_test_pool_lift(pow_ctx* ctx, size_t n, const pow_test_lift_io
   const uint32_t rows = pow_pool_lift_rows(n32);
   const size_t words = (size_t)n32 * sizeof(uint32_t), kb = (size_t)k * sizeof(uint32_t);
   const size_t up_words = std::max<size_t>((size_t)cap * pow_pool_lift_rows(cap), 1);
-  uint32_t* d_parent = nullptr;
-  uint32_t* d_depth = nullptr;
-  uint32_t* d_up = nullptr;
-  uint32_t* d_io = nullptr;  // in0, in1, then the results, as pool_lift_run lays them out
-  int rc = POW_OK;
-  auto step = [&](hipError_t e, const char* what) {
-    if (rc == POW_OK && e != hipSuccess) rc = fail(POW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
-  };
-  step(hipMalloc(&d_parent, words), "hipMalloc");
-  step(hipMalloc(&d_depth, words), "hipMalloc");
-  step(hipMalloc(&d_up, up_words * sizeof(uint32_t)), "hipMalloc");
-  step(hipMalloc(&d_io, (5 * (size_t)k + 1) * sizeof(uint32_t)), "hipMalloc");
+  Frame f(ctx);
+  uint32_t* const d_parent = f.alloc(n32);
+  uint32_t* const d_depth = f.alloc(n32);
+  uint32_t* const d_up = f.alloc(up_words);
+  uint32_t* const d_io = f.alloc(5 * (size_t)k + 1);  // in0, in1, then the results, as pool_lift_run lays them out
   uint32_t launches = 0;
   uint64_t work = 0;
-  if (rc == POW_OK) {
-    step(hipMemsetAsync(d_up, 0xEE, up_words * sizeof(uint32_t), ctx->stream), "reset");
-    step(hipMemcpyAsync(d_parent, io->parent, words, hipMemcpyHostToDevice, ctx->stream), "copy in");
-    step(hipMemcpyAsync(d_depth, io->depth, words, hipMemcpyHostToDevice, ctx->stream), "copy in");
+  if (f.rc == POW_OK) {
+    f.step(hipMemsetAsync(d_up, 0xEE, up_words * sizeof(uint32_t), ctx->stream), "reset");
+    f.up(d_parent, io->parent, words), f.up(d_depth, io->depth, words);
     // the table a pool of `covered` nodes had: made from nothing at that size; its launches are not reported
     uint32_t before = 0;
-    if (rc == POW_OK && covered)
-      step(pow_queue_pool_lift(ctx->stream, d_parent, d_up, cap, 0, covered, true, &before, &work), "K13a");
+    if (f.rc == POW_OK && covered)
+      f.step(pow_queue_pool_lift(ctx->stream, d_parent, d_up, cap, 0, covered, true, &before, &work), "K13a");
     // the query call's update, stale when nothing was covered
-    if (rc == POW_OK)
-      step(pow_queue_pool_lift(ctx->stream, d_parent, d_up, cap, covered, n32, covered == 0, &launches, &work), "K13a, K13b");
+    if (f.rc == POW_OK)
+      f.step(pow_queue_pool_lift(ctx->stream, d_parent, d_up, cap, covered, n32, covered == 0, &launches, &work), "K13a, K13b");
   }
-  if (rc == POW_OK && k) {
+  if (f.rc == POW_OK && k) {
     uint32_t* const d_in0 = d_io;
     uint32_t* const d_in1 = d_io + k;
     uint32_t* const d_out = d_in1 + k;
     const PowLiftView v{d_parent, d_depth, d_up, cap, n32, pow_pool_rounds(n32)};
-    if (io->mode != 2u) {
-      step(hipMemcpyAsync(d_in0, io->in0, kb, hipMemcpyHostToDevice, ctx->stream), "copy in");
-      step(hipMemcpyAsync(d_in1, io->in1, kb, hipMemcpyHostToDevice, ctx->stream), "copy in");
-    }
+    if (io->mode != 2u) f.up(d_in0, io->in0, kb), f.up(d_in1, io->in1, kb);
     if (io->mode == 1u) {
-      step(pow_launch_pool_lift_fork(ctx->stream, v, k, d_in0, d_in1, d_out, d_out + k, d_out + 2 * (size_t)k), "K13d");
-      step(hipMemcpyAsync(io->out0, d_out, kb, hipMemcpyDeviceToHost, ctx->stream), "copy out");
-      step(hipMemcpyAsync(io->out1, d_out + k, kb, hipMemcpyDeviceToHost, ctx->stream), "copy out");
-      step(hipMemcpyAsync(io->out2, d_out + 2 * (size_t)k, kb, hipMemcpyDeviceToHost, ctx->stream), "copy out");
+      f.step(pow_launch_pool_lift_fork(ctx->stream, v, k, d_in0, d_in1, d_out, d_out + k, d_out + 2 * (size_t)k), "K13d");
+      f.down(io->out0, d_out, kb), f.down(io->out1, d_out + k, kb), f.down(io->out2, d_out + 2 * (size_t)k, kb);
     } else {
       const bool chain = io->mode == 2u;
-      step(pow_launch_pool_lift_ancestor(ctx->stream, v, k, chain ? nullptr : d_in0, d_in1, io->tip, d_out), "K13c");
-      step(hipMemcpyAsync(io->out0, d_out, kb + (chain ? sizeof(uint32_t) : 0), hipMemcpyDeviceToHost, ctx->stream), "copy out");
+      f.step(pow_launch_pool_lift_ancestor(ctx->stream, v, k, chain ? nullptr : d_in0, d_in1, io->tip, d_out), "K13c");
+      f.down(io->out0, d_out, kb + (chain ? sizeof(uint32_t) : 0));
     }
   }
-  if (rc == POW_OK && io->table)
-    for (uint32_t j = 1; j <= rows; ++j)
-      step(hipMemcpyAsync(io->table + (size_t)(j - 1u) * n32, d_up + (size_t)(j - 1u) * cap, words, hipMemcpyDeviceToHost, ctx->stream),
-           "copy out");
+  for (uint32_t j = 1; io->table && j <= rows; ++j)
+    f.down(io->table + (size_t)(j - 1u) * n32, d_up + (size_t)(j - 1u) * cap, words);
   // + 100 ns per node and launch
-  const int waited = pow_ctx_stream_wait(ctx, "pow_test_pool_lift", 100ull * (work + k + (io->table ? (uint64_t)n32 * rows : 0)));
-  if (rc == POW_OK) rc = waited;
+  const int rc = f.wait("pow_test_pool_lift", 100ull * (work + k + (io->table ? (uint64_t)n32 * rows : 0)));
   if (rc == POW_OK && io->launches) *io->launches = launches;
-  if (waited == POW_OK || !ctx->wedged)  // after a watchdog the launches may still write
-    (void)hipFree(d_parent), (void)hipFree(d_depth), (void)hipFree(d_up), (void)hipFree(d_io);
   return rc;
 }
 
@@ -528,10 +524,8 @@ static_assert(sizeof(pow_test_above_io) == 17 * 8, "tests/pool_above_util.py Abo
 // no hashing and no name table: the library's own sequences.  Mode 0:
 // pow_queue_pool_tips.  Modes 1 and 2: K13's table made from nothing
 // (pow_queue_pool_lift), then pow_queue_pool_above, as pool_above_run queues
-// them; mode 2 goes on as pow_pool_drop does through the prune's second half,
-// by K12d's total (a root is dropped with its subtree, so never everything kept):
-// new arrays at pow_pool_prune_cap's capacity and pow_queue_pool_compact over a
-// view with no table (K12e, K12f; K10b is not run), behind a second bounded wait.
+// them; mode 2 goes on as pow_pool_drop does, by K12d's total (a root is
+// dropped with its subtree, so never everything kept), through compact_half.
 extern "C" int pow_test_pool_above(pow_ctx* ctx, size_t n, const pow_test_above_io* io) {
   if (n > POW_POOL_MAX_BLOCKS) return fail(POW_EINVAL, "too many nodes (%zu > 2^20)", n);
   if (!ctx || !io) return fail(POW_EINVAL, "null");
@@ -540,98 +534,53 @@ extern "C" int pow_test_pool_above(pow_ctx* ctx, size_t n, const pow_test_above_
   if (io->fin > 1u) return fail(POW_EINVAL, "fin %u > 1", io->fin);
   if (io->mode && (io->k == 0 || io->k > POW_POOL_MAX_ROOTS || !io->roots))
     return fail(POW_EINVAL, "1..%d roots", POW_POOL_MAX_ROOTS);
-  if ((!io->parent || !io->depth || !io->index || !io->n_bad) && n) return fail(POW_EINVAL, "null");
   for (size_t q = 0; io->mode && q < io->k; ++q)
     if (io->roots[q] >= n) return fail(POW_EINVAL, "root %zu (node %u) past the forest's %zu", q, io->roots[q], n);
-  for (size_t i = 0; i < n; ++i)
-    if (io->parent[i] >= n && io->parent[i] < POW_POOL_NONE)
-      return fail(POW_EINVAL, "parent %u of node %zu is neither a node nor an end", io->parent[i], i);
+  if (int rc = check_forest(n, io->parent && io->depth && io->index && io->n_bad, io->parent)) return rc;
   if (n == 0) return POW_OK;
   HIP_OK(hipSetDevice(ctx->device));
   const uint32_t n32 = (uint32_t)n, fin = io->fin, k = io->mode ? (uint32_t)io->k : 0u;
   const PowPoolLivePlan from = pow_pool_live_plan(n32);
   const size_t words = (size_t)n32 * sizeof(uint32_t);
   const size_t up_words = std::max<size_t>((size_t)n32 * pow_pool_lift_rows(n32), 1);
-  uint32_t* base = nullptr;
-  uint32_t* to_base = nullptr;
-  uint32_t* d_up = nullptr;
-  uint32_t* d_find = nullptr;  // the k records, then the roots, as pool_above_run lays them out
   std::vector<PowAboveAcc> acc(std::max<uint32_t>(k, 1));
   PowPoolLiveCtl ctl{};
-  int rc = POW_OK;
-  auto step = [&](hipError_t e, const char* what) {
-    if (rc == POW_OK && e != hipSuccess) rc = fail(POW_EHIP, "%s failed: %s", what, hipGetErrorString(e));
-  };
-  auto release = [&](int waited) {  // after a watchdog the launches may still write
-    if (waited == POW_OK || !ctx->wedged) (void)hipFree(base), (void)hipFree(to_base), (void)hipFree(d_up), (void)hipFree(d_find);
-  };
-  step(hipMalloc(&base, from.words * sizeof(uint32_t)), "hipMalloc");
-  step(hipMalloc(&d_up, up_words * sizeof(uint32_t)), "hipMalloc");
-  step(hipMalloc(&d_find, (5 * (size_t)std::max<uint32_t>(k, 1)) * sizeof(uint32_t)), "hipMalloc");
-  if (rc != POW_OK) {
-    release(POW_OK);
-    return rc;
-  }
+  Frame f(ctx);
+  uint32_t* const base = f.alloc(from.words);
+  uint32_t* const d_up = f.alloc(up_words);
+  uint32_t* const d_find = f.alloc(5 * (size_t)std::max<uint32_t>(k, 1));  // the k records, then the roots, as pool_above_run lays them out
+  if (f.rc != POW_OK) return f.rc;
   const PowPoolDev F = pow_pool_live_dev(base, from, nullptr, n32, 0);
   PowAboveAcc* const d_acc = (PowAboveAcc*)d_find;
   uint32_t* const d_roots = d_find + 4 * (size_t)k;
-  auto up = [&](void* dst, const void* src, size_t bytes) {
-    if (rc == POW_OK && src && bytes) step(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream), "copy in");
-  };
-  auto down = [&](void* dst, const void* src, size_t bytes) {
-    if (rc == POW_OK && dst && bytes) step(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream), "copy out");
-  };
-  step(hipMemsetAsync(base, 0, from.words * sizeof(uint32_t), ctx->stream), "reset");  // status, kind, digests, names
-  step(hipMemsetAsync(d_up, 0xEE, up_words * sizeof(uint32_t), ctx->stream), "reset");  // past every size, as the lift hook's
-  up(F.parent, io->parent, words), up(F.index, io->index, words), up(F.bad[fin], io->n_bad, words);
-  up(F.depth[fin], io->depth, words), up(d_roots, io->roots, (size_t)k * sizeof(uint32_t));
+  f.step(hipMemsetAsync(base, 0, from.words * sizeof(uint32_t), ctx->stream), "reset");  // status, kind, digests, names
+  f.step(hipMemsetAsync(d_up, 0xEE, up_words * sizeof(uint32_t), ctx->stream), "reset");  // past every size, as the lift hook's
+  f.up(F.parent, io->parent, words), f.up(F.index, io->index, words), f.up(F.bad[fin], io->n_bad, words);
+  f.up(F.depth[fin], io->depth, words), f.up(d_roots, io->roots, (size_t)k * sizeof(uint32_t));
   uint32_t launches = 0;
   uint64_t work = 0;
-  if (rc == POW_OK && io->mode == 0u) step(pow_queue_pool_tips(ctx->stream, F, fin, io->flags), "K14a, K14b, K12c, K12d, K14c");
-  if (rc == POW_OK && io->mode) {
+  if (f.rc == POW_OK && io->mode == 0u) f.step(pow_queue_pool_tips(ctx->stream, F, fin, io->flags), "K14a, K14b, K12c, K12d, K14c");
+  if (f.rc == POW_OK && io->mode) {
     const PowLiftView v{F.parent, F.depth[fin], d_up, n32, n32, pow_pool_rounds(n32)};
-    step(pow_queue_pool_lift(ctx->stream, F.parent, d_up, n32, 0, n32, true, &launches, &work), "K13a");
-    if (rc == POW_OK) step(pow_queue_pool_above(ctx->stream, F, fin, v, d_roots, k, d_acc, true, io->mode == 2u), "K14d, K12c, K12d");
-    down(acc.data(), d_acc, (size_t)k * sizeof(PowAboveAcc));
+    f.step(pow_queue_pool_lift(ctx->stream, F.parent, d_up, n32, 0, n32, true, &launches, &work), "K13a");
+    if (f.rc == POW_OK) f.step(pow_queue_pool_above(ctx->stream, F, fin, v, d_roots, k, d_acc, true, io->mode == 2u), "K14d, K12c, K12d");
+    f.down(acc.data(), d_acc, (size_t)k * sizeof(PowAboveAcc));
   }
-  down(&ctl, F.ctl, sizeof ctl), down(io->marks, F.depth[fin ^ 1u], n);
+  f.down(&ctl, F.ctl, sizeof ctl), f.down(io->marks, F.depth[fin ^ 1u], n);
   // the list comes down whole: what lies past the total is scratch, and the caller's array has room for n
-  if (io->mode == 0u) down(io->list, F.next[0], words);
-  int waited = pow_ctx_stream_wait(ctx, "pow_test_pool_above", 100ull * (work + (uint64_t)n32 * (k + 5ull)));
-  if (rc == POW_OK) rc = waited;
-  if (rc == POW_OK && ctl.marked > n32) rc = fail(POW_EHIP, "K12d counted %u marks on %u nodes", ctl.marked, n32);
-  if (rc != POW_OK) {
-    release(waited);
-    return rc;
-  }
+  if (io->mode == 0u) f.down(io->list, F.next[0], words);
+  if (f.wait("pow_test_pool_above", 100ull * (work + (uint64_t)n32 * (k + 5ull))) != POW_OK) return f.rc;
   const uint32_t kept = ctl.marked;
+  if (kept > n32) return fail(POW_EHIP, "K12d counted %u marks on %u nodes", kept, n32);
   if (io->total) *io->total = kept;
   for (uint32_t q = 0; q < k; ++q) {
     if (io->size) io->size[q] = acc[q].size;
     if (io->height) io->height[q] = acc[q].height;
     if (io->best) io->best[q] = acc[q].best;
   }
-  if (io->mode != 2u) {
-    release(waited);
-    return rc;
-  }
-  if (kept >= n32) {  // a root is a member of its own subtree
-    release(waited);
-    return fail(POW_EHIP, "K14d kept all %u nodes under %u roots", n32, k);
-  }
-  const uint32_t cap = pow_pool_prune_cap(kept, pow_pool_live_first_cap(0, ctx->pool_first_cap));
-  const PowPoolLivePlan to = pow_pool_live_plan(cap);
-  step(hipMalloc(&to_base, to.words * sizeof(uint32_t)), "hipMalloc");
-  if (rc != POW_OK) {
-    release(POW_OK);
-    return rc;
-  }
-  const PowPoolDev T = pow_pool_live_dev(to_base, to, nullptr, kept, 0);
-  const size_t kw = (size_t)kept * sizeof(uint32_t);
-  step(pow_queue_pool_compact(ctx->stream, F, T, cap, fin, io->map != nullptr), "K12e, K12f");  // no table: no K10b
-  down(io->map, F.next[0], words), down(io->parent_out, T.parent, kw), down(io->depth_out, T.depth[fin], kw);
-  waited = pow_ctx_stream_wait(ctx, "pow_test_pool_above (gather)", 100ull * (n + 2ull * kept));
-  if (rc == POW_OK) rc = waited;
-  release(waited);
-  return rc;
+  if (io->mode != 2u) return POW_OK;
+  if (kept >= n32) return fail(POW_EHIP, "K14d kept all %u nodes under %u roots", n32, k);  // a root is a member of its own subtree
+  return compact_half(f, "pow_test_pool_above (gather)", F, kept, fin, io->map, io->parent_out, io->depth_out,
+                      [](const PowPoolDev&) {});
 }
+

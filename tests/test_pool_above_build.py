@@ -116,7 +116,8 @@ def test_the_untouched_files_and_the_reused_wrappers():
     assert count.index("pow_launch_pool_prune_count(stream, D, fin)") < count.index("pow_launch_pool_prune_scan(stream, D)")
     run, drop = pool_function("pool_above_run"), pool_function("pow_pool_drop")
     assert run.count("pool_lift_update(p, covered, stale, &launches, &work)") == 1
-    assert "pow_queue_pool_compact" not in drop and drop.count("pow_pool_prune(") == 1  # the prune's own second half
+    assert "pow_queue_pool_compact" not in drop and "pow_pool_prune(" not in drop
+    assert drop.count("pool_compact(p, kept, map)") == 1  # the prune's own second half, called as the prune calls it
     assert "hip" not in drop[drop.index("if (k == 0) {"):drop.index("uint32_t kept = 0;")]  # no roots: no GPU work
     for f, launches in (("pow_pool_prune.hip", 6), ("pow_pool_lift.hip", 4)):
         t = open(os.path.join(CSRC, f)).read()
@@ -129,7 +130,7 @@ def test_warmup_does_not_launch_the_kernels():
 
 def test_the_host_side_of_the_three_calls():
     """tips: one timed section.  subtrees: one, pool_above_run's.  drop: that
-    one and the prune's.  No host loop runs over the pool's blocks: the loops
+    one and pool_compact's.  No host loop runs over the pool's blocks: the loops
     are over the roots."""
     tips, subtrees, drop = (pool_function(n) for n in ("pow_pool_tips", "pow_pool_subtrees", "pow_pool_drop"))
     args, run = pool_function("pool_above_args"), pool_function("pool_above_run")
@@ -157,10 +158,13 @@ def test_the_host_side_of_the_three_calls():
         order = [body.index(s) for s in ("!p)", "pool_above_args(p, roots, k)", "pool_ready(", "ctx->stats = pow_stats{}",
                                          "pool_above_run(")]
         assert order == sorted(order)
-    order = [run.index(s) for s in ("RESERVE(t.d_up", "RESERVE(p->d_find", "hipMemcpyHostToDevice", "timed_begin(",
-                                    "pool_lift_update(", "pow_queue_pool_above(", "hipEventRecord(ctx->ev1",
-                                    "hipMemcpyDeviceToHost", "timed_end(", "t.covered = n;")]
+    # the table's step is the K13 queries' (test_pool_lift_build holds its two halves): once in front, once behind
+    order = [run.index(s) for s in ("pool_lift_ready(p, &covered, &stale)", "RESERVE(p->d_find", "hipMemcpyHostToDevice",
+                                    "timed_begin(", "pool_lift_update(", "pow_queue_pool_above(", "hipEventRecord(ctx->ev1",
+                                    "hipMemcpyDeviceToHost", "timed_end(", "pool_lift_commit(p);")]
     assert order == sorted(order) and "launches + (marks ? 3u : 1u), &ctx->stats" in run
+    assert run.count("pool_lift_ready(") == 1 and run.count("pool_lift_commit(") == 1
+    assert "RESERVE(t.d_up" in pool_function("pool_lift_ready") and "t.gen" not in run and "t.covered" not in run
     # the sequences: resets in front, K12c and K12d behind the marks
     order = [q_tips.index(s) for s in ("hipMemsetAsync(D.depth[fin ^ 1u], 0", "pow_launch_pool_above_child(",
                                        "pow_launch_pool_above_tip(", "pow_launch_pool_above_count(",
@@ -170,22 +174,43 @@ def test_the_host_side_of_the_three_calls():
                                         "hipMemsetAsync(D.depth[fin ^ 1u], 1, D.n, stream)", "pow_launch_pool_above_subtree(",
                                         "pow_launch_pool_above_count(")]
     assert order == sorted(order)  # whole words to 0 first, then D.n bytes to 1: the last word's tail stays 0
-    # the drop: dead until its section is through, the hand-over set only around the prune
-    order = [drop.index(s) for s in ("p->dead = true;", "pool_above_run(", "p->dead = false;", "p->keep_ready = true;",
-                                     "pow_pool_prune(p, nullptr, 0, 0, 0, map, info)", "p->keep_ready = false;")]
-    assert order == sorted(order)
+    # the drop: dead from before the keep-marks until the compaction is through, and for good if they kept everything
+    order = [drop.index(s) for s in ("ctx->stats = pow_stats{}", "p->dead = true;", "pool_above_run(",
+                                     "if (kept >= p->size) return fail(POW_EHIP,", "pool_compact(p, kept, map)",
+                                     "p->dead = false;")] + [drop.rindex("return pool_result(p, info);")]
+    assert order == sorted(order) and drop.count("return pool_result(p, info);") == 2  # no roots, and the drop's end
+    assert drop.count("p->dead = true;") == drop.count("p->dead = false;") == drop.count("pow_stats{}") == 1
+    assert "ctx->stats." not in drop  # both sections add into the stats through timed_end: nothing is patched up
+    # no state bit hands one call over to another: the compaction has one statement and two callers, nothing inside
+    # the library calls the public prune, and the mark's section is only the mark's
+    from mpi_blockchain_amd import build
+    from test_build import _strip_comments_and_strings
+    from test_pool_deep_host import function_bodies
+    bodies = function_bodies(_strip_comments_and_strings(open(os.path.join(CSRC, "pow_api.cpp")).read()))
+    assert [fn for fn, body in bodies if "pow_queue_pool_compact(" in body] == ["pool_compact"]
+    assert [fn for fn, body in bodies if re.search(r"\bpool_compact\(", body)] == ["pow_pool_prune", "pow_pool_drop"]
+    for f in build.SOURCES + build.HEADERS:
+        text = open(os.path.join(CSRC, f)).read()
+        assert "keep_ready" not in text, f
+        assert not [fn for fn, body in function_bodies(_strip_comments_and_strings(text)) if "pow_pool_prune(" in body], f
+    for dirpath, _, files in os.walk(CSRC):
+        for f in files:
+            assert "keep_ready" not in open(os.path.join(dirpath, f), errors="replace").read(), f
     mark_run = pool_function("pool_mark_run")
-    assert mark_run.index("if (p->keep_ready) {") < mark_run.index("RESERVE(") and "p->keep_ready = false;" in mark_run
-    assert "if (tips || n_tips || flags || on || p->h_ctl.p->marked >= p->size)" in mark_run  # only the drop's own prune
-    api = open(os.path.join(CSRC, "pow_api.cpp")).read()
-    assert api.count("keep_ready = true") == 1
+    assert "h_ctl.p->marked" not in mark_run and mark_run.index("const uint32_t n = p->size") < mark_run.index("RESERVE(")
+    assert mark_run.count("return POW_OK;") == 1  # one way through
 
 
 def test_the_hook_runs_the_librarys_sequences():
     hooks = open(os.path.join(CSRC, "pow_hooks.cpp")).read()
     body = hooks[hooks.index('extern "C" int pow_test_pool_above('):]
-    for name in QUEUES + ("pow_queue_pool_lift", "pow_queue_pool_compact"):
+    for name in QUEUES + ("pow_queue_pool_lift",):
         assert f"{name}(ctx->stream, " in body, name
+    # ... and the compaction through the second half it shares with the prune's hook
+    half = hooks[hooks.index("int compact_half("):hooks.index("}  // namespace\n\n// The kernels' leading-zero count")]
+    assert "pow_queue_pool_compact(ctx->stream, F, T, cap, fin, map != nullptr)" in half and "pow_launch_pool" not in half
+    assert body.count("compact_half(f, ") == 1 and hooks.count("compact_half(f, ") == 2
+    assert hooks.count("pow_queue_pool_compact(") == 1
     assert "pow_launch_pool" not in body and "hipLaunchKernelGGL" not in hooks
     from mpi_blockchain_amd import build
     assert "pow_hooks.cpp" in build.TEST_ONLY

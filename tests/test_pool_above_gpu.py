@@ -18,8 +18,11 @@ from mpi_blockchain_amd._lib import POW_EINVAL, POW_ENOSPC, PoolInfo, PowError
 from mpi_blockchain_amd.block import POOL_NONE, POOL_ROOT, BlockPool, mine_chain, mine_race, prune_structs
 from mpi_blockchain_amd.miner import GpuMiner, StopBoard
 
+import pool_above_util as au
+import pool_deep_util as du
 import pool_util as pu
-from test_pool_lift_gpu import Table, ask_forks, every_query
+from test_pool_lift_gpu import Table, ask_ancestors, ask_forks, every_query
+from test_pool_prune_gpu import prune_both
 from test_pool_stream_gpu import POISON, compare, feed, last_error
 
 pytestmark = pytest.mark.gpu
@@ -213,6 +216,53 @@ def test_published_shape(miner, race31, order):
         tips = ask_tips(miner, pool, mirror)
         assert len(tips) == 2 * 6 and mirror.index[mirror.best] == mined[0].index + 6  # the losers of the six heights left
         ask_subtrees(miner, pool, mirror, table, range(len(mirror)))
+
+
+def test_a_drop_a_prune_a_drop_and_queries_on_one_pool(miner, race31):
+    """The drop and the prune share their second half and nothing else: a
+    drop, a plain prune with tips and flags, a second drop and K13 queries on
+    one pool, each against the mirror (do_drop, prune_both and ask_ancestors
+    hold the launches' closed forms) and against the numpy statements over the
+    arrays the pool gave before the call."""
+    blocks, won, lost = race31
+
+    def arrays():
+        r = pool.read()
+        return r.parent, r.depth, np.array(mirror.index, dtype=np.uint32), r.n_bad
+
+    def drop(structs, root):
+        parent, depth, index, n_bad = arrays()
+        on = au.subtrees_of(parent, depth, index, n_bad, [root])[3]
+        _, want_parent, want_depth = au.dropped(parent, depth, 1 - on)
+        left = do_drop(miner, pool, mirror, table, structs, [root], 4)
+        assert len(left) == len(structs) - int(on.sum()) and miner.stats()["kernel_ms"] > 0
+        assert all(a is b for a, b in zip(left, [s for s, gone in zip(structs, on) if not gone]))
+        after = pool.read()
+        assert after.parent.tolist() == want_parent.tolist() and after.depth.tolist() == want_depth.tolist()
+        return left
+
+    pool, mirror, _ = feed(miner, [blocks], 4)
+    with pool:
+        table = Table()
+        structs = drop(list(blocks), lost[7])                       # the table from nothing: rows(31) + 3 + 3 launches
+        assert len(structs) == 30
+        # a plain prune: one low loser as a tip, and every sound block of the two greatest heights by index
+        tip, min_index = mirror.find(pu.name_of(blocks[lost[3]])), blocks[0].index + 9
+        parent, depth, index, n_bad = arrays()
+        seeds = sorted({tip} | set(np.flatnonzero((index >= min_index) & (n_bad == 0)).tolist()))
+        kept, want = du.map_of(du.marks_of(parent, depth, seeds))
+        structs, new, info = prune_both(miner, pool, mirror, structs, ([tip], min_index, True))
+        assert new == want.tolist() and 0 < kept == len(structs) == info["size"] < 30
+        table.pruned(True)
+        structs = drop(structs, mirror.find(pu.name_of(blocks[won[8]])))  # the table went with the prune: from nothing
+        assert 0 < len(structs) < kept
+        _, steps = every_query(mirror)
+        ask_ancestors(miner, pool, mirror, table, steps)             # made again behind the drop, then up to date
+        parent = pool.read().parent
+        for (p, s), got in zip(steps, pool.ancestors([p for p, _ in steps], [s for _, s in steps]).tolist()):
+            walk, end = du.plain_walk(parent, p)
+            assert got == (walk[s] if s < len(walk) else end), (p, s)
+        assert miner.stats()["launches"] == 1 and pool.lift_info()["covered"] == len(structs)
 
 
 # ---- the tree of 40: two roots, branches of several depths ----

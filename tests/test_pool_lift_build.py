@@ -70,7 +70,7 @@ def test_no_null_stream_in_lift_sources():
     assert kernel.count("__launch_bounds__(256)") == 4 and kernel.count("dim3(256), 0, stream") == 4
     bodies = {name: pool_function(name) for name in ("pow_pool_ancestors", "pow_pool_fork_points", "pow_pool_chain",
                                                      "pow_pool_lift_get_info", "pool_lift_args", "pool_lift_update",
-                                                     "pool_lift_run")}
+                                                     "pool_lift_run", "pool_lift_ready")}
     bodies["pow_queue_pool_lift"] = pool_function("pow_queue_pool_lift", "hipError_t")
     for name, body in bodies.items():
         assert not null_stream_calls(body), name
@@ -133,10 +133,29 @@ def test_the_host_side_of_the_query_calls():
     assert order == sorted(order)
     assert "have = stale ? 0u : pow_pool_lift_rows(covered), rows = pow_pool_lift_rows(n)" in queue
     assert run.count("hipMemcpyAsync(") == 2  # the arguments up in one copy, the results down in one
-    order = [run.index(s) for s in ("RESERVE(t.d_up", "RESERVE(p->d_find", "hipMemcpyHostToDevice", "timed_begin(",
-                                    "pool_lift_update(", "pow_launch_pool_lift_fork(", "pow_launch_pool_lift_ancestor(",
-                                    "hipEventRecord(ctx->ev1", "hipMemcpyDeviceToHost", "timed_end(", "t.covered = n;")]
+    order = [run.index(s) for s in ("pool_lift_ready(p, &covered, &stale)", "RESERVE(p->d_find", "hipMemcpyHostToDevice",
+                                    "timed_begin(", "pool_lift_update(", "pow_launch_pool_lift_fork(",
+                                    "pow_launch_pool_lift_ancestor(", "hipEventRecord(ctx->ev1", "hipMemcpyDeviceToHost",
+                                    "timed_end(", "pool_lift_commit(p);")]
     assert order == sorted(order)
+    # the table's step, stated once for this run and K14's: made ready in front of the timed section (what the update
+    # starts from, the table at the pool's capacity, nothing covered meanwhile), committed behind the wait
+    ready, commit = pool_function("pool_lift_ready"), api_function("pool_lift_commit", POOL_API, "void")
+    stale = api_function("pool_lift_stale", POOL_API, "bool")
+    order = [ready.index(s) for s in ("*stale = pool_lift_stale(p);", "if (t.capacity < p->plan.cap) {", "t.release_table();",
+                                      "RESERVE(t.d_up, (size_t)p->plan.cap * pow_pool_lift_rows(p->plan.cap));",
+                                      "t.capacity = p->plan.cap;", "*covered = *stale ? 0u : t.covered;", "t.covered = 0;")]
+    assert order == sorted(order) and "timed_" not in ready + commit + stale and "for (" not in ready + commit + stale
+    assert "p->lift.covered = p->size;" in commit and "p->lift.gen = p->gen;" in commit
+    assert "t.covered == 0 || t.capacity == 0 || t.gen != p->gen || t.covered > p->size || p->plan.cap > t.capacity" in stale
+    api = open(os.path.join(CSRC, POOL_API)).read()
+    assert api.count("t.gen != p->gen") == 1 and len(re.findall(r"\bgen [!=]= p->gen", api)) == 1  # one predicate
+    assert api.count("pool_lift_stale(p)") == 2 and api.count("RESERVE(t.d_up") == 1
+    for user in (run, pool_function("pool_above_run")):
+        assert user.count("pool_lift_ready(") == 1 and user.count("pool_lift_commit(") == 1
+        assert user.index("pool_lift_ready(") < user.index("RESERVE(p->d_find") < user.index("timed_begin(")
+        assert user.index("timed_end(") < user.index("pool_lift_commit(")
+        assert "t.gen" not in user and "t.covered" not in user and "release_table" not in user
     # pow_stats.launches is the count of what was queued: every launcher call in the sequence is counted exactly
     # once, and pool_lift_run hands that count (and the query launch) to timed_end ...
     launchers = re.findall(r"pow_launch_pool_lift_\w+\(", queue)
@@ -162,6 +181,7 @@ def test_the_host_side_of_the_query_calls():
         assert order == sorted(order), name
     info = pool_function("pow_pool_lift_get_info")
     assert "hip" not in info and "ctx" not in info  # no GPU work
+    assert "covered = pool_lift_stale(p) ? 0u : t.covered;" in info and "gen" not in info  # fresh by the same predicate
 
 
 def test_the_table_is_one_member_and_the_generation_has_two_bumps():
@@ -172,8 +192,9 @@ def test_the_table_is_one_member_and_the_generation_has_two_bumps():
     assert api.count("++p->gen") == 2
     fill = api[api.index("static void pool_fill_info("):]
     assert "if (reranked) ++p->gen;" in fill[:fill.index("\n}\n")]
-    prune = pool_function("pow_pool_prune")
-    assert prune.count("p->lift.release_table(), ++p->gen;") == 1  # the prune gives the table's memory back
-    assert prune.index("timed_end(") < prune.index("p->lift.release_table(), ++p->gen;") < prune.index("p->size = kept;")
+    compact = pool_function("pool_compact")  # the prune's second half, and the drop's
+    assert compact.count("p->lift.release_table(), ++p->gen;") == 1  # it gives the table's memory back
+    assert api.count("p->lift.release_table(), ++p->gen;") == 1
+    assert compact.index("timed_end(") < compact.index("p->lift.release_table(), ++p->gen;") < compact.index("p->size = kept;")
     add = pool_function("pow_pool_add")
     assert "lift" not in add and "gen" not in add  # the add launches nothing new: the bump is pool_fill_info's

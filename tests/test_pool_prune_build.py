@@ -69,7 +69,8 @@ def test_no_null_stream_in_prune_sources():
     assert kernel.count("hipLaunchKernelGGL(") == 6 and kernel.count("__global__") == 6
     assert "<<<" not in kernel and "hipGraph" not in kernel
     assert kernel.count("__launch_bounds__(256)") == 6 and kernel.count("dim3(256), 0, stream") == 6
-    bodies = {name: pool_function(name) for name in ("pow_pool_mark", "pow_pool_prune", "pool_mark_run", "pool_mark_args")}
+    bodies = {name: pool_function(name) for name in ("pow_pool_mark", "pow_pool_prune", "pool_mark_run", "pool_mark_args",
+                                                     "pool_compact")}
     bodies.update({name: pool_function(name, "hipError_t") for name in QUEUES})
     for name, body in bodies.items():
         assert not null_stream_calls(body), name
@@ -126,14 +127,14 @@ def test_the_pool_has_no_new_holder_and_k10_k11_are_as_they_were():
 
 def test_the_host_side_of_both_calls():
     """mark: one timed section.  prune: that one and, if it drops and keeps,
-    a second; the old arrays wait until its wait has passed.  No host loop
+    a second (pool_compact); the old arrays wait until its wait has passed.  No host loop
     runs over the pool's blocks: the one loop is the check of the tips."""
     args, run = pool_function("pool_mark_args"), pool_function("pool_mark_run")
-    mark, prune = pool_function("pow_pool_mark"), pool_function("pow_pool_prune")
+    mark, prune, compact = pool_function("pow_pool_mark"), pool_function("pow_pool_prune"), pool_function("pool_compact")
     q_mark, q_compact = (pool_function(name, "hipError_t") for name in QUEUES)
     assert re.findall(r"\bfor \(([^;]*);", args) == ["size_t k = 0"] and "k < n_tips" in args
     assert re.findall(r"\bfor \(([^;]*);", q_mark) == ["uint32_t r = 0"]
-    for body in (mark, prune, run, q_compact):
+    for body in (mark, prune, compact, run, q_compact):
         assert "for (" not in body and "while" not in body and "std::vector" not in body and "std::iota" not in body
     assert run.count("timed_begin(") == 1 and run.count("timed_end(") == 1
     # the caller's part of the mark's section ...
@@ -152,13 +153,18 @@ def test_the_host_side_of_both_calls():
         assert "ctx" not in body and "pow_pool*" not in body  # a stream and views, never a pool
     assert "3u + rounds, &ctx->stats" in run
     assert mark.count("pool_mark_run(") == 1 and "timed_begin(" not in mark and "hipMalloc" not in mark
-    assert prune.count("pool_mark_run(") == 1 and prune.count("timed_begin(") == 1 and prune.count("timed_end(") == 1
-    order = [prune.index(s) for s in ("pool_mark_run(", "pool_retire(p->d_arr, p->d_old_arr, to.words)",
-                                      "pool_retire(p->d_table, p->d_old_table, slots)", "timed_begin(",
-                                      "pow_queue_pool_compact(ctx->stream, F, T, cap, p->fin, map != nullptr)",
-                                      "hipEventRecord(ctx->ev1",
-                                      "sizeof(PowPoolLiveCtl), hipMemcpyDeviceToHost", "timed_end(",
-                                      "p->d_old_arr.release(), p->d_old_table.release();", "p->dead = false;")]
+    assert prune.count("pool_mark_run(") == 1 and "timed_" not in prune and "pool_retire(" not in prune
+    assert compact.count("timed_begin(") == 1 and compact.count("timed_end(") == 1 and "p->dead" not in compact
+    order = [prune.index(s) for s in ("pool_mark_run(", "if (kept >= n) {", "} else if (int rc = pool_compact(p, kept, map)) {",
+                                      "p->dead = false;", "return pool_result(p, info);")]
+    assert order == sorted(order) and prune.count("pool_compact(") == 1
+    order = [compact.index(s) for s in ("pool_retire(p->d_arr, p->d_old_arr, to.words)",
+                                        "pool_retire(p->d_table, p->d_old_table, slots)", "timed_begin(",
+                                        "pow_queue_pool_compact(ctx->stream, F, T, cap, p->fin, map != nullptr)",
+                                        "hipEventRecord(ctx->ev1",
+                                        "sizeof(PowPoolLiveCtl), hipMemcpyDeviceToHost", "timed_end(",
+                                        "p->d_old_arr.release(), p->d_old_table.release();", "p->size = kept;",
+                                        "pool_fill_info(p, *ctl, 0, false, true);")]
     assert order == sorted(order)
     retire = pool_function("pool_retire")  # what each of the two lines above does: the old buffer kept, a new one made
     order = [retire.index(s) for s in ("old = d_new;", "d_new = DevBuf<uint32_t>{};", "RESERVE(d_new, n);")]
@@ -168,9 +174,10 @@ def test_the_host_side_of_both_calls():
                                           "if (T.table) QUEUE_OK(pow_launch_pool_insert(stream, T))",
                                           "} else if (want_map) {", "hipMemsetD32Async((hipDeviceptr_t)F.next[0], (int)POW_POOL_NONE, F.n")]
     assert order == sorted(order)
-    # the prune's T is the survivors' view with the new table: T.n = kept, T.slots = slots
-    assert "T = pow_pool_live_dev(p->d_arr.p, to, p->d_table.p, kept, slots)" in prune
-    assert "pow_pool_prune_cap(kept, pow_pool_live_first_cap(0, ctx->pool_first_cap))" in prune
-    assert "pow_pool_prune_slots(cap, kept, ctx->pool_slots_log2)" in prune
-    assert "HostToDevice" not in prune and "padded_message" not in prune and "verify_tiles" not in prune  # no struct goes up
+    # the compaction's T is the survivors' view with the new table: T.n = kept, T.slots = slots
+    assert "T = pow_pool_live_dev(p->d_arr.p, to, p->d_table.p, kept, slots)" in compact
+    assert "pow_pool_prune_cap(kept, pow_pool_live_first_cap(0, ctx->pool_first_cap))" in compact
+    assert "pow_pool_prune_slots(cap, kept, ctx->pool_slots_log2)" in compact
+    for body in (prune, compact):  # no struct goes up
+        assert "HostToDevice" not in body and "padded_message" not in body and "verify_tiles" not in body
     assert prune.index("p->dead = true;") < prune.index("pool_mark_run(")
